@@ -29,6 +29,10 @@ keys (metric, value, unit, n_gpus, steps, warmup, ms_per_step, higher_is_better,
 it all as one 30 KB line, which the driver could not parse.  The certificate at tol = 1e-4 includes the ELEMENT-WISE bar of the exact path
 (rtol = atol = 1e-4 on every tap and every equaliser-output sample).
 
+`--dump-outputs DIR` writes what the headline path returned for its last timed step (rank 0: taps, error traces, equaliser output, phase,
+recovered output, test-angle indices, step sizes) as DIR/<name>.npy, float32 / float64, at most 64 MB (`dump_files`).  The captures depend on
+the arguments only, so two builds run with the same arguments can be compared file by file.
+
 The full result (N = 1, workload c3) additionally carries
   tier_b_loose  the same solver held to tol = 1e-2 (the SER-equivalent tier), informational
   cert_24dB     the same shape at 24 dB SNR, where both paths make thousands of symbol errors: counts within 3 sigma per mode
@@ -142,9 +146,10 @@ def stage_list(rx):
     return names, fns
 
 
-def timed_steps(rx, steps, warmup, barrier_sync, overlap=False, pool=None):
+def timed_steps(rx, steps, warmup, barrier_sync, overlap=False, pool=None, after=None):
     """W warm-up passes, then exactly K passes bracketed by barrier + device sync; HIP events between the stages.  Returns
-    (elapsed s, mean stage ms, per-step pass kernel ms of tier b).
+    (elapsed s, mean stage ms, per-step pass kernel ms of tier b).  after(rx): called right behind the timed region, while the receiver still
+    holds the results of the last timed pass.
 
     overlap: consecutive passes as ResidentReceiver.run(overlap=True) enqueues them - the phase search of pass k on stream 2 beside the
     training of pass k + 1 (the last one flushed inside the timed region).  The stage times are then event pairs on the stream the stage
@@ -193,6 +198,8 @@ def timed_steps(rx, steps, warmup, barrier_sync, overlap=False, pool=None):
         rx.wait_post(marker(steps))
         barrier_sync()
         elapsed = time.perf_counter() - t0
+        if after:
+            after(rx)
         if pool:
             # back to the pool's first capture (the one the exact path, the CPU legs and the SER harness work on): one untimed pass, so that the results,
             # reports and deviations read after this call belong to it
@@ -222,13 +229,16 @@ def timed_steps(rx, steps, warmup, barrier_sync, overlap=False, pool=None):
                 acq_ms[j - 1].append(a)
     barrier_sync()
     elapsed = time.perf_counter() - t0
+    if after:
+        after(rx)
     stage_ms = [float(np.mean([ev[k][j + 1].elapsed_ms(ev[k][j]) for k in range(steps)])) for j in range(len(fns))]
     return elapsed, stage_ms, pass_ms, acq_ms
 
 
-def timed_group(group, steps, warmup, barrier_sync, overlap=True, pool=None):
+def timed_group(group, steps, warmup, barrier_sync, overlap=True, pool=None, after=None):
     """timed_steps for a pipeline.ReceiverGroup: exactly K passes in total, dealt round robin to the receivers (each on its own host thread and
     library streams), bracketed by barrier + device sync; HIP events on the stream every stage ran on, from all receivers.
+    after(rx): as in timed_steps, on the thread of the receiver that ran the last timed pass.
     pool: resident captures rotated through the receivers (pass k of receiver i is capture (i + k n) mod len(pool) of the pool: consecutive passes of
     the job are consecutive, DIFFERENT captures), handed over as references like timed_steps does."""
     from qampy_amd import _lib
@@ -278,6 +288,8 @@ def timed_group(group, steps, warmup, barrier_sync, overlap=True, pool=None):
     group.run(steps, overlap=overlap, mark=mark, prefetch=overlap, feed=feed)
     barrier_sync()
     elapsed = time.perf_counter() - t0
+    if after:
+        group.map(after, which=[(steps - 1) % n])
     if pool:
         group.map(to_first)
     full = [d for d in marks.values() if "apply" in d]
@@ -484,10 +496,10 @@ def transfer_times(sig, rx):
 
 
 # ------------------------------------------------------------------------------------------------------------ config 5
-def pilot_chain(cap, dtype=np.complex64, frames=None):
+def pilot_chain(cap, dtype=np.complex64, frames=None, keep=False):
     """BASELINE config 5 through the basic API (host arrays in and out): sync2frame -> corr_foe -> pilot_equaliser_nframes (data-aided
     second stage, filter over every frame; from the second frame on the frames' pilot-aided sweeps train together: one launch per stage
-    over all (frame, mode) chains) -> pilot_cpe over all frames; returns stage times and results."""
+    over all (frame, mode) chains) -> pilot_cpe over all frames; returns stage times and results (keep: with the arrays the calls returned)."""
     from qampy_amd import equalisation, phaserec
     from qampy_amd.signals import PilotSignal
     sig = PilotSignal(cap["E"].astype(dtype), cap["M"], cap["fb"], cap["fs"], cap["frame_len"], cap["seq_len"], cap["ins_rat"], cap["pilots"],
@@ -506,9 +518,12 @@ def pilot_chain(cap, dtype=np.complex64, frames=None):
     out, ph = phaserec.pilot_cpe(eq, N=5, use_seq=False, nframes=len(frames))
     t.append(time.perf_counter())
     d = np.diff(t)
-    return dict(ok=bool(ok), seconds=t[-1] - t[0], frames=len(frames),
-                stages_ms=dict(frame_sync=d[0] * 1e3, foe=d[1] * 1e3, pilot_equaliser_and_filter=d[2] * 1e3, pilot_cpe=d[3] * 1e3),
-                ser=[float(v) for v in out.cal_ser(frames=np.arange(len(frames)))], taps=np.array(taps))
+    res = dict(ok=bool(ok), seconds=t[-1] - t[0], frames=len(frames),
+               stages_ms=dict(frame_sync=d[0] * 1e3, foe=d[1] * 1e3, pilot_equaliser_and_filter=d[2] * 1e3, pilot_cpe=d[3] * 1e3),
+               ser=[float(v) for v in out.cal_ser(frames=np.arange(len(frames)))], taps=np.array(taps))
+    if keep:
+        res["arrays"] = dict(taps=np.array(taps), eq=np.asarray(eq), out=np.asarray(out), ph=np.asarray(ph))
+    return res
 
 
 class _OracleKernels:
@@ -592,10 +607,12 @@ def run_c5(args, cfg):
     cap = synth.make_pilot_capture(M=cfg["M"], frame_len=cfg["nsym"], nframes=args.c5_frames)
     for _ in range(max(args.warmup, 1)):
         pilot_chain(cap)
-    runs = [pilot_chain(cap) for _ in range(args.steps)]
+    runs = [pilot_chain(cap, keep=bool(args.dump_outputs) and k == args.steps - 1) for k in range(args.steps)]
     el = sum(r["seconds"] for r in runs)
     best = runs[-1]
     nfr = best["frames"]
+    if args.dump_outputs:
+        write_dump(dump_files(best.pop("arrays")), args.dump_outputs)
     one = pilot_chain(cap, frames=[0])                      # the same capture, first frame only (what rounds 1-3 timed)
     # the sequential heart of a frame: Niter sweeps x 3 stages x seq_len steps of the exact recurrence with the adaptive step, two modes side by side
     steps_per_frame = 3 * 30 * 1024
@@ -744,9 +761,9 @@ def make_pool(cfg, nsym, rx, first_seed, ncap):
     return pool
 
 
-def run_pair(cfg, sig, nsym, steps, warmup, barrier_sync, pit, exact_steps, tol_check, overlap=False, in_flight=1, pool_n=1, first_seed=1000):
+def run_pair(cfg, sig, nsym, steps, warmup, barrier_sync, pit, exact_steps, tol_check, overlap=False, in_flight=1, pool_n=1, first_seed=1000, after=None):
     """Tier b (timed, `steps` passes) and the exact path beside it on the same resident capture: both blocks, the measured
-    deviation and the certificate.  Returns (tier_b, tier_a, extras for the roofline).
+    deviation and the certificate.  Returns (tier_b, tier_a, extras for the roofline).  after: timed_steps' hook, for tier b's timed passes.
 
     overlap: the timed passes are consecutive captures of a running receiver (ResidentReceiver.run(overlap=True): phase search of pass k
     beside the training of pass k + 1); the same receiver is then timed one capture at a time as well (`one_capture_at_a_time`)."""
@@ -759,13 +776,13 @@ def run_pair(cfg, sig, nsym, steps, warmup, barrier_sync, pit, exact_steps, tol_
         rx = group.rx[0]
         names, _ = stage_list(rx)
         pool = make_pool(cfg, nsym, rx, first_seed, pool_n) if pool_n > 1 else None
-        elapsed, stage_ms, pass_ms, acq_ms = timed_group(group, steps, warmup, barrier_sync, overlap=True, pool=pool)
+        elapsed, stage_ms, pass_ms, acq_ms = timed_group(group, steps, warmup, barrier_sync, overlap=True, pool=pool, after=after)
     else:
         rx = make_receiver(cfg, sig, tier="b", pit=pit)
         rx.load(sig)
         names, _ = stage_list(rx)
         pool = make_pool(cfg, nsym, rx, first_seed, pool_n) if (overlap and pool_n > 1) else None
-        elapsed, stage_ms, pass_ms, acq_ms = timed_steps(rx, steps, warmup, barrier_sync, overlap=overlap, pool=pool)
+        elapsed, stage_ms, pass_ms, acq_ms = timed_steps(rx, steps, warmup, barrier_sync, overlap=overlap, pool=pool, after=after)
     reports = rx.pit_reports()
     pass_all = None
     if group is None and not getattr(rx, "exchanges", None):
@@ -1313,6 +1330,51 @@ def emit(out, detail_path):
     sys.stdout.flush()
 
 
+# ------------------------------------------------------------------------------------------------------------ output dump
+DUMP_MAX_BYTES = 64 << 20          # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 18              # positions kept along the last axis of a longer array (halved until the files fit)
+DUMP_SEED = 1000                   # the sample of an axis of length n: np.random.default_rng([DUMP_SEED, n]) - the same in every run and build
+
+
+def _real_view(a):
+    """float32 / float64 copy of an output array: complex -> trailing axis (real, imaginary); integers -> float64 (exact)."""
+    if np.iscomplexobj(a):
+        return np.stack([a.real, a.imag], axis=-1).astype(np.float64 if a.dtype == np.complex128 else np.float32)
+    return a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+
+
+def dump_files(res):
+    """The arrays a caller of the timed path receives (a dict as ResidentReceiver.fetch() returns it; tuples of per-stage arrays become
+    <name>1, <name>2, ..., tuples of scalars one array) as {file name: float array} within DUMP_MAX_BYTES: an array longer than the sample along
+    its last axis is kept at a fixed, seeded, sorted sample of positions, stored beside it as <name>_sample_index."""
+    arrays = {}
+    for k, v in res.items():
+        if isinstance(v, (tuple, list)) and not all(np.ndim(x) == 0 for x in v):
+            arrays.update(("%s%d" % (k, i + 1), np.asarray(x)) for i, x in enumerate(v))
+        else:
+            arrays[k] = np.asarray(v)
+    sample = DUMP_SAMPLE
+    while sample >= 1024:
+        files = {}
+        for name, a in sorted(arrays.items()):
+            if a.ndim and a.shape[-1] > sample:
+                pos = np.sort(np.random.default_rng([DUMP_SEED, a.shape[-1]]).choice(a.shape[-1], sample, replace=False))
+                files[name] = _real_view(a[..., pos])
+                files[name + "_sample_index"] = pos.astype(np.float64)
+            else:
+                files[name] = _real_view(a)
+        if sum(f.nbytes for f in files.values()) <= DUMP_MAX_BYTES:
+            return files
+        sample //= 2
+    raise ValueError("outputs do not fit into %d bytes" % DUMP_MAX_BYTES)
+
+
+def write_dump(files, path):
+    os.makedirs(path, exist_ok=True)
+    for name, a in files.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1350,7 +1412,12 @@ def main():
     ap.add_argument("--detail-out", default=os.path.join("gpurun_out", "bench_detail.json"),
                     help="file the FULL result goes to (other shapes and tolerances, recipes, per-pass arrays, notes); stdout carries the compact headline line only; '' = no file")
     ap.add_argument("--dry-run", action="store_true", help="no GPU: kernels replaced by a sleep, socket collectives - exercises launcher + reductions")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps: what the headline path returned for its LAST timed step (rank 0), as DIR/<name>.npy in float32 / float64 "
+                         "(complex: trailing axis real, imaginary; long arrays at a fixed seeded sample of positions, <name>_sample_index.npy), <= 64 MB in all")
     args = ap.parse_args()
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs: a dry run computes nothing")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(sys.argv[1:], args.gpus))
@@ -1431,6 +1498,8 @@ def main():
 
     # ---- independent channel per rank (seed 1000 + channel), synthesised on the GPU (or the host), then made resident
     split = args.split_capture and world > 1 and args.tier == "b"
+    dumped = {}                                      # --dump-outputs: the last timed pass's results, reduced to the files at once (dump_files)
+    keep_last = (lambda r: dumped.update(files=dump_files(r.fetch()))) if (args.dump_outputs and rank == 0) else None
     sig = make_input(cfg, nsym, sharding.channel_seed(0 if split else rank), host=args.host_synth)
     tier_a = tier_b = None
     if split:                                        # every rank holds the same capture
@@ -1440,7 +1509,7 @@ def main():
                                   dtype=np.complex64, alphabet=sig.coded_symbols, pit=pit, comm=cm)
         rx.load(sig)
         stage_names, _ = stage_list(rx)
-        elapsed, stage_ms, pass_ms, acq_ms = timed_steps(rx, args.steps, args.warmup, barrier_sync)
+        elapsed, stage_ms, pass_ms, acq_ms = timed_steps(rx, args.steps, args.warmup, barrier_sync, after=keep_last)
         reports = rx.pit_reports()
         errs = [(d["errors"], d["compared"]) for d in rx.ser(sig.symbols, maxlag=256, window=8192, trim=2000)]
         tier_b = tier_b_block(cfg, rx, stage_names, pass_ms, acq_ms, reports, nsym * args.steps / elapsed / 1e6, elapsed / args.steps * 1e3, errs, nsym)
@@ -1450,7 +1519,7 @@ def main():
         for t_ in tol_ladder:
             pit, tol_check = dict(tol=t_), t_
             tier_b, tier_a, ex = run_pair(cfg, sig, nsym, args.steps, args.warmup, barrier_sync, pit, args.exact_steps if world == 1 else 0, tol_check, overlap=overlap, in_flight=args.in_flight,
-                                          pool_n=max(1, args.pool), first_seed=sharding.channel_seed(rank))
+                                          pool_n=max(1, args.pool), first_seed=sharding.channel_seed(rank), after=keep_last)
             if tier_b["certified"] or world > 1:         # (N > 1: every rank must take the same rung - the tightest; its certificate is all-reduced below)
                 break
             tried.append(dict(tol=t_, certified=False, checks=tier_b.get("checks"), passes=[st["P"] for st in tier_b["stages"]], value=tier_b["value"],
@@ -1463,7 +1532,7 @@ def main():
         rx = make_receiver(cfg, sig, tier="a")
         rx.load(sig)
         stage_names, _ = stage_list(rx)
-        elapsed, stage_ms, _, _ = timed_steps(rx, args.steps, args.warmup, barrier_sync)
+        elapsed, stage_ms, _, _ = timed_steps(rx, args.steps, args.warmup, barrier_sync, after=keep_last)
         reports = None
         errs = [(d["errors"], d["compared"]) for d in rx.ser(sig.symbols, maxlag=256, window=8192, trim=2000)] if cfg["A"] else []
         tier_a = dict(method="exact sequential recurrence (reference order of evaluation)", value=round(nsym * args.steps / elapsed / 1e6, 4), unit="MSym/s",
@@ -1536,15 +1605,21 @@ def main():
     uncertified_b = args.tier == "b" and not use_b and tier_a is None       # N > 1 (no exact run beside it) and a stage that did not converge
     head_ms = stage_ms
     if args.tier == "b" and not use_b and tier_a is not None:
-        out["value"] = tier_a["value"]
-        out["ms_per_step"] = tier_a["ms_per_step"]
-        out["stages_ms"] = tier_a["stages_ms"]
-        out["steps"] = tier_a["steps"]
+        # the exact path takes the headline: timed on its own with this run's --steps / --warmup (the block beside tier b ran --exact-steps passes)
+        rxh = make_receiver(cfg, sig, tier="a")
+        rxh.load(sig)
+        el_h, ms_h, _, _ = timed_steps(rxh, args.steps, args.warmup, _lib.sync, after=keep_last)
+        del rxh
+        out["value"] = round(nsym * args.steps / el_h / 1e6, 4)
+        out["ms_per_step"] = round(el_h / args.steps * 1e3, 3)
+        out["stages_ms"] = {n: round(t, 3) for n, t in zip(stage_names, ms_h)}
         out["note"] = "tier b did not certify itself in this run: headline = exact path"
-        head_ms = [tier_a["stages_ms"][n] for n in stage_names]
+        head_ms = ms_h
     if uncertified_b:
         out["note"] = "tier b did NOT certify itself on every rank and no exact path ran beside it (N > 1): value is tier b's, uncertified"
     out["headline_tier"] = "b" if (use_b or uncertified_b) else "a"
+    if dumped:
+        write_dump(dumped.pop("files"), args.dump_outputs)
     out["config"]["tol"] = tol_check if args.tier == "b" else None
     out["config"]["train_mode_detail"] = (
         ("parallel-in-time solver of the reference's recurrence (tier b, tol %g), certified in-run.  Device: estimated rms deviation of the equaliser output from the "

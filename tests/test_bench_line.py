@@ -101,3 +101,29 @@ def test_two_rank_line_under_torchrun_as_the_driver_starts_it(tmp_path):
         assert k in res, k
     assert res["n_gpus"] == 2 and res["ranks_seen"] == 2 and res["steps"] == 3 and res["warmup"] == 1 and len(res["ms_per_step_per_rank"]) == 2
     assert res["value"] == pytest.approx(2 * res["config"]["nsym_per_channel"] * 3 / (res["ms_per_step"] * 3e-3) / 1e6, rel=1e-3)
+
+
+def test_dump_files_are_float_bounded_and_the_same_every_run(tmp_path):
+    """`--dump-outputs`: what ResidentReceiver.fetch() returns at the C3 shape (2^22 symbols, two stages) becomes float32 / float64 files within
+    64 MB; long arrays are kept at a seeded sample of positions that does not change from run to run."""
+    import numpy as np
+    bench = _bench()
+    rng = np.random.default_rng(0)
+
+    def c(*shape):
+        return (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(np.complex64)
+    n = 2 ** 22 - 20
+    res = dict(wxy=c(2, 2, 41), err=(c(2, n - 20), c(2, n - 20)), eq=c(2, n), mu=(np.float32(2e-4), np.float32(2e-4)), out=c(2, n),
+               ph=rng.standard_normal((2, n)).astype(np.float32), idx=rng.integers(0, 64, (2, n)).astype(np.int32))
+    files = bench.dump_files(res)
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert files["wxy"].shape == (2, 2, 41, 2) and np.array_equal(files["wxy"][..., 1], res["wxy"].imag)
+    assert files["mu"].shape == (2,) and set(files) >= {"err1", "err2", "eq", "out", "ph", "idx"}
+    pos = files["out_sample_index"].astype(np.int64)
+    assert np.all(np.diff(pos) > 0) and pos[-1] < n
+    assert np.array_equal(files["out"][..., 0], res["out"][:, pos].real) and np.array_equal(files["idx"], res["idx"][:, pos].astype(np.float64))
+    again = bench.dump_files(res)
+    assert sorted(again) == sorted(files) and all(np.array_equal(again[k], files[k]) for k in files)
+    bench.write_dump(files, str(tmp_path / "d"))
+    assert np.array_equal(np.load(str(tmp_path / "d" / "eq.npy")), files["eq"])
