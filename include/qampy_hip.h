@@ -38,8 +38,9 @@ extern "C" {
  * built against another header fails loudly (compare with qh_abi_version() at load time) instead of passing shifted
  * arguments.  History: 1 = round 1; 2 = round 2 (qh_bps_recover_*_dev gained `angles`, qh_train_equaliser_*_pit_dev takes
  * (gram, opts, report), the *_seg_dev entry points were removed - unversioned at the time); 3 = round 3 (qh_pit_opts:
- * start, dev_safety; qh_pit_report: deviation[]); 4 = qh_pit_opts: adaptive. */
-#define QH_ABI_VERSION 10
+ * start, dev_safety; qh_pit_report: deviation[]); 4 = qh_pit_opts: adaptive; 11 = signal-quality metrics (qh_metrics_*,
+ * qh_soft_l_value_demapper_*, qh_estimate_snr_*, qh_cal_mi_mc_*). */
+#define QH_ABI_VERSION 11
 int qh_abi_version(void);
 
 /* ---- status codes (python shim: 1,2 -> ValueError, 3,4 -> RuntimeError) */
@@ -463,6 +464,46 @@ int qh_ser_c64_dev(const void *E, int64_t N, const int32_t *idx_tx, int nmodes, 
                    int maxlag, int64_t window, int64_t trim, int64_t *result);
 int qh_ser_c128_dev(const void *E, int64_t N, const int32_t *idx_tx, int nmodes, int64_t ntx, const void *symbols, int M,
                     int maxlag, int64_t window, int64_t trim, int64_t *result);
+
+/* ---- signal-quality metrics (metrics.hip).  Reference: the last `#pythran export`s of qampy/core/pythran_dsp.py that
+ * qampy/core/signal_quality.py:27-29 binds - soft_l_value_demapper (:87-104), soft_l_value_demapper_minmax (:106-131),
+ * estimate_snr (:244-286), cal_mi_mc (:289-300), cal_mi_mc_fast (:303-313) - and the metric methods of qampy/signals.py:295-560.
+ * `alphabet` (M,) is the constellation in coded order: point g carries Gray label g, bit k of it (MSB first) is
+ * (g >> (nbits - 1 - k)) & 1, so no bit table is passed (the python layer inverts the reference's bits_map).  M = 2^nbits,
+ * nbits 1..8, for everything that works on bits; M <= 256 for the rest.  Sums are reduced in double in a fixed order:
+ * repeated calls give bit-identical results. */
+/* L (N, nbits) float64: log-likelihood ratios ln P(bit = 1) / P(bit = 0) at linear `snr`; complex64 input is evaluated in
+ * float with each (bit, side) sum shifted by its own minimum distance, so L stays finite far beyond fp32's exp range. */
+int qh_soft_l_value_demapper_c64(const void *rx, int64_t N, int nbits, double snr, const void *alphabet, int M, double *L);
+int qh_soft_l_value_demapper_c128(const void *rx, int64_t N, int nbits, double snr, const void *alphabet, int M, double *L);
+int qh_soft_l_value_demapper_minmax_c64(const void *rx, int64_t N, int nbits, double snr, const void *alphabet, int M, double *L);
+int qh_soft_l_value_demapper_minmax_c128(const void *rx, int64_t N, int nbits, double snr, const void *alphabet, int M, double *L);
+int qh_soft_l_value_demapper_c64_dev(const void *rx, int64_t N, int nbits, double snr, const void *alphabet, int M, int minmax, double *L);
+int qh_soft_l_value_demapper_c128_dev(const void *rx, int64_t N, int nbits, double snr, const void *alphabet, int M, int minmax, double *L);
+/* estimate_snr: result (HOST, 3 doubles) = linear snr, S0, N0.  Classes are the alphabet points tx equals exactly; ntx == N.
+ * An empty class gives NaN (np.mean of an empty selection), as in the reference. */
+int qh_estimate_snr_c64(const void *rx, int64_t N, const void *tx, int64_t ntx, const void *alphabet, int M, double *result);
+int qh_estimate_snr_c128(const void *rx, int64_t N, const void *tx, int64_t ntx, const void *alphabet, int M, double *result);
+/* cal_mi_mc (noise (L,)) and cal_mi_mc_fast (x, tx (L,)): *mi (HOST) in bits per symbol. */
+int qh_cal_mi_mc_c64(const void *noise, int64_t L, const void *alphabet, int M, double N0, double *mi);
+int qh_cal_mi_mc_c128(const void *noise, int64_t L, const void *alphabet, int M, double N0, double *mi);
+int qh_cal_mi_mc_fast_c64(const void *x, const void *tx, int64_t L, const void *alphabet, int M, double N0, double *mi);
+int qh_cal_mi_mc_fast_c128(const void *x, const void *tx, int64_t L, const void *alphabet, int M, double N0, double *mi);
+/* Device-resident forms on one row E (N,) in HBM against idx_tx (ntx,) int32 in HBM (one transmitted mode, e.g. a row of
+ * qh_make_decision_*_dev's output), aligned like qh_ser_*_dev's result: E[i] * j^rot is compared with alphabet[idx_tx[i - lag]]
+ * for i in [trim, N - trim) with 0 <= i - lag < ntx (labels outside [0, M) are skipped).  alphabet (M,) in HBM.
+ * qh_estimate_snr_*_dev: result (HOST, 3 doubles) snr, S0, N0 over that overlap.
+ * qh_metrics_*_dev: one pass, no LLR stored; decisions as qh_ser_*_dev.  counts (HOST, 3 x int64): symbol errors, bit errors,
+ * compared symbols.  sums (HOST, 2 + nbits doubles): sum |t - r|^2; sum log2 sum_j exp(-(|r - s_j|^2 - |r - t|^2) snr) (the fast
+ * MI with N0 = 1 / snr); per bit k sum log2(1 + exp((-1)^b L_k)) with exact (minmax = 0) or max-log (minmax = 1) LLRs at `snr`. */
+int qh_estimate_snr_c64_dev(const void *E, int64_t N, const int32_t *idx_tx, int64_t ntx, const void *alphabet, int M, int rot, int64_t lag,
+                            int64_t trim, double *result);
+int qh_estimate_snr_c128_dev(const void *E, int64_t N, const int32_t *idx_tx, int64_t ntx, const void *alphabet, int M, int rot, int64_t lag,
+                             int64_t trim, double *result);
+int qh_metrics_c64_dev(const void *E, int64_t N, const int32_t *idx_tx, int64_t ntx, const void *alphabet, int M, int rot, int64_t lag,
+                       int64_t trim, double snr, int minmax, int64_t *counts, double *sums);
+int qh_metrics_c128_dev(const void *E, int64_t N, const int32_t *idx_tx, int64_t ntx, const void *alphabet, int M, int rot, int64_t lag,
+                        int64_t trim, double snr, int minmax, int64_t *counts, double *sums);
 
 /* On-device synthesis of an impaired capture (the reference builds its test signals with signals.py,
  * core/resample.py:73-126 and core/impairments.py:94-233): random Gray-labelled M-QAM symbols (Philox, keyed by seed /

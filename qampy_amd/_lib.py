@@ -28,6 +28,8 @@ _BPS = [_vp, _i64, _vp, _i64, _i, _vp, _i, _i, _vp]
 _RECOVER = [_vp, _i, _i64, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]
 _SELECT = [_vp, _i64, _i, _vp, _i64, _vp]
 _DECIDE = [_vp, _i64, _vp, _i, _vp, _vp, _vp]
+_LLR = [_vp, _i64, _i, C.c_double, _vp, _i, _vp]
+_ALIGNED = [_vp, _i64, _vp, _i64, _vp, _i, _i, _i64, _i64]          # row, N, idx_tx, ntx, alphabet, M, rot, lag, trim
 
 
 def _train_sig(mu_ptr, dev=False):
@@ -113,10 +115,18 @@ SIGNATURES = {
     "qh_stream_handle": [C.POINTER(_vp)],
     "qh_ser_c64_dev": [_vp, _i64, _vp, _i, _i64, _vp, _i, _i, _i64, _i64, _vp],
     "qh_ser_c128_dev": [_vp, _i64, _vp, _i, _i64, _vp, _i, _i, _i64, _i64, _vp],
+    "qh_soft_l_value_demapper_c64": _LLR, "qh_soft_l_value_demapper_c128": _LLR,
+    "qh_soft_l_value_demapper_minmax_c64": _LLR, "qh_soft_l_value_demapper_minmax_c128": _LLR,
+    "qh_soft_l_value_demapper_c64_dev": _LLR[:-1] + [_i, _vp], "qh_soft_l_value_demapper_c128_dev": _LLR[:-1] + [_i, _vp],
+    "qh_estimate_snr_c64": [_vp, _i64, _vp, _i64, _vp, _i, _vp], "qh_estimate_snr_c128": [_vp, _i64, _vp, _i64, _vp, _i, _vp],
+    "qh_cal_mi_mc_c64": [_vp, _i64, _vp, _i, C.c_double, _vp], "qh_cal_mi_mc_c128": [_vp, _i64, _vp, _i, C.c_double, _vp],
+    "qh_cal_mi_mc_fast_c64": [_vp, _vp, _i64, _vp, _i, C.c_double, _vp], "qh_cal_mi_mc_fast_c128": [_vp, _vp, _i64, _vp, _i, C.c_double, _vp],
+    "qh_estimate_snr_c64_dev": _ALIGNED + [_vp], "qh_estimate_snr_c128_dev": _ALIGNED + [_vp],
+    "qh_metrics_c64_dev": _ALIGNED + [C.c_double, _i, _vp, _vp], "qh_metrics_c128_dev": _ALIGNED + [C.c_double, _i, _vp, _vp],
 }
 
 PIT_MAXPASS, PIT_MAXCHUNK = 24, 32
-ABI_VERSION = 10             # QH_ABI_VERSION of include/qampy_hip.h
+ABI_VERSION = 11             # QH_ABI_VERSION of include/qampy_hip.h
 
 
 class PitOpts(C.Structure):

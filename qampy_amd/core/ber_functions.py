@@ -76,3 +76,117 @@ def cal_ser_dev(out, idx_tx, alphabet, maxlag=256, window=4096, trim=0):
         res.append(dict(errors=int(h[0]), compared=int(h[1]), ser=float(h[0]) / max(int(h[1]), 1), tx_mode=int(h[2]),
                         rotation=int(h[3]), lag=int(h[4]), window_matches=int(h[5]), window=int(h[6])))
     return res
+
+
+# ------------------------------------------------------------------------------------------------ alignment of tx and rx
+def _adjust_to(data, N, back=True):
+    """``data`` repeated to ``N`` samples (ber_functions.py:309-320): whole copies, then the first ``N mod len`` samples
+    behind them (``back``) or the last ``N mod len`` samples in front of them.  As in the reference, a remainder of 0 in
+    front puts a whole copy there (``data[-0:]`` is all of ``data``), and ``N < 0`` gives the remainder alone."""
+    n = data.shape[0]
+    copies, rem = N // n, N % n
+    body = np.concatenate([data] * copies) if copies > 0 else np.array([], dtype=data.dtype)
+    return np.hstack([body, data[:rem]]) if back else np.hstack([data[-rem:], body])
+
+
+def _extend_to(short, N, offset):
+    """``short`` made periodic to ``N`` samples with its start ``offset`` samples in."""
+    if offset == 0:
+        return _adjust_to(short, N)
+    head = _adjust_to(short, offset, back=False)
+    return np.hstack([head, _adjust_to(short, N - head.shape[0])])
+
+
+def adjust_data_length(data_tx, data_rx, method=None, offset=0):
+    """
+    Bring ``data_tx`` and ``data_rx`` to a common length (ber_functions.py:248-307).
+
+    ``"truncate"``: cut the longer one.  ``"extend"``: repeat the shorter one periodically, its start ``offset`` samples into
+    the other.  ``None``: only ``data_tx`` changes - cut if longer, repeated if shorter.
+    """
+    ntx, nrx = len(data_tx), len(data_rx)
+    if method is None:
+        if ntx > nrx:
+            return data_tx[:nrx], data_rx
+        if ntx < nrx:
+            if offset == 0:
+                return _adjust_to(data_tx, nrx), data_rx
+            return np.hstack([_adjust_to(data_tx, offset, back=False), _adjust_to(data_tx, nrx - offset)]), data_rx
+        return data_tx, data_rx
+    if method == "truncate":
+        n = min(ntx, nrx)
+        return (data_tx[:n] if ntx > n else data_tx), (data_rx[:n] if nrx > n else data_rx)
+    if method == "extend":
+        if ntx > nrx:
+            return data_tx, _extend_to(data_rx, ntx, offset)
+        if ntx < nrx:
+            return _extend_to(data_tx, nrx, offset), data_rx
+        return data_tx, data_rx
+    return None
+
+
+def sync_and_adjust(data_tx, data_rx, adjust="tx"):
+    """
+    Line up one received row with one transmitted row and give them a common length (ber_functions.py:108-160).
+
+    The offset and the quarter turn come from :func:`find_sequence_offset_complex`; the sequence named by ``adjust`` is
+    rotated, rolled or made periodic around the other one.  Returns ``((tx, rx), peak)``, ``peak`` the correlation
+    maximum the mode assignment of ``SignalQAM._sync_and_adjust`` compares.
+    """
+    assert adjust in ("tx", "rx"), "adjust need to be either 'tx' or 'rx'"
+    ntx, nrx = data_tx.shape[0], data_rx.shape[0]
+    if adjust == "tx":
+        offset, tx, _, peak = find_sequence_offset_complex(data_rx, data_tx)
+        if ntx > nrx:
+            return adjust_data_length(np.roll(tx, offset), data_rx, method="truncate"), peak
+        if ntx < nrx:
+            return adjust_data_length(tx, data_rx, method="extend", offset=offset), peak
+        return (np.roll(tx, offset), data_rx), peak
+    offset, rx, _, peak = find_sequence_offset_complex(data_tx, data_rx)
+    if ntx > nrx:
+        return adjust_data_length(data_tx, rx, method="extend", offset=offset), peak
+    if ntx < nrx:
+        return adjust_data_length(data_tx, np.roll(rx, offset), method="truncate"), peak
+    return (data_tx, np.roll(rx, offset)), peak
+
+
+# ------------------------------------------------------------------------------------------------ device-resident metrics
+def cal_metrics_dev(out, idx_tx, alphabet, snr_db=None, maxlag=256, window=4096, trim=0, llr_minmax=False):
+    """
+    Signal-quality metrics of recovered rows that live in HBM: SER, BER, EVM, SNR estimate, GMI (exact or max-log LLRs) and
+    the fast MI, without moving the rows or any LLR to the host.
+
+    Each row is aligned as :func:`cal_ser_dev` aligns it (its tx mode, quarter turn and lag); then, over the compared
+    overlap, the SNR is estimated from the known symbols (``qh_estimate_snr_*_dev``, what ``SignalQAM.est_snr`` does) unless
+    ``snr_db`` is given, and one fused pass (``qh_metrics_*_dev``) counts symbol / bit errors and sums the error power,
+    the per-bit GMI terms at that SNR and the MI terms at ``N0 = 1 / snr`` (what ``cal_gmi`` / ``cal_mi`` do).
+
+    Returns one dict per row: ``ser, ber, evm, snr, s0, n0, gmi, gmi_per_bit, mi, errors, bit_errors, compared, tx_mode,
+    rotation, lag`` (``snr`` linear; ``s0`` / ``n0`` NaN when ``snr_db`` is given).
+    """
+    from .. import _lib
+    suf = "c64" if np.dtype(out.dtype) == np.complex64 else "c128"
+    nrows, N = out.shape
+    nmodes, ntx = idx_tx.shape
+    M = int(np.prod(alphabet.shape))
+    nbits = int(np.log2(M))
+    res = []
+    for r, al in enumerate(cal_ser_dev(out, idx_tx, alphabet, maxlag, window, trim)):
+        row, tx = out.row(r).ptr, idx_tx.row(al["tx_mode"]).ptr
+        aligned = (al["rotation"], al["lag"], int(trim))
+        if snr_db is None:
+            est = np.zeros(3, np.float64)
+            _lib.call("qh_estimate_snr_%s_dev" % suf, row, N, tx, ntx, alphabet.ptr, M, *aligned, _lib.ptr(est))
+            snr, s0, n0 = (float(v) for v in est)
+        else:
+            snr, s0, n0 = 10 ** (float(snr_db) / 10), float("nan"), float("nan")
+        counts, sums = np.zeros(3, np.int64), np.zeros(2 + nbits, np.float64)
+        _lib.call("qh_metrics_%s_dev" % suf, row, N, tx, ntx, alphabet.ptr, M, *aligned, snr, int(bool(llr_minmax)), _lib.ptr(counts),
+                  _lib.ptr(sums))
+        n = max(int(counts[2]), 1)
+        gmi_per_bit = 1 - sums[2:] / n
+        res.append(dict(ser=int(counts[0]) / n, ber=int(counts[1]) / (n * nbits), evm=float(np.sqrt(sums[0] / n)), snr=snr, s0=s0, n0=n0,
+                        gmi=float(np.sum(gmi_per_bit)), gmi_per_bit=gmi_per_bit, mi=float(np.log2(M) - sums[1] / n),
+                        errors=int(counts[0]), bit_errors=int(counts[1]), compared=int(counts[2]), tx_mode=al["tx_mode"],
+                        rotation=al["rotation"], lag=al["lag"]))
+    return res

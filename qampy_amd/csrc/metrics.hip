@@ -1,0 +1,604 @@
+// Signal-quality metrics on the device: soft demapper (LLRs), GMI, MI, BER / SER / EVM of an aligned row and the
+// data-aided SNR estimate.  Reference: pythran_dsp.soft_l_value_demapper / _minmax (qampy/core/pythran_dsp.py:87-131),
+// estimate_snr (:244-286), cal_mi_mc / cal_mi_mc_fast (:289-313) and their callers cal_gmi / cal_mi / cal_ber / cal_evm
+// (qampy/signals.py:340-560).
+//
+// Bit labels need no table: point g of the alphabet (coded order) carries Gray label g, bit k (MSB first) is
+// (g >> (nbits - 1 - k)) & 1.  The kernels are templated on nbits, so each (bit, side) subset is fixed at compile time.
+//
+// Range of the exact LLR.  L = ln sum_{bit=1} exp(-snr d_g) - ln sum_{bit=0} exp(-snr d_g) (d_g = |s_g - r|^2).  In
+// complex64 each (bit, side) sum is shifted by that subset's own minimum distance m, so its largest term is 1 and the sum
+// never underflows: L = snr (m_0 - m_1) + ln S'_1 - ln S'_0 - nbits * M exp2 per symbol.  complex128 shifts by the global
+// minimum only (M exp per symbol); its range then matches (and exceeds) the reference's unshifted double sums.
+//
+// Reductions are in double: per-block partials in a fixed order, then a fixed-order final sum (reduce_partials), so
+// repeated calls give bit-identical results (the class statistics of the SNR estimate too: each class is added by one
+// owner thread in index order).
+#include "common.h"
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+namespace qh {
+namespace {
+
+constexpr int MET_THREADS = 256, MET_MAXBLK = 1024, MET_NBMAX = 8;
+constexpr double LOG2E = 1.4426950408889634, LN2 = 0.6931471805599453;
+
+template <typename R> __device__ __forceinline__ R hyp_(R a, R b);
+template <> __device__ __forceinline__ float hyp_<float>(float a, float b) { return hypotf(a, b); }
+template <> __device__ __forceinline__ double hyp_<double>(double a, double b) { return hypot(a, b); }
+__device__ __forceinline__ float exp2_(float x) { return exp2f(x); }
+__device__ __forceinline__ double exp2_(double x) { return exp2(x); }
+__device__ __forceinline__ float log2_(float x) { return log2f(x); }
+__device__ __forceinline__ double log2_(double x) { return log2(x); }
+
+template <typename R> __device__ __forceinline__ R dist2(Cx<R> a, Cx<R> b)
+{
+    const R dx = a.re - b.re, dy = a.im - b.im;
+    return dx * dx + dy * dy;
+}
+
+template <typename R> __device__ __forceinline__ Cx<R> rot90(Cx<R> x, int k)       // x * j^k
+{
+    switch (k & 3) {
+    case 1: return Cx<R>{-x.im, x.re};
+    case 2: return Cx<R>{-x.re, -x.im};
+    case 3: return Cx<R>{x.im, -x.re};
+    default: return x;
+    }
+}
+
+// log2(1 + exp(x)) without overflow (softplus / ln 2)
+__device__ __forceinline__ double softplus2(double x) { return (x > 0 ? x : 0.) * LOG2E + log1p(exp(-fabs(x))) * LOG2E; }
+
+// Per-(bit, side) minimum distances, the global minimum and (DECIDE) the decision of ser.hip: first minimum of |r - s_g|
+// (hypot, as det_symbol_argmin).  sy: the alphabet in LDS.
+template <typename R, int NB, bool DECIDE> struct Scan {
+    R m0[NB], m1[NB], dmin;
+    int idx;
+    __device__ __forceinline__ void run(Cx<R> r, const Cx<R> *sy)
+    {
+        constexpr int M = 1 << NB;
+        const R inf = __builtin_inf();
+#pragma unroll
+        for (int k = 0; k < NB; k++) m0[k] = m1[k] = inf;
+        dmin = inf;
+        R hbest = inf;
+        idx = 0;
+#pragma unroll
+        for (int g = 0; g < M; g++) {
+            const Cx<R> s = sy[g];
+            const R d = dist2(r, s);
+#pragma unroll
+            for (int k = 0; k < NB; k++) {
+                if ((g >> (NB - 1 - k)) & 1) m1[k] = min_(m1[k], d);
+                else m0[k] = min_(m0[k], d);
+            }
+            dmin = min_(dmin, d);
+            if (DECIDE) {
+                const R h = hyp_<R>(r.re - s.re, r.im - s.im);
+                if (h < hbest) { hbest = h; idx = g; }
+            }
+        }
+    }
+};
+
+// Exact LLRs of one symbol from its Scan (see the header comment for the shifts).  Also returns log2 of
+// sum_g exp(-snr (d_g - dmin)), the sum the fast MI needs, at the cost of one more exp2 in complex64.
+template <typename R, int NB, bool DECIDE>
+__device__ __forceinline__ void llr_exact(Cx<R> r, const Cx<R> *sy, R snr, const Scan<R, NB, DECIDE> &sc, R *L, R *log2_all)
+{
+    constexpr int M = 1 << NB;
+    constexpr bool PER_SUBSET = sizeof(R) == 4;
+    const R t = snr * (R)LOG2E;
+    R s0[NB], s1[NB];
+#pragma unroll
+    for (int k = 0; k < NB; k++) s0[k] = s1[k] = 0;
+#pragma unroll
+    for (int g = 0; g < M; g++) {
+        const R d = dist2(r, sy[g]);
+        if (PER_SUBSET) {
+#pragma unroll
+            for (int k = 0; k < NB; k++) {
+                if ((g >> (NB - 1 - k)) & 1) s1[k] += exp2_((sc.m1[k] - d) * t);
+                else s0[k] += exp2_((sc.m0[k] - d) * t);
+            }
+        } else {
+            const R e = exp2_((sc.dmin - d) * t);
+#pragma unroll
+            for (int k = 0; k < NB; k++) {
+                if ((g >> (NB - 1 - k)) & 1) s1[k] += e;
+                else s0[k] += e;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NB; k++) {
+        const R l = (R)LN2 * (log2_(s1[k]) - log2_(s0[k]));
+        L[k] = PER_SUBSET ? snr * (sc.m0[k] - sc.m1[k]) + l : l;
+    }
+    if (PER_SUBSET) {     // bit 0's two sides cover the alphabet; the side holding the global minimum is already shifted by it
+        *log2_all = sc.m0[0] <= sc.m1[0] ? log2_(s0[0] + s1[0] * exp2_((sc.dmin - sc.m1[0]) * t))
+                                         : log2_(s1[0] + s0[0] * exp2_((sc.dmin - sc.m0[0]) * t));
+    } else {
+        *log2_all = log2_(s0[0] + s1[0]);
+    }
+}
+
+// log2 sum_g exp(-(d_g - dmin) / N0) by its own loop (minmax LLRs and the host-array fast MI)
+template <typename R, int M>
+__device__ __forceinline__ R log2_sum_loop(Cx<R> r, const Cx<R> *sy, R dmin, R n0inv_log2e)
+{
+    R s = 0;
+#pragma unroll
+    for (int g = 0; g < M; g++) s += exp2_((dmin - dist2(r, sy[g])) * n0inv_log2e);
+    return log2_(s);
+}
+
+// Block sum of F per-thread doubles into partial[blockIdx.x * F + f] (fixed order: wave DPP tree, then waves 0..3)
+template <int F> __device__ __forceinline__ void block_partials(double *acc, double *partial)
+{
+    __shared__ double wsum[MET_THREADS / 64][F];
+#pragma unroll
+    for (int f = 0; f < F; f++) {
+        const double v = wave_sum(acc[f]);
+        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6][f] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < F) {
+        double s = 0;
+        for (int w = 0; w < MET_THREADS / 64; w++) s += wsum[w][threadIdx.x];
+        partial[(size_t)blockIdx.x * F + threadIdx.x] = s;
+    }
+}
+
+template <typename R, int M> __device__ __forceinline__ void load_alphabet(Cx<R> *sy, const Cx<R> *alphabet)
+{
+    for (int g = threadIdx.x; g < M; g += blockDim.x) sy[g] = alphabet[g];
+    __syncthreads();
+}
+
+// ------------------------------------------------------------------------------------------------ kernels
+// L (N, NB) float64: LLRs of every symbol (soft_l_value_demapper / _minmax)
+template <typename R, int NB, bool MINMAX>
+__global__ void __launch_bounds__(MET_THREADS) llr_kernel(const Cx<R> *E, int64_t N, const Cx<R> *alphabet, R snr, double *L)
+{
+    constexpr int M = 1 << NB;
+    __shared__ Cx<R> sy[M];
+    load_alphabet<R, M>(sy, alphabet);
+    for (int64_t i = (int64_t)blockIdx.x * MET_THREADS + threadIdx.x; i < N; i += (int64_t)gridDim.x * MET_THREADS) {
+        const Cx<R> r = ldg(E + i);
+        Scan<R, NB, false> sc;
+        sc.run(r, sy);
+        R l[NB], la;
+        if (MINMAX) {
+#pragma unroll
+            for (int k = 0; k < NB; k++) l[k] = snr * (sc.m0[k] - sc.m1[k]);
+        } else {
+            llr_exact<R, NB, false>(r, sy, snr, sc, l, &la);
+        }
+#pragma unroll
+        for (int k = 0; k < NB; k++) L[(size_t)i * NB + k] = (double)l[k];
+    }
+}
+
+// Fused pass over an aligned row: rx[i] * j^rot against alphabet[tx[i - lag]] for i in [i0, i1), i - lag in [0, ntx).
+// partial fields: symbol errors, bit errors, compared, sum |t - r|^2, sum log2 sum_j exp(-(|r - s_j|^2 - |r - t|^2) snr),
+// then per bit sum log2(1 + exp((-1)^b L)).  Transmitted indices outside [0, M) are skipped.
+template <typename R, int NB, bool MINMAX>
+__global__ void __launch_bounds__(MET_THREADS) metrics_kernel(const Cx<R> *E, int64_t i0, int64_t i1, int rot, int64_t lag, const int32_t *tx,
+                                                              int64_t ntx, const Cx<R> *alphabet, R snr, double *partial)
+{
+    constexpr int M = 1 << NB, F = 5 + NB;
+    __shared__ Cx<R> sy[M];
+    load_alphabet<R, M>(sy, alphabet);
+    double acc[F];
+#pragma unroll
+    for (int f = 0; f < F; f++) acc[f] = 0;
+    const R t2 = snr * (R)LOG2E;
+    for (int64_t i = i0 + (int64_t)blockIdx.x * MET_THREADS + threadIdx.x; i < i1; i += (int64_t)gridDim.x * MET_THREADS) {
+        const int64_t it = i - lag;
+        if (it < 0 || it >= ntx) continue;
+        const int t = tx[it];
+        if ((unsigned)t >= (unsigned)M) continue;
+        const Cx<R> r = rot90(ldg(E + i), rot);
+        Scan<R, NB, true> sc;
+        sc.run(r, sy);
+        acc[0] += sc.idx != t;
+        acc[1] += __popc((unsigned)(sc.idx ^ t));
+        acc[2] += 1;
+        const R dt = dist2(r, sy[t]);
+        acc[3] += (double)dt;
+        R l[NB], la;
+        if (MINMAX) {
+#pragma unroll
+            for (int k = 0; k < NB; k++) l[k] = snr * (sc.m0[k] - sc.m1[k]);
+            la = log2_sum_loop<R, M>(r, sy, sc.dmin, t2);
+        } else {
+            llr_exact<R, NB, true>(r, sy, snr, sc, l, &la);
+        }
+        acc[4] += (double)((dt - sc.dmin) * t2) + (double)la;
+#pragma unroll
+        for (int k = 0; k < NB; k++) acc[5 + k] += softplus2((t >> (NB - 1 - k)) & 1 ? -(double)l[k] : (double)l[k]);
+    }
+    block_partials<F>(acc, partial);
+}
+
+// cal_mi_mc_fast on host arrays: sum over l of log2 sum_j exp(-(|x_l - s_j|^2 - |x_l - t_l|^2) / N0)
+template <typename R, int NB>
+__global__ void __launch_bounds__(MET_THREADS) mi_fast_kernel(const Cx<R> *x, const Cx<R> *tx, int64_t L, const Cx<R> *alphabet, R n0inv, double *partial)
+{
+    constexpr int M = 1 << NB;
+    __shared__ Cx<R> sy[M];
+    load_alphabet<R, M>(sy, alphabet);
+    double acc[1] = {0};
+    const R t2 = n0inv * (R)LOG2E;
+    for (int64_t l = (int64_t)blockIdx.x * MET_THREADS + threadIdx.x; l < L; l += (int64_t)gridDim.x * MET_THREADS) {
+        const Cx<R> r = ldg(x + l);
+        R dmin = __builtin_inf();
+#pragma unroll
+        for (int g = 0; g < M; g++) dmin = min_(dmin, dist2(r, sy[g]));
+        acc[0] += (double)((dist2(r, ldg(tx + l)) - dmin) * t2) + (double)log2_sum_loop<R, M>(r, sy, dmin, t2);
+    }
+    block_partials<1>(acc, partial);
+}
+
+// cal_mi_mc: sum over (i, l) of log2 sum_j exp(-(|s_i - s_j|^2 + 2 Re((s_i - s_j) n_l)) / N0), shifted by the largest exponent
+template <typename R>
+__global__ void __launch_bounds__(MET_THREADS) mi_mc_kernel(const Cx<R> *noise, int64_t L, const Cx<R> *alphabet, int M, R n0inv, double *partial)
+{
+    __shared__ Cx<R> sy[256];
+    for (int g = threadIdx.x; g < M; g += blockDim.x) sy[g] = alphabet[g];
+    __syncthreads();
+    double acc[1] = {0};
+    const int64_t P = L * M;
+    for (int64_t p = (int64_t)blockIdx.x * MET_THREADS + threadIdx.x; p < P; p += (int64_t)gridDim.x * MET_THREADS) {
+        const int i = (int)(p % M);
+        const Cx<R> n = ldg(noise + p / M), si = sy[i];
+        R amax = -__builtin_inf();
+        for (int j = 0; j < M; j++) {
+            const Cx<R> dd{si.re - sy[j].re, si.im - sy[j].im};
+            amax = fmax(amax, -(dd.re * dd.re + dd.im * dd.im + 2 * (dd.re * n.re - dd.im * n.im)) * n0inv);
+        }
+        R s = 0;
+        for (int j = 0; j < M; j++) {
+            const Cx<R> dd{si.re - sy[j].re, si.im - sy[j].im};
+            s += exp2_((-(dd.re * dd.re + dd.im * dd.im + 2 * (dd.re * n.re - dd.im * n.im)) * n0inv - amax) * (R)LOG2E);
+        }
+        acc[0] += (double)amax * LOG2E + (double)log2_(s);
+    }
+    block_partials<1>(acc, partial);
+}
+
+// out[f] = sum over blocks of partial[b * F + f]: one wave per field, lane j adds blocks j, j + 64, ... in order
+__global__ void __launch_bounds__(64) reduce_partials_kernel(const double *partial, int nblk, int F, double *out)
+{
+    const int f = blockIdx.x;
+    double s = 0;
+    for (int b = threadIdx.x; b < nblk; b += 64) s += partial[(size_t)b * F + f];
+    s = wave_sum(s);
+    if (threadIdx.x == 0) out[f] = s;
+}
+
+// SNR estimate, pass 1 (per class: count, sum re, sum im) and pass 2 (per class: sum |r - mu|^2), over the aligned row.
+// Deterministic: the block stages 256 symbols in LDS; the block is P = 256 / S groups of S >= M threads (S = 64, 128 or 256), thread g of
+// group q adds the staged symbols of class g in slice q of the tile in index order, and the P group sums are added in order at the end.
+// Per-block sums go to partial[block][M][3] / [block][M]; labels outside [0, M) belong to no class.
+template <typename R, bool PASS2>
+__global__ void __launch_bounds__(MET_THREADS) class_stats_kernel(const Cx<R> *E, int64_t i0, int64_t i1, int rot, int64_t lag, const int32_t *tx,
+                                                                  int64_t ntx, int M, const double *mu, double *partial)
+{
+    constexpr int F = PASS2 ? 1 : 3;
+    __shared__ int lab[MET_THREADS];
+    __shared__ double v0[MET_THREADS], v1[MET_THREADS], acc[MET_THREADS][F];
+    const int S = M <= 64 ? 64 : M <= 128 ? 128 : 256, P = MET_THREADS / S, len = MET_THREADS / P;
+    const int g = threadIdx.x % S, q = threadIdx.x / S;
+    double a0 = 0, a1 = 0, a2 = 0;
+    for (int64_t base = i0 + (int64_t)blockIdx.x * MET_THREADS; base < i1; base += (int64_t)gridDim.x * MET_THREADS) {
+        const int64_t i = base + threadIdx.x, it = i - lag;
+        int t = -1;
+        double x0 = 0, x1 = 0;
+        if (i < i1 && it >= 0 && it < ntx) {
+            t = tx[it];
+            if ((unsigned)t < (unsigned)M) {
+                const Cx<R> r = rot90(ldg(E + i), rot);
+                if (PASS2) {
+                    const double dx = (double)r.re - mu[2 * t], dy = (double)r.im - mu[2 * t + 1];
+                    x0 = dx * dx + dy * dy;
+                } else {
+                    x0 = (double)r.re; x1 = (double)r.im;
+                }
+            } else {
+                t = -1;
+            }
+        }
+        __syncthreads();                     // the previous tile is consumed
+        lab[threadIdx.x] = t; v0[threadIdx.x] = x0; v1[threadIdx.x] = x1;
+        __syncthreads();
+        if (g < M) {
+            for (int k = q * len; k < (q + 1) * len; k++) {
+                if (lab[k] != g) continue;
+                if (PASS2) { a0 += v0[k]; }
+                else { a0 += 1; a1 += v0[k]; a2 += v1[k]; }
+            }
+        }
+    }
+    acc[threadIdx.x][0] = a0;
+    if (!PASS2) { acc[threadIdx.x][1] = a1; acc[threadIdx.x][2] = a2; }
+    __syncthreads();
+    if (threadIdx.x < M) {
+        double *p = partial + ((size_t)blockIdx.x * M + threadIdx.x) * F;
+        for (int f = 0; f < F; f++) {
+            double s = 0;
+            for (int w = 0; w < P; w++) s += acc[w * S + threadIdx.x][f];
+            p[f] = s;
+        }
+    }
+}
+
+// mu[t] = class mean from the pass-1 sums (0 / 0 = NaN for an empty class, as np.mean of an empty selection)
+__global__ void class_mean_kernel(const double *sums, int M, double *mu)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < M) { mu[2 * t] = sums[3 * t + 1] / sums[3 * t]; mu[2 * t + 1] = sums[3 * t + 2] / sums[3 * t]; }
+}
+
+// label of tx[i]: index of the alphabet point it equals exactly, else -1 (estimate_snr selects with symbols_tx == gray_symbols[ind])
+template <typename R>
+__global__ void __launch_bounds__(MET_THREADS) exact_label_kernel(const Cx<R> *tx, int64_t n, const Cx<R> *alphabet, int M, int32_t *idx)
+{
+    const int64_t i = (int64_t)blockIdx.x * MET_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const Cx<R> x = ldg(tx + i);
+    int k = -1;
+    for (int g = M - 1; g >= 0; g--) if (alphabet[g].re == x.re && alphabet[g].im == x.im) k = g;
+    idx[i] = k;
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+unsigned grid_for(int64_t n)
+{
+    int64_t b = (n + MET_THREADS - 1) / MET_THREADS;
+    return (unsigned)(b < 1 ? 1 : b > MET_MAXBLK ? MET_MAXBLK : b);
+}
+
+int nbits_of(int M)
+{
+    for (int nb = 1; nb <= MET_NBMAX; nb++) if (M == 1 << nb) return nb;
+    return 0;
+}
+
+// dispatch a kernel templated on NB = 1..8
+#define QH_NB_DISPATCH(nb, ...)                                                                                        \
+    switch (nb) {                                                                                                       \
+    case 1: { constexpr int NB = 1; __VA_ARGS__; } break;                                                                      \
+    case 2: { constexpr int NB = 2; __VA_ARGS__; } break;                                                                      \
+    case 3: { constexpr int NB = 3; __VA_ARGS__; } break;                                                                      \
+    case 4: { constexpr int NB = 4; __VA_ARGS__; } break;                                                                      \
+    case 5: { constexpr int NB = 5; __VA_ARGS__; } break;                                                                      \
+    case 6: { constexpr int NB = 6; __VA_ARGS__; } break;                                                                      \
+    case 7: { constexpr int NB = 7; __VA_ARGS__; } break;                                                                      \
+    default: { constexpr int NB = 8; __VA_ARGS__; } break;                                                                     \
+    }
+
+// sum of F fields over nblk block partials into out (device), fixed order
+int reduce_fields(const double *partial, int nblk, int F, double *out)
+{
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(F), dim3(64), 0, g_stream, partial, nblk, F, out);
+    QH_HIP(hipGetLastError());
+    return QH_OK;
+}
+
+}  // namespace
+
+template <typename R> int llr_dev(const void *E, int64_t N, int nbits, double snr, const void *alphabet, int M, int minmax, double *L)
+{
+    int rc = ensure_init();
+    if (rc) return rc;
+    const int nb = nbits_of(M);
+    QH_REQUIRE(N >= 0 && nb > 0 && nbits == nb, "soft_l_value_demapper: M must be 2^nbits, nbits in 1..8");
+    if (N == 0) return QH_OK;
+    const unsigned g = grid_for(N);
+    if (minmax) { QH_NB_DISPATCH(nb, hipLaunchKernelGGL((llr_kernel<R, NB, true>), dim3(g), dim3(MET_THREADS), 0, g_stream, (const Cx<R> *)E, N, (const Cx<R> *)alphabet, (R)snr, L)) }
+    else { QH_NB_DISPATCH(nb, hipLaunchKernelGGL((llr_kernel<R, NB, false>), dim3(g), dim3(MET_THREADS), 0, g_stream, (const Cx<R> *)E, N, (const Cx<R> *)alphabet, (R)snr, L)) }
+    QH_HIP(hipGetLastError());
+    return QH_OK;
+}
+
+template <typename R> int llr_host(const void *E, int64_t N, int nbits, double snr, const void *alphabet, int M, int minmax, double *L)
+{
+    int rc = ensure_init();
+    if (rc) return rc;
+    QH_REQUIRE(N >= 0 && nbits_of(M) > 0 && nbits == nbits_of(M), "soft_l_value_demapper: M must be 2^nbits, nbits in 1..8");
+    if (N == 0) return QH_OK;
+    DevBuf dE, ds, dL;
+    if ((rc = dE.from_host(E, (size_t)N * sizeof(Cx<R>)))) return rc;
+    if ((rc = ds.from_host(alphabet, (size_t)M * sizeof(Cx<R>)))) return rc;
+    if ((rc = dL.alloc((size_t)N * nbits * sizeof(double)))) return rc;
+    if ((rc = llr_dev<R>(dE.p, N, nbits, snr, ds.p, M, minmax, (double *)dL.p))) return rc;
+    if ((rc = dL.to_host(L, dL.n))) return rc;
+    QH_HIP(hipStreamSynchronize(g_stream));
+    return QH_OK;
+}
+
+template <typename R>
+int metrics_dev(const void *E, int64_t N, const int32_t *idx_tx, int64_t ntx, const void *alphabet, int M, int rot, int64_t lag, int64_t trim,
+                double snr, int minmax, int64_t *counts, double *sums)
+{
+    int rc = ensure_init();
+    if (rc) return rc;
+    const int nb = nbits_of(M);
+    QH_REQUIRE(N > 0 && ntx > 0 && nb > 0 && trim >= 0 && 2 * trim < N, "metrics: bad sizes (M must be 2^nbits, nbits in 1..8)");
+    const int F = 5 + nb;
+    const unsigned g = grid_for(N - 2 * trim);
+    void *buf = nullptr;
+    if ((rc = scratch(13, ((size_t)g + 1) * F * sizeof(double), &buf))) return rc;
+    double *part = (double *)buf, *tot = part + (size_t)g * F;
+    if (minmax) {
+        QH_NB_DISPATCH(nb, hipLaunchKernelGGL((metrics_kernel<R, NB, true>), dim3(g), dim3(MET_THREADS), 0, g_stream, (const Cx<R> *)E, trim, N - trim, rot, lag,
+                                               idx_tx, ntx, (const Cx<R> *)alphabet, (R)snr, part))
+    } else {
+        QH_NB_DISPATCH(nb, hipLaunchKernelGGL((metrics_kernel<R, NB, false>), dim3(g), dim3(MET_THREADS), 0, g_stream, (const Cx<R> *)E, trim, N - trim, rot, lag,
+                                               idx_tx, ntx, (const Cx<R> *)alphabet, (R)snr, part))
+    }
+    QH_HIP(hipGetLastError());
+    if ((rc = reduce_fields(part, (int)g, F, tot))) return rc;
+    double h[5 + MET_NBMAX];
+    QH_HIP(hipMemcpyAsync(h, tot, (size_t)F * sizeof(double), hipMemcpyDeviceToHost, g_stream));
+    QH_HIP(hipStreamSynchronize(g_stream));
+    for (int f = 0; f < 3; f++) counts[f] = (int64_t)h[f];
+    for (int f = 3; f < F; f++) sums[f - 3] = h[f];
+    return QH_OK;
+}
+
+// class statistics -> (snr, S0, N0) in result; L: the length the class fractions are taken over (the reference's signal_rx.shape[0])
+template <typename R>
+int snr_stats(const void *E, int64_t i0, int64_t i1, int rot, int64_t lag, const int32_t *idx_tx, int64_t ntx, int M, int64_t L, double *result)
+{
+    const unsigned g = grid_for(i1 - i0);
+    void *buf = nullptr;
+    const size_t np = (size_t)g * M * 3, nt = (size_t)M * 3 + (size_t)M * 2 + M;
+    int rc;
+    if ((rc = scratch(14, (np + nt) * sizeof(double), &buf))) return rc;
+    double *part = (double *)buf, *sums = part + np, *mu = sums + (size_t)M * 3, *sse = mu + (size_t)M * 2;
+    hipLaunchKernelGGL((class_stats_kernel<R, false>), dim3(g), dim3(MET_THREADS), 0, g_stream, (const Cx<R> *)E, i0, i1, rot, lag, idx_tx, ntx, M,
+                       (const double *)nullptr, part);
+    QH_HIP(hipGetLastError());
+    if ((rc = reduce_fields(part, (int)g, 3 * M, sums))) return rc;
+    hipLaunchKernelGGL(class_mean_kernel, dim3((M + 63) / 64), dim3(64), 0, g_stream, (const double *)sums, M, mu);
+    hipLaunchKernelGGL((class_stats_kernel<R, true>), dim3(g), dim3(MET_THREADS), 0, g_stream, (const Cx<R> *)E, i0, i1, rot, lag, idx_tx, ntx, M,
+                       (const double *)mu, part);
+    QH_HIP(hipGetLastError());
+    if ((rc = reduce_fields(part, (int)g, M, sse))) return rc;
+    std::vector<double> h(nt);
+    QH_HIP(hipMemcpyAsync(h.data(), sums, nt * sizeof(double), hipMemcpyDeviceToHost, g_stream));
+    QH_HIP(hipStreamSynchronize(g_stream));
+    // estimate_snr (pythran_dsp.py:275-286), classes in alphabet order
+    double in_pow = 0, N0 = 0;
+    for (int t = 0; t < M; t++) {
+        const double K = h[3 * t], Px = K / (double)L;
+        const double mre = h[3 * M + 2 * t], mim = h[3 * M + 2 * t + 1];
+        const double sigma = std::sqrt(h[5 * M + t] / K);
+        N0 += sigma * sigma * Px;
+        in_pow += (mre * mre + mim * mim) * Px;
+    }
+    result[0] = in_pow / N0; result[1] = in_pow; result[2] = N0;
+    return QH_OK;
+}
+
+template <typename R>
+int estimate_snr_dev(const void *E, int64_t N, const int32_t *idx_tx, int64_t ntx, const void *alphabet, int M, int rot, int64_t lag, int64_t trim,
+                     double *result)
+{
+    (void)alphabet;
+    int rc = ensure_init();
+    if (rc) return rc;
+    QH_REQUIRE(N > 0 && ntx > 0 && M >= 1 && M <= 256 && trim >= 0 && 2 * trim < N, "estimate_snr: bad sizes");
+    // compared symbols of the aligned overlap: the class fractions are taken over them
+    const int64_t a = std::max(trim, lag), b = std::min(N - trim, ntx + lag);
+    QH_REQUIRE(b > a, "estimate_snr: the alignment leaves no overlap");
+    return snr_stats<R>(E, trim, N - trim, rot, lag, idx_tx, ntx, M, b - a, result);
+}
+
+template <typename R> int estimate_snr_host(const void *rx, int64_t N, const void *tx, int64_t ntx, const void *alphabet, int M, double *result)
+{
+    int rc = ensure_init();
+    if (rc) return rc;
+    QH_REQUIRE(N > 0 && ntx == N && M >= 1 && M <= 256, "estimate_snr: signal_rx and symbols_tx need the same length, M <= 256");
+    DevBuf dE, dt, ds, di;
+    if ((rc = dE.from_host(rx, (size_t)N * sizeof(Cx<R>)))) return rc;
+    if ((rc = dt.from_host(tx, (size_t)N * sizeof(Cx<R>)))) return rc;
+    if ((rc = ds.from_host(alphabet, (size_t)M * sizeof(Cx<R>)))) return rc;
+    if ((rc = di.alloc((size_t)N * sizeof(int32_t)))) return rc;
+    hipLaunchKernelGGL((exact_label_kernel<R>), dim3((unsigned)((N + MET_THREADS - 1) / MET_THREADS)), dim3(MET_THREADS), 0, g_stream, (const Cx<R> *)dt.p, N,
+                       (const Cx<R> *)ds.p, M, (int32_t *)di.p);
+    QH_HIP(hipGetLastError());
+    return snr_stats<R>(dE.p, 0, N, 0, 0, (const int32_t *)di.p, N, M, N, result);
+}
+
+template <typename R> int mi_fast_host(const void *x, const void *tx, int64_t L, const void *alphabet, int M, double N0, double *mi)
+{
+    int rc = ensure_init();
+    if (rc) return rc;
+    const int nb = nbits_of(M);
+    QH_REQUIRE(L > 0 && nb > 0, "cal_mi_mc_fast: M must be 2^nbits, nbits in 1..8");
+    DevBuf dx, dt, ds, dp;
+    const unsigned g = grid_for(L);
+    if ((rc = dx.from_host(x, (size_t)L * sizeof(Cx<R>)))) return rc;
+    if ((rc = dt.from_host(tx, (size_t)L * sizeof(Cx<R>)))) return rc;
+    if ((rc = ds.from_host(alphabet, (size_t)M * sizeof(Cx<R>)))) return rc;
+    if ((rc = dp.alloc(((size_t)g + 1) * sizeof(double)))) return rc;
+    double *part = (double *)dp.p;
+    QH_NB_DISPATCH(nb, hipLaunchKernelGGL((mi_fast_kernel<R, NB>), dim3(g), dim3(MET_THREADS), 0, g_stream, (const Cx<R> *)dx.p, (const Cx<R> *)dt.p, L,
+                                           (const Cx<R> *)ds.p, (R)(1. / N0), part))
+    QH_HIP(hipGetLastError());
+    if ((rc = reduce_fields(part, (int)g, 1, part + g))) return rc;
+    double s = 0;
+    QH_HIP(hipMemcpyAsync(&s, part + g, sizeof(double), hipMemcpyDeviceToHost, g_stream));
+    QH_HIP(hipStreamSynchronize(g_stream));
+    *mi = std::log2((double)M) - s / (double)L;
+    return QH_OK;
+}
+
+template <typename R> int mi_mc_host(const void *noise, int64_t L, const void *alphabet, int M, double N0, double *mi)
+{
+    int rc = ensure_init();
+    if (rc) return rc;
+    QH_REQUIRE(L > 0 && M >= 1 && M <= 256, "cal_mi_mc: bad sizes (M <= 256)");
+    DevBuf dn, ds, dp;
+    const unsigned g = grid_for(L * M);
+    if ((rc = dn.from_host(noise, (size_t)L * sizeof(Cx<R>)))) return rc;
+    if ((rc = ds.from_host(alphabet, (size_t)M * sizeof(Cx<R>)))) return rc;
+    if ((rc = dp.alloc(((size_t)g + 1) * sizeof(double)))) return rc;
+    double *part = (double *)dp.p;
+    hipLaunchKernelGGL((mi_mc_kernel<R>), dim3(g), dim3(MET_THREADS), 0, g_stream, (const Cx<R> *)dn.p, L, (const Cx<R> *)ds.p, M, (R)(1. / N0), part);
+    QH_HIP(hipGetLastError());
+    if ((rc = reduce_fields(part, (int)g, 1, part + g))) return rc;
+    double s = 0;
+    QH_HIP(hipMemcpyAsync(&s, part + g, sizeof(double), hipMemcpyDeviceToHost, g_stream));
+    QH_HIP(hipStreamSynchronize(g_stream));
+    *mi = std::log2((double)M) - s / (double)M / (double)L;
+    return QH_OK;
+}
+
+}  // namespace qh
+
+extern "C" {
+int qh_soft_l_value_demapper_c64(const void *rx, int64_t N, int nbits, double snr, const void *alphabet, int M, double *L)
+{ return qh::llr_host<float>(rx, N, nbits, snr, alphabet, M, 0, L); }
+int qh_soft_l_value_demapper_c128(const void *rx, int64_t N, int nbits, double snr, const void *alphabet, int M, double *L)
+{ return qh::llr_host<double>(rx, N, nbits, snr, alphabet, M, 0, L); }
+int qh_soft_l_value_demapper_minmax_c64(const void *rx, int64_t N, int nbits, double snr, const void *alphabet, int M, double *L)
+{ return qh::llr_host<float>(rx, N, nbits, snr, alphabet, M, 1, L); }
+int qh_soft_l_value_demapper_minmax_c128(const void *rx, int64_t N, int nbits, double snr, const void *alphabet, int M, double *L)
+{ return qh::llr_host<double>(rx, N, nbits, snr, alphabet, M, 1, L); }
+int qh_soft_l_value_demapper_c64_dev(const void *rx, int64_t N, int nbits, double snr, const void *alphabet, int M, int minmax, double *L)
+{ return qh::llr_dev<float>(rx, N, nbits, snr, alphabet, M, minmax, L); }
+int qh_soft_l_value_demapper_c128_dev(const void *rx, int64_t N, int nbits, double snr, const void *alphabet, int M, int minmax, double *L)
+{ return qh::llr_dev<double>(rx, N, nbits, snr, alphabet, M, minmax, L); }
+int qh_estimate_snr_c64(const void *rx, int64_t N, const void *tx, int64_t ntx, const void *alphabet, int M, double *result)
+{ return qh::estimate_snr_host<float>(rx, N, tx, ntx, alphabet, M, result); }
+int qh_estimate_snr_c128(const void *rx, int64_t N, const void *tx, int64_t ntx, const void *alphabet, int M, double *result)
+{ return qh::estimate_snr_host<double>(rx, N, tx, ntx, alphabet, M, result); }
+int qh_estimate_snr_c64_dev(const void *E, int64_t N, const int32_t *idx_tx, int64_t ntx, const void *alphabet, int M, int rot, int64_t lag,
+                            int64_t trim, double *result)
+{ return qh::estimate_snr_dev<float>(E, N, idx_tx, ntx, alphabet, M, rot, lag, trim, result); }
+int qh_estimate_snr_c128_dev(const void *E, int64_t N, const int32_t *idx_tx, int64_t ntx, const void *alphabet, int M, int rot, int64_t lag,
+                             int64_t trim, double *result)
+{ return qh::estimate_snr_dev<double>(E, N, idx_tx, ntx, alphabet, M, rot, lag, trim, result); }
+int qh_cal_mi_mc_c64(const void *noise, int64_t L, const void *alphabet, int M, double N0, double *mi)
+{ return qh::mi_mc_host<float>(noise, L, alphabet, M, N0, mi); }
+int qh_cal_mi_mc_c128(const void *noise, int64_t L, const void *alphabet, int M, double N0, double *mi)
+{ return qh::mi_mc_host<double>(noise, L, alphabet, M, N0, mi); }
+int qh_cal_mi_mc_fast_c64(const void *x, const void *tx, int64_t L, const void *alphabet, int M, double N0, double *mi)
+{ return qh::mi_fast_host<float>(x, tx, L, alphabet, M, N0, mi); }
+int qh_cal_mi_mc_fast_c128(const void *x, const void *tx, int64_t L, const void *alphabet, int M, double N0, double *mi)
+{ return qh::mi_fast_host<double>(x, tx, L, alphabet, M, N0, mi); }
+int qh_metrics_c64_dev(const void *E, int64_t N, const int32_t *idx_tx, int64_t ntx, const void *alphabet, int M, int rot, int64_t lag, int64_t trim,
+                       double snr, int minmax, int64_t *counts, double *sums)
+{ return qh::metrics_dev<float>(E, N, idx_tx, ntx, alphabet, M, rot, lag, trim, snr, minmax, counts, sums); }
+int qh_metrics_c128_dev(const void *E, int64_t N, const int32_t *idx_tx, int64_t ntx, const void *alphabet, int M, int rot, int64_t lag, int64_t trim,
+                        double snr, int minmax, int64_t *counts, double *sums)
+{ return qh::metrics_dev<double>(E, N, idx_tx, ntx, alphabet, M, rot, lag, trim, snr, minmax, counts, sums); }
+}

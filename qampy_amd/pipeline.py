@@ -543,6 +543,27 @@ class ResidentReceiver:
             self._idx_tx_src = symbols_tx
         return _ber.cal_ser_dev(self.out if self.Mtestangles else self.eq, self._idx_tx, self.alphabet, maxlag, window, trim)
 
+    def metrics(self, symbols_tx, snr_db=None, maxlag=256, window=4096, trim=0, llr_minmax=False):
+        """Signal-quality metrics (SER, BER, EVM, SNR estimate, GMI, MI) of the recovered (else equalised) rows against the
+        transmitted symbols, computed in HBM (``qampy_amd.core.ber_functions.cal_metrics_dev``); aligned as :meth:`ser`
+        aligns them.  ``snr_db``: the SNR the GMI / MI are evaluated at (None: estimated per row).  One dict per row."""
+        from .core import ber_functions as _ber
+        self._prepare_tx(symbols_tx)
+        return _ber.cal_metrics_dev(self.out if self.Mtestangles else self.eq, self._idx_tx, self.alphabet, snr_db, maxlag, window, trim,
+                                    llr_minmax)
+
+    def _prepare_tx(self, symbols_tx):
+        """Alphabet and transmitted indices in HBM (cached per ``symbols_tx`` object), after the pending post-processing."""
+        from .core import ber_functions as _ber
+        if self.alphabet_host is None:
+            raise ValueError("the metrics need the alphabet")
+        if getattr(self, "alphabet", None) is None:
+            self.alphabet = DeviceArray.from_host(self.alphabet_host)
+        self.wait_post()
+        if getattr(self, "_idx_tx", None) is None or self._idx_tx_src is not symbols_tx:
+            self._idx_tx = _ber.tx_indices_dev(np.ascontiguousarray(symbols_tx, dtype=self.ct), self.alphabet)
+            self._idx_tx_src = symbols_tx
+
     def bytes_per_symbol(self):
         """Algorithmic HBM bytes per symbol period of one run() (general formula)."""
         cs = np.dtype(self.ct).itemsize
@@ -801,6 +822,15 @@ class ChannelBank:
             r.alphabet = DeviceArray.from_host(r.alphabet_host)
         idx_tx = _ber.tx_indices_dev(np.ascontiguousarray(symbols_tx, dtype=self.ct), r.alphabet)
         return _ber.cal_ser_dev((self.out if r.Mtestangles else self.eq).row(ch), idx_tx, r.alphabet, maxlag, window, trim)
+
+    def metrics(self, ch, symbols_tx, snr_db=None, maxlag=256, window=4096, trim=0, llr_minmax=False):
+        """Per-row signal-quality metrics of channel ``ch`` (device pass, see :meth:`ResidentReceiver.metrics`)."""
+        from .core import ber_functions as _ber
+        r = self.rx
+        if getattr(r, "alphabet", None) is None:
+            r.alphabet = DeviceArray.from_host(r.alphabet_host)
+        idx_tx = _ber.tx_indices_dev(np.ascontiguousarray(symbols_tx, dtype=self.ct), r.alphabet)
+        return _ber.cal_metrics_dev((self.out if r.Mtestangles else self.eq).row(ch), idx_tx, r.alphabet, snr_db, maxlag, window, trim, llr_minmax)
 
     def fetch(self, ch):
         _lib.sync()

@@ -11,6 +11,7 @@ real ``qampy.signals.SignalQAMGrayCoded`` - works with ``qampy_amd.equalisation`
 import numpy as np
 
 from . import theory
+from .core import ber_functions
 
 _ATTRS = ("_M", "_fb", "_fs", "_coded_symbols", "_symbols")
 
@@ -84,6 +85,135 @@ class SignalQAM(np.ndarray):
                 k = "_" + k
             setattr(out, k, v)
         return out
+
+    # ---- signal-quality metrics (qampy/signals.py:245-560); rows of ``signal_rx`` are modes, results are per mode
+    @property
+    def Nbits(self):
+        """Bits per symbol."""
+        return int(np.log2(self.M))
+
+    def _signal_present(self, signal):
+        return np.atleast_2d(np.asarray(self if signal is None else signal))
+
+    def _sync_and_adjust(self, tx, rx, synced=False):
+        """Transmitted and received rows brought together (signals.py:245-266): unless ``synced``, every received mode takes
+        the still unassigned transmitted mode with the largest correlation peak, rotated and rolled onto it
+        (``ber_functions.sync_and_adjust``); ``synced``: only the lengths are adjusted."""
+        if tx is None:
+            raise ValueError("no transmitted symbols attached")
+        tx, rx = np.atleast_2d(tx), np.atleast_2d(rx)
+        if synced:
+            return self._adjust_only(tx, rx)
+        free = list(range(max(tx.shape[0], rx.shape[0])))
+        tx_out, rx_out = [], []
+        for j in range(rx.shape[0]):
+            best, pick = -100., None
+            for i in free:
+                pair, peak = ber_functions.sync_and_adjust(tx[i], rx[j])
+                if peak > best:
+                    best, pick, chosen = peak, i, pair
+            free.remove(pick)
+            tx_out.append(chosen[0])
+            rx_out.append(chosen[1])
+        return np.array(tx_out), np.array(rx_out)
+
+    @staticmethod
+    def _adjust_only(tx, rx):
+        """Lengths only (signals.py:268-292): modes beyond the received ones are dropped, tx cut or repeated to rx's length."""
+        if tx.shape[0] > rx.shape[0]:
+            tx = tx[:rx.shape[0]]
+        if tx.shape == rx.shape:
+            return tx, rx
+        method = "truncate" if tx.shape[1] > rx.shape[1] else "extend"
+        pairs = [ber_functions.adjust_data_length(t, r, method) for t, r in zip(tx, rx)]
+        return np.array([p[0] for p in pairs]), np.array([p[1] for p in pairs])
+
+    def make_decision(self, signal=None, verbose=False):
+        """Nearest alphabet point per sample (signals.py:847-870); ``verbose``: also the distances and indices."""
+        from .core.equalisation import hip_equalisation as hk
+        signal = self._signal_present(signal)
+        alphabet = np.ascontiguousarray(self.coded_symbols, dtype=signal.dtype)
+        out = [hk.make_decision(np.ascontiguousarray(row), alphabet) for row in signal]
+        det, dist, idx = (np.array([o[n] for o in out]) for n in range(3))
+        return (det, dist, idx) if verbose else det
+
+    def demodulate(self, symbols):
+        """Bits ``(nmodes, N * Nbits)`` (MSB first per symbol) of integer labels or of the decisions of complex symbols."""
+        symbols = np.atleast_2d(symbols)
+        idx = symbols if np.issubdtype(symbols.dtype, np.integer) else self.make_decision(symbols, verbose=True)[2]
+        shifts = np.arange(self.Nbits - 1, -1, -1)
+        return ((idx[..., None].astype(np.int64) >> shifts) & 1).astype(bool).reshape(idx.shape[0], -1)
+
+    def cal_ser(self, signal_rx=None, synced=False, verbose=False):
+        """Symbol error rate per mode (signals.py:295-333); ``verbose``: also the error vector and the synchronised tx."""
+        tx, rx = self._sync_and_adjust(self.symbols, self._signal_present(signal_rx), synced)
+        errs = self.make_decision(rx) - tx
+        ser = np.count_nonzero(errs, axis=-1) / rx.shape[1]
+        return (ser, errs, tx) if verbose else ser
+
+    def cal_ber(self, signal_rx=None, synced=False, verbose=False):
+        """Bit error rate per mode (signals.py:335-374); ``verbose``: also the bit errors and the synchronised tx bits."""
+        tx, rx = self._sync_and_adjust(self.symbols, self._signal_present(signal_rx), synced)
+        rx_bits, tx_bits = self.demodulate(rx), self.demodulate(tx)
+        errs = tx_bits ^ rx_bits
+        ber = np.count_nonzero(errs, axis=-1) / rx_bits.shape[1]
+        return (ber, errs, tx_bits) if verbose else ber
+
+    def cal_evm(self, signal_rx=None, synced=False, blind=False):
+        """RMS error vector magnitude per mode against the known symbols, or (``blind``) against the decisions
+        (signals.py:376-421)."""
+        rx = self._signal_present(signal_rx)
+        if blind:
+            tx = self.make_decision(rx)
+        else:
+            tx, rx = self._sync_and_adjust(self.symbols, rx, synced)
+        d = tx - rx
+        return np.asarray(np.sqrt(np.mean(d.real ** 2 + d.imag ** 2, axis=-1)))
+
+    def est_snr(self, signal_rx=None, synced=False, symbols_tx=None, verbose=False):
+        """Linear SNR per mode from the known symbols (signals.py:423-455); ``verbose``: ``(snr, S0, N0)``."""
+        from .core import hip_dsp
+        tx, rx = self._sync_and_adjust(self.symbols if symbols_tx is None else symbols_tx, self._signal_present(signal_rx), synced)
+        est = np.array([hip_dsp.estimate_snr(np.ascontiguousarray(r), np.ascontiguousarray(t, dtype=r.dtype),
+                                             np.ascontiguousarray(self.coded_symbols, dtype=r.dtype)) for r, t in zip(rx, tx)], dtype=np.float64)
+        est = est.reshape(-1, 3)
+        return (est[:, 0], est[:, 1], est[:, 2]) if verbose else est[:, 0]
+
+    def _snr_linear(self, snr, tx, rx):
+        """Per-mode linear SNR: estimated on the aligned rows when ``snr`` is None, else ``snr`` in dB (one value or one per mode)."""
+        if snr is None:
+            return self.est_snr(rx, synced=True, symbols_tx=tx)
+        snr = np.atleast_1d(snr)
+        return np.ones(rx.shape[0]) * 10 ** (snr / 10) if snr.size != rx.shape[0] else 10 ** (snr / 10)
+
+    def cal_gmi(self, signal_rx=None, synced=False, snr=None, llr_minmax=False):
+        """``(GMI, GMI_per_bit)`` per mode from soft-decision LLRs (signals.py:457-508); ``snr`` in dB, estimated when None.
+        One fused device pass per mode (``qh_metrics_*_dev``): the LLRs are never stored."""
+        from . import _lib
+        tx, rx = self._sync_and_adjust(self.symbols, self._signal_present(signal_rx), synced)
+        snr = self._snr_linear(snr, tx, rx)
+        ct = rx.dtype
+        alphabet = _lib.DeviceArray.from_host(np.ascontiguousarray(self.coded_symbols, dtype=ct))
+        labels = self.make_decision(tx, verbose=True)[2].astype(np.int32)
+        nb = self.Nbits
+        per_bit = np.zeros((rx.shape[0], nb), dtype=np.float64)
+        for m in range(rx.shape[0]):
+            row = _lib.DeviceArray.from_host(np.ascontiguousarray(rx[m]))
+            lab = _lib.DeviceArray.from_host(np.ascontiguousarray(labels[m]))
+            counts, sums = np.zeros(3, np.int64), np.zeros(2 + nb, np.float64)
+            _lib.call("qh_metrics_%s_dev" % ("c64" if ct == np.complex64 else "c128"), row.ptr, rx.shape[1], lab.ptr, rx.shape[1],
+                      alphabet.ptr, alphabet.shape[0], 0, 0, 0, float(snr[m]), int(bool(llr_minmax)), _lib.ptr(counts), _lib.ptr(sums))
+            per_bit[m] = 1 - sums[2:] / max(int(counts[2]), 1)
+        return np.sum(per_bit, axis=-1), per_bit
+
+    def cal_mi(self, signal_rx=None, synced=False, snr=None, fast=True):
+        """Mutual information per mode (signals.py:510-548); ``snr`` in dB, estimated when None (then ``N0 = 1 / snr``)."""
+        from .core import signal_quality
+        tx, rx = self._sync_and_adjust(self.symbols, self._signal_present(signal_rx), synced)
+        N0 = 1 / self._snr_linear(snr, tx, rx)
+        alphabet = np.ascontiguousarray(self.coded_symbols, dtype=rx.dtype)
+        return np.array([signal_quality.cal_mi(np.ascontiguousarray(rx[m]), np.ascontiguousarray(tx[m], dtype=rx.dtype), alphabet, N0[m], fast)
+                         for m in range(rx.shape[0])], dtype=np.float64)
 
 
 # ------------------------------------------------------------------------------------------------ pilot frames
@@ -231,3 +361,43 @@ class PilotSignal(np.ndarray):
         rx = self.get_data(frames)
         tx = np.tile(self._symbols, len(frames))
         return np.array([np.mean(synth.decide(r, self._coded_symbols) != synth.decide(t[:r.size], self._coded_symbols)) for r, t in zip(rx, tx)])
+
+    # ---- metrics of the payload (qampy/signals.py:1834-1950): a SignalQAM of the payload against the tiled transmitted payload
+    def _payload(self, frames=None):
+        if self._symbols is None:
+            raise ValueError("no transmitted payload attached")
+        frames = np.arange(self.nframes) if frames is None else np.atleast_1d(frames)
+        rx = self.get_data(frames)
+        tx = np.tile(self._symbols, len(frames))[:, :rx.shape[1]]
+        return SignalQAM(rx, self.M, fb=self.fb, fs=self.fb, symbols=tx, coded_symbols=self._coded_symbols)
+
+    def _pilot_signal(self, frames=None):
+        """The pilots as a SignalQAM of the pilot alphabet; the transmitted pilots are taken as their nearest pilot point."""
+        from . import synth
+        frames = np.arange(self.nframes) if frames is None else np.atleast_1d(frames)
+        rx = self.extract_pilots(frames)
+        alphabet = theory.coded_symbols_qam(self.Mpilots, dtype=rx.dtype)
+        npil = np.count_nonzero(self._idx_pil)
+        tx = np.tile(alphabet[np.array([synth.decide(p, alphabet) for p in self._pilots[:, :npil]])], len(frames))[:, :rx.shape[1]]
+        return SignalQAM(rx, self.Mpilots, fb=self.fb, fs=self.fb, symbols=tx, coded_symbols=alphabet)
+
+    def cal_ber(self, frames=None, synced=True, signal_rx=None, verbose=False):
+        """Bit error rate per mode of the payload (signals.py:1834-1860)."""
+        return self._payload(frames).cal_ber(signal_rx, synced=synced, verbose=verbose)
+
+    def cal_evm(self, frames=None, synced=True, signal_rx=None, blind=False):
+        """EVM per mode of the payload (signals.py:1862-1890)."""
+        return self._payload(frames).cal_evm(signal_rx, synced=synced, blind=blind)
+
+    def cal_gmi(self, frames=None, synced=True, snr=None, signal_rx=None, use_pilot_snr=False):
+        """``(GMI, GMI_per_bit)`` of the payload (signals.py:1892-1925); ``use_pilot_snr``: at the SNR estimated on the pilots
+        (converted to dB, the unit ``snr`` is taken in)."""
+        assert not (use_pilot_snr and snr is not None), "use_pilot_snr must not be True if snr is not None"
+        if use_pilot_snr:
+            snr = 10 * np.log10(self.est_snr(use_pilots=True))
+        return self._payload(frames).cal_gmi(signal_rx, synced=synced, snr=snr)
+
+    def est_snr(self, frames=None, synced=True, signal_rx=None, symbols_tx=None, use_pilots=False):
+        """Linear SNR per mode from the payload, or (``use_pilots``) from the pilots (signals.py:1927-1950)."""
+        sig = self._pilot_signal(frames) if use_pilots else self._payload(frames)
+        return sig.est_snr(signal_rx, synced=synced, symbols_tx=symbols_tx)
