@@ -470,8 +470,9 @@ int qh_ser_c128_dev(const void *E, int64_t N, const int32_t *idx_tx, int nmodes,
  * estimate_snr (:244-286), cal_mi_mc (:289-300), cal_mi_mc_fast (:303-313) - and the metric methods of qampy/signals.py:295-560.
  * `alphabet` (M,) is the constellation in coded order: point g carries Gray label g, bit k of it (MSB first) is
  * (g >> (nbits - 1 - k)) & 1, so no bit table is passed (the python layer inverts the reference's bits_map).  M = 2^nbits,
- * nbits 1..8, for everything that works on bits; M <= 256 for the rest.  Sums are reduced in double in a fixed order:
- * repeated calls give bit-identical results. */
+ * nbits 1..10, for everything that works on bits; M <= 1024 for the rest.  Sums are reduced in double in a fixed order:
+ * repeated calls give bit-identical results.  Bad sizes, an nbits other than log2 M, 2 trim >= N and an alignment without
+ * overlap return QH_ERR_ARG before anything is launched. */
 /* L (N, nbits) float64: log-likelihood ratios ln P(bit = 1) / P(bit = 0) at linear `snr`; complex64 input is evaluated in
  * float with each (bit, side) sum shifted by its own minimum distance, so L stays finite far beyond fp32's exp range. */
 int qh_soft_l_value_demapper_c64(const void *rx, int64_t N, int nbits, double snr, const void *alphabet, int M, double *L);

@@ -4,7 +4,9 @@
 // (qampy/signals.py:340-560).
 //
 // Bit labels need no table: point g of the alphabet (coded order) carries Gray label g, bit k (MSB first) is
-// (g >> (nbits - 1 - k)) & 1.  The kernels are templated on nbits, so each (bit, side) subset is fixed at compile time.
+// (g >> (nbits - 1 - k)) & 1.  The kernels are templated on nbits (1..10, M up to 1024).  Up to nbits 8 the loops over the
+// alphabet unroll fully, so each (bit, side) subset is fixed at compile time; above that they unroll by 8 and test the bits
+// at run time (the same operations in the same order, a fraction of the code).
 //
 // Range of the exact LLR.  L = ln sum_{bit=1} exp(-snr d_g) - ln sum_{bit=0} exp(-snr d_g) (d_g = |s_g - r|^2).  In
 // complex64 each (bit, side) sum is shifted by that subset's own minimum distance m, so its largest term is 1 and the sum
@@ -22,7 +24,10 @@
 namespace qh {
 namespace {
 
-constexpr int MET_THREADS = 256, MET_MAXBLK = 1024, MET_NBMAX = 8;
+constexpr int MET_THREADS = 256, MET_MAXBLK = 1024, MET_NBMAX = 10;
+
+// unroll factor of a loop over the 2^NB alphabet points: all of them up to 256 points, 8 at a time beyond
+template <int NB> constexpr int unroll_points() { return NB <= 8 ? 1 << NB : 8; }
 constexpr double LOG2E = 1.4426950408889634, LN2 = 0.6931471805599453;
 
 template <typename R> __device__ __forceinline__ R hyp_(R a, R b);
@@ -66,7 +71,7 @@ template <typename R, int NB, bool DECIDE> struct Scan {
         dmin = inf;
         R hbest = inf;
         idx = 0;
-#pragma unroll
+#pragma unroll unroll_points<NB>()
         for (int g = 0; g < M; g++) {
             const Cx<R> s = sy[g];
             const R d = dist2(r, s);
@@ -95,7 +100,7 @@ __device__ __forceinline__ void llr_exact(Cx<R> r, const Cx<R> *sy, R snr, const
     R s0[NB], s1[NB];
 #pragma unroll
     for (int k = 0; k < NB; k++) s0[k] = s1[k] = 0;
-#pragma unroll
+#pragma unroll unroll_points<NB>()
     for (int g = 0; g < M; g++) {
         const R d = dist2(r, sy[g]);
         if (PER_SUBSET) {
@@ -127,11 +132,12 @@ __device__ __forceinline__ void llr_exact(Cx<R> r, const Cx<R> *sy, R snr, const
 }
 
 // log2 sum_g exp(-(d_g - dmin) / N0) by its own loop (minmax LLRs and the host-array fast MI)
-template <typename R, int M>
+template <typename R, int NB>
 __device__ __forceinline__ R log2_sum_loop(Cx<R> r, const Cx<R> *sy, R dmin, R n0inv_log2e)
 {
+    constexpr int M = 1 << NB;
     R s = 0;
-#pragma unroll
+#pragma unroll unroll_points<NB>()
     for (int g = 0; g < M; g++) s += exp2_((dmin - dist2(r, sy[g])) * n0inv_log2e);
     return log2_(s);
 }
@@ -214,7 +220,7 @@ __global__ void __launch_bounds__(MET_THREADS) metrics_kernel(const Cx<R> *E, in
         if (MINMAX) {
 #pragma unroll
             for (int k = 0; k < NB; k++) l[k] = snr * (sc.m0[k] - sc.m1[k]);
-            la = log2_sum_loop<R, M>(r, sy, sc.dmin, t2);
+            la = log2_sum_loop<R, NB>(r, sy, sc.dmin, t2);
         } else {
             llr_exact<R, NB, true>(r, sy, snr, sc, l, &la);
         }
@@ -237,9 +243,9 @@ __global__ void __launch_bounds__(MET_THREADS) mi_fast_kernel(const Cx<R> *x, co
     for (int64_t l = (int64_t)blockIdx.x * MET_THREADS + threadIdx.x; l < L; l += (int64_t)gridDim.x * MET_THREADS) {
         const Cx<R> r = ldg(x + l);
         R dmin = __builtin_inf();
-#pragma unroll
+#pragma unroll unroll_points<NB>()
         for (int g = 0; g < M; g++) dmin = min_(dmin, dist2(r, sy[g]));
-        acc[0] += (double)((dist2(r, ldg(tx + l)) - dmin) * t2) + (double)log2_sum_loop<R, M>(r, sy, dmin, t2);
+        acc[0] += (double)((dist2(r, ldg(tx + l)) - dmin) * t2) + (double)log2_sum_loop<R, NB>(r, sy, dmin, t2);
     }
     block_partials<1>(acc, partial);
 }
@@ -248,7 +254,7 @@ __global__ void __launch_bounds__(MET_THREADS) mi_fast_kernel(const Cx<R> *x, co
 template <typename R>
 __global__ void __launch_bounds__(MET_THREADS) mi_mc_kernel(const Cx<R> *noise, int64_t L, const Cx<R> *alphabet, int M, R n0inv, double *partial)
 {
-    __shared__ Cx<R> sy[256];
+    __shared__ Cx<R> sy[1 << MET_NBMAX];
     for (int g = threadIdx.x; g < M; g += blockDim.x) sy[g] = alphabet[g];
     __syncthreads();
     double acc[1] = {0};
@@ -284,17 +290,20 @@ __global__ void __launch_bounds__(64) reduce_partials_kernel(const double *parti
 // SNR estimate, pass 1 (per class: count, sum re, sum im) and pass 2 (per class: sum |r - mu|^2), over the aligned row.
 // Deterministic: the block stages 256 symbols in LDS; the block is P = 256 / S groups of S >= M threads (S = 64, 128 or 256), thread g of
 // group q adds the staged symbols of class g in slice q of the tile in index order, and the P group sums are added in order at the end.
+// Above 256 classes (C > 1, M <= 256 C) the block is one group and thread g owns the classes g, g + 256, ..., each in index order.
 // Per-block sums go to partial[block][M][3] / [block][M]; labels outside [0, M) belong to no class.
-template <typename R, bool PASS2>
+template <typename R, bool PASS2, int C>
 __global__ void __launch_bounds__(MET_THREADS) class_stats_kernel(const Cx<R> *E, int64_t i0, int64_t i1, int rot, int64_t lag, const int32_t *tx,
                                                                   int64_t ntx, int M, const double *mu, double *partial)
 {
     constexpr int F = PASS2 ? 1 : 3;
     __shared__ int lab[MET_THREADS];
     __shared__ double v0[MET_THREADS], v1[MET_THREADS], acc[MET_THREADS][F];
-    const int S = M <= 64 ? 64 : M <= 128 ? 128 : 256, P = MET_THREADS / S, len = MET_THREADS / P;
+    const int S = C > 1 || M > 128 ? 256 : M <= 64 ? 64 : 128, P = MET_THREADS / S, len = MET_THREADS / P;
     const int g = threadIdx.x % S, q = threadIdx.x / S;
-    double a0 = 0, a1 = 0, a2 = 0;
+    double a0[C], a1[C], a2[C];
+#pragma unroll
+    for (int c = 0; c < C; c++) a0[c] = a1[c] = a2[c] = 0;
     for (int64_t base = i0 + (int64_t)blockIdx.x * MET_THREADS; base < i1; base += (int64_t)gridDim.x * MET_THREADS) {
         const int64_t i = base + threadIdx.x, it = i - lag;
         int t = -1;
@@ -316,16 +325,40 @@ __global__ void __launch_bounds__(MET_THREADS) class_stats_kernel(const Cx<R> *E
         __syncthreads();                     // the previous tile is consumed
         lab[threadIdx.x] = t; v0[threadIdx.x] = x0; v1[threadIdx.x] = x1;
         __syncthreads();
-        if (g < M) {
-            for (int k = q * len; k < (q + 1) * len; k++) {
-                if (lab[k] != g) continue;
-                if (PASS2) { a0 += v0[k]; }
-                else { a0 += 1; a1 += v0[k]; a2 += v1[k]; }
+        if (C == 1) {
+            if (g < M) {
+                for (int k = q * len; k < (q + 1) * len; k++) {
+                    if (lab[k] != g) continue;
+                    if (PASS2) { a0[0] += v0[k]; }
+                    else { a0[0] += 1; a1[0] += v0[k]; a2[0] += v1[k]; }
+                }
+            }
+        } else {
+            for (int k = 0; k < MET_THREADS; k++) {
+                const int l = lab[k];
+                if (l < 0 || l % MET_THREADS != g) continue;
+#pragma unroll
+                for (int c = 0; c < C; c++) {        // constant register index: c = l / 256
+                    if (l / MET_THREADS != c) continue;
+                    if (PASS2) { a0[c] += v0[k]; }
+                    else { a0[c] += 1; a1[c] += v0[k]; a2[c] += v1[k]; }
+                }
             }
         }
     }
-    acc[threadIdx.x][0] = a0;
-    if (!PASS2) { acc[threadIdx.x][1] = a1; acc[threadIdx.x][2] = a2; }
+    if (C > 1) {                             // one group: the owner's sums are the block's
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+            const int cl = g + c * MET_THREADS;
+            if (cl >= M) continue;
+            double *p = partial + ((size_t)blockIdx.x * M + cl) * F;
+            p[0] = a0[c];
+            if (!PASS2) { p[1] = a1[c]; p[2] = a2[c]; }
+        }
+        return;
+    }
+    acc[threadIdx.x][0] = a0[0];
+    if (!PASS2) { acc[threadIdx.x][1] = a1[0]; acc[threadIdx.x][2] = a2[0]; }
     __syncthreads();
     if (threadIdx.x < M) {
         double *p = partial + ((size_t)blockIdx.x * M + threadIdx.x) * F;
@@ -369,7 +402,7 @@ int nbits_of(int M)
     return 0;
 }
 
-// dispatch a kernel templated on NB = 1..8
+// dispatch a kernel templated on NB = 1..10
 #define QH_NB_DISPATCH(nb, ...)                                                                                        \
     switch (nb) {                                                                                                       \
     case 1: { constexpr int NB = 1; __VA_ARGS__; } break;                                                                      \
@@ -379,7 +412,9 @@ int nbits_of(int M)
     case 5: { constexpr int NB = 5; __VA_ARGS__; } break;                                                                      \
     case 6: { constexpr int NB = 6; __VA_ARGS__; } break;                                                                      \
     case 7: { constexpr int NB = 7; __VA_ARGS__; } break;                                                                      \
-    default: { constexpr int NB = 8; __VA_ARGS__; } break;                                                                     \
+    case 8: { constexpr int NB = 8; __VA_ARGS__; } break;                                                                      \
+    case 9: { constexpr int NB = 9; __VA_ARGS__; } break;                                                                      \
+    default: { constexpr int NB = 10; __VA_ARGS__; } break;                                                                    \
     }
 
 // sum of F fields over nblk block partials into out (device), fixed order
@@ -397,7 +432,7 @@ template <typename R> int llr_dev(const void *E, int64_t N, int nbits, double sn
     int rc = ensure_init();
     if (rc) return rc;
     const int nb = nbits_of(M);
-    QH_REQUIRE(N >= 0 && nb > 0 && nbits == nb, "soft_l_value_demapper: M must be 2^nbits, nbits in 1..8");
+    QH_REQUIRE(N >= 0 && nb > 0 && nbits == nb, "soft_l_value_demapper: M must be 2^nbits, nbits in 1..10");
     if (N == 0) return QH_OK;
     const unsigned g = grid_for(N);
     if (minmax) { QH_NB_DISPATCH(nb, hipLaunchKernelGGL((llr_kernel<R, NB, true>), dim3(g), dim3(MET_THREADS), 0, g_stream, (const Cx<R> *)E, N, (const Cx<R> *)alphabet, (R)snr, L)) }
@@ -410,7 +445,7 @@ template <typename R> int llr_host(const void *E, int64_t N, int nbits, double s
 {
     int rc = ensure_init();
     if (rc) return rc;
-    QH_REQUIRE(N >= 0 && nbits_of(M) > 0 && nbits == nbits_of(M), "soft_l_value_demapper: M must be 2^nbits, nbits in 1..8");
+    QH_REQUIRE(N >= 0 && nbits_of(M) > 0 && nbits == nbits_of(M), "soft_l_value_demapper: M must be 2^nbits, nbits in 1..10");
     if (N == 0) return QH_OK;
     DevBuf dE, ds, dL;
     if ((rc = dE.from_host(E, (size_t)N * sizeof(Cx<R>)))) return rc;
@@ -429,7 +464,8 @@ int metrics_dev(const void *E, int64_t N, const int32_t *idx_tx, int64_t ntx, co
     int rc = ensure_init();
     if (rc) return rc;
     const int nb = nbits_of(M);
-    QH_REQUIRE(N > 0 && ntx > 0 && nb > 0 && trim >= 0 && 2 * trim < N, "metrics: bad sizes (M must be 2^nbits, nbits in 1..8)");
+    QH_REQUIRE(N > 0 && ntx > 0 && nb > 0 && trim >= 0 && 2 * trim < N, "metrics: bad sizes (M must be 2^nbits, nbits in 1..10)");
+    QH_REQUIRE(std::min(N - trim, ntx + lag) > std::max(trim, lag), "metrics: the alignment leaves no overlap");
     const int F = 5 + nb;
     const unsigned g = grid_for(N - 2 * trim);
     void *buf = nullptr;
@@ -462,13 +498,17 @@ int snr_stats(const void *E, int64_t i0, int64_t i1, int rot, int64_t lag, const
     int rc;
     if ((rc = scratch(14, (np + nt) * sizeof(double), &buf))) return rc;
     double *part = (double *)buf, *sums = part + np, *mu = sums + (size_t)M * 3, *sse = mu + (size_t)M * 2;
-    hipLaunchKernelGGL((class_stats_kernel<R, false>), dim3(g), dim3(MET_THREADS), 0, g_stream, (const Cx<R> *)E, i0, i1, rot, lag, idx_tx, ntx, M,
-                       (const double *)nullptr, part);
+    if (M <= MET_THREADS) hipLaunchKernelGGL((class_stats_kernel<R, false, 1>), dim3(g), dim3(MET_THREADS), 0, g_stream, (const Cx<R> *)E, i0, i1, rot, lag,
+                                             idx_tx, ntx, M, (const double *)nullptr, part);
+    else hipLaunchKernelGGL((class_stats_kernel<R, false, (1 << MET_NBMAX) / MET_THREADS>), dim3(g), dim3(MET_THREADS), 0, g_stream, (const Cx<R> *)E, i0, i1,
+                            rot, lag, idx_tx, ntx, M, (const double *)nullptr, part);
     QH_HIP(hipGetLastError());
     if ((rc = reduce_fields(part, (int)g, 3 * M, sums))) return rc;
     hipLaunchKernelGGL(class_mean_kernel, dim3((M + 63) / 64), dim3(64), 0, g_stream, (const double *)sums, M, mu);
-    hipLaunchKernelGGL((class_stats_kernel<R, true>), dim3(g), dim3(MET_THREADS), 0, g_stream, (const Cx<R> *)E, i0, i1, rot, lag, idx_tx, ntx, M,
-                       (const double *)mu, part);
+    if (M <= MET_THREADS) hipLaunchKernelGGL((class_stats_kernel<R, true, 1>), dim3(g), dim3(MET_THREADS), 0, g_stream, (const Cx<R> *)E, i0, i1, rot, lag,
+                                             idx_tx, ntx, M, (const double *)mu, part);
+    else hipLaunchKernelGGL((class_stats_kernel<R, true, (1 << MET_NBMAX) / MET_THREADS>), dim3(g), dim3(MET_THREADS), 0, g_stream, (const Cx<R> *)E, i0, i1,
+                            rot, lag, idx_tx, ntx, M, (const double *)mu, part);
     QH_HIP(hipGetLastError());
     if ((rc = reduce_fields(part, (int)g, M, sse))) return rc;
     std::vector<double> h(nt);
@@ -494,7 +534,7 @@ int estimate_snr_dev(const void *E, int64_t N, const int32_t *idx_tx, int64_t nt
     (void)alphabet;
     int rc = ensure_init();
     if (rc) return rc;
-    QH_REQUIRE(N > 0 && ntx > 0 && M >= 1 && M <= 256 && trim >= 0 && 2 * trim < N, "estimate_snr: bad sizes");
+    QH_REQUIRE(N > 0 && ntx > 0 && M >= 1 && M <= 1 << MET_NBMAX && trim >= 0 && 2 * trim < N, "estimate_snr: bad sizes (M <= 1024)");
     // compared symbols of the aligned overlap: the class fractions are taken over them
     const int64_t a = std::max(trim, lag), b = std::min(N - trim, ntx + lag);
     QH_REQUIRE(b > a, "estimate_snr: the alignment leaves no overlap");
@@ -505,7 +545,7 @@ template <typename R> int estimate_snr_host(const void *rx, int64_t N, const voi
 {
     int rc = ensure_init();
     if (rc) return rc;
-    QH_REQUIRE(N > 0 && ntx == N && M >= 1 && M <= 256, "estimate_snr: signal_rx and symbols_tx need the same length, M <= 256");
+    QH_REQUIRE(N > 0 && ntx == N && M >= 1 && M <= 1 << MET_NBMAX, "estimate_snr: signal_rx and symbols_tx need the same length, M <= 1024");
     DevBuf dE, dt, ds, di;
     if ((rc = dE.from_host(rx, (size_t)N * sizeof(Cx<R>)))) return rc;
     if ((rc = dt.from_host(tx, (size_t)N * sizeof(Cx<R>)))) return rc;
@@ -522,7 +562,7 @@ template <typename R> int mi_fast_host(const void *x, const void *tx, int64_t L,
     int rc = ensure_init();
     if (rc) return rc;
     const int nb = nbits_of(M);
-    QH_REQUIRE(L > 0 && nb > 0, "cal_mi_mc_fast: M must be 2^nbits, nbits in 1..8");
+    QH_REQUIRE(L > 0 && nb > 0, "cal_mi_mc_fast: M must be 2^nbits, nbits in 1..10");
     DevBuf dx, dt, ds, dp;
     const unsigned g = grid_for(L);
     if ((rc = dx.from_host(x, (size_t)L * sizeof(Cx<R>)))) return rc;
@@ -545,7 +585,7 @@ template <typename R> int mi_mc_host(const void *noise, int64_t L, const void *a
 {
     int rc = ensure_init();
     if (rc) return rc;
-    QH_REQUIRE(L > 0 && M >= 1 && M <= 256, "cal_mi_mc: bad sizes (M <= 256)");
+    QH_REQUIRE(L > 0 && M >= 1 && M <= 1 << MET_NBMAX, "cal_mi_mc: bad sizes (M <= 1024)");
     DevBuf dn, ds, dp;
     const unsigned g = grid_for(L * M);
     if ((rc = dn.from_host(noise, (size_t)L * sizeof(Cx<R>)))) return rc;
