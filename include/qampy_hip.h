@@ -230,6 +230,17 @@ int qh_comp_freq_offset_c128(const void *E, int nmodes, int64_t L, const double 
 int qh_pilot_phase_trace_c64(const void *E, int nmodes, int64_t L, const int64_t *knots, const double *kph, int nk, void *out, void *trace);
 int qh_pilot_phase_trace_c128(const void *E, int nmodes, int64_t L, const int64_t *knots, const double *kph, int nk, void *out, void *trace);
 
+/* ---- chromatic dispersion (qampy/core/equalisation/equalisation.py:596-669 CDcomp, qampy/core/impairments.py:673-703 add_dispersion):
+ * every row of E (nmodes, L) filtered by the all-pass H(w) = exp(j (c2 w^2 + c1 w + c0)), w = 2 pi k / N the digital angular frequency of
+ * fftfreq bin k of a block FFT of size N (a power of two, 256 .. 8192, both precisions).  mode 0, circular: overlap-save of blocks of N / 2
+ * output samples with N / 4 of halo on each side, the input taken modulo L; out (nmodes, L); N == L is one exact circular transform per row.
+ * mode 1, linear: the zero-padded overlap-add of CDcomp with N > 0 (blocks of N / 2 input samples at offset N / 4 of N zeros); out
+ * (nmodes, (L / (N / 2)) * (N / 2)).  out must not alias E.  Deterministic. */
+int qh_cd_filter_c64(const void *E, int nmodes, int64_t L, int N, double c2, double c1, double c0, int mode, void *out);
+int qh_cd_filter_c128(const void *E, int nmodes, int64_t L, int N, double c2, double c1, double c0, int mode, void *out);
+int qh_cd_filter_c64_dev(const void *E, int nmodes, int64_t L, int N, double c2, double c1, double c0, int mode, void *out);
+int qh_cd_filter_c128_dev(const void *E, int nmodes, int64_t L, int N, double c2, double c1, double c0, int mode, void *out);
+
 /* ---- select_angles: out[i] = angles[(p > 1 ? i : 0), idx[i]] ;  idx int64 (L,) ------------------------------- */
 int qh_select_angles_f32(const void *angles, int64_t p, int A, const int64_t *idx, int64_t L, void *out);
 int qh_select_angles_f64(const void *angles, int64_t p, int A, const int64_t *idx, int64_t L, void *out);

@@ -373,3 +373,42 @@ def search_windows(E, os, mu, M, starts, win_len, Ntaps=None, TrSyms=None, Niter
     return _kernels.train_equaliser_windows_search(E, starts, win_len, TrSyms, Niter, os, E.real.dtype.type(mu), _init_taps(Ntaps, nmodes, nmodes, E.dtype),
                                                    np.arange(nmodes) if modes is None else np.atleast_1d(modes), adaptive_stepsize,
                                                    _reshape_symbols(symbols, method, M, E.dtype, nmodes).copy(), method)
+
+
+def CDcomp(E, fs, N, L, D, wl):
+    """
+    Static chromatic dispersion compensation (qampy/core/equalisation/equalisation.py:596-669) on the GPU (csrc/cd.hip).  Like the
+    reference, ``E`` is flattened to one row, ``H = exp(-0.5j beta2 L omega^2)`` is sampled on ``pi fs linspace(-1, 1, n)`` (n: the
+    transform length) and the pair ``(sigEQ, H)`` is returned, ``sigEQ`` in the input's dtype.  The sign is the reference's: the
+    dispersion that ``add_dispersion(D, L)`` adds is removed by ``CDcomp(..., -L, D, ...)``.  Because of the linspace grid that
+    removal is not exact (rms error 0.022 at 2^14 samples and 1000 km, 40 GS/s), as in the reference.
+
+    N = 0, cyclic: the length is a power of two from 256 to 8192 - one exact circular transform, as the reference.  Other lengths:
+    overlap-save blocks of the default size of :func:`qampy_amd.core.filter.cd_filter_dev` with the reference's H (on the grid of the
+    whole length) - about 1e-5 to 3e-5 rms of the signal from the reference's single transform at 100 to 1000 km.
+
+    N > 0: the reference's overlap-add of N-point blocks (N / 2 samples each, N / 4 zeros on each side; output length
+    (N / 2) (len // (N / 2))), N a power of two from 256 to 8192.  The reference multiplies the unshifted block spectrum by its
+    centred H, which compensates nothing (rms error 2.0 on a dispersed signal of rms 1.4); here H is taken in fftfreq
+    (``ifftshift``) order, the computation the reference intends.
+    """
+    from .. import filter as _filter
+    E = np.asarray(E).flatten()
+    if E.dtype not in (np.complex64, np.complex128):
+        E = E.astype(np.complex128)
+    samp = E.size
+    c = 2.99792458e8
+    n = samp if N == 0 else int(N)
+    if N == 0:
+        if (samp & (samp - 1)) == 0 and _filter.CD_NMIN <= samp <= _filter.CD_NMAX:
+            Nb = samp
+        else:
+            Nb = _filter.cd_block_size(_filter.cd_spread(fs, D, L, wl))
+        mode = "circular"
+    else:
+        Nb = _filter._check_block(N)
+        mode = "linear"
+    omega = np.pi * fs * np.linspace(-1, 1, n, dtype=complex)
+    H = np.exp(-.5j * omega ** 2 * (D * wl ** 2 / (c * 2 * np.pi)) * L)
+    out = _filter.cd_filter_host(E.reshape(1, -1), Nb, _filter.cd_coeffs_linspace(fs, D, L, wl, n), mode)
+    return out[0], H

@@ -121,6 +121,7 @@ int ensure_init()
 // grow-only scratch slots so that the resident pipeline never allocates (and never synchronises) inside a timed region
 thread_local void *g_scratch[16] = {nullptr};
 thread_local size_t g_scratch_n[16] = {0};
+thread_local unsigned g_scratch_epoch = 0;
 // ---- the table of form switches (common.h FormKey; qh_set_form / qh_set_trainer).  Values:
 //   trainer    0 automatic, 1 direct, 2 lookahead, 3 iterative          pit_form   0 automatic, 1 segment (throughput form), 2 block (latency forms)
 //   seg_lanes  0 automatic, 8, 16                                       pit_probe  1: complex64 takes the complex128 analysis of a pass
@@ -258,6 +259,7 @@ int scratch(int slot, size_t bytes, void **p)
     *p = g_scratch[slot];
     return QH_OK;
 }
+unsigned scratch_epoch() { return g_scratch_epoch; }
 
 }  // namespace qh
 
@@ -354,6 +356,7 @@ int qh_release_scratch(void)
         if (qh::g_scratch[i]) QH_HIP(hipFree(qh::g_scratch[i]));
         qh::g_scratch[i] = nullptr; qh::g_scratch_n[i] = 0;
     }
+    qh::g_scratch_epoch++;
     qh::pool_release();
     qh::hpool_release();
     return QH_OK;
@@ -368,6 +371,7 @@ int qh_thread_release(void)
         if (qh::g_scratch[i]) (void)hipFree(qh::g_scratch[i]);
         qh::g_scratch[i] = nullptr; qh::g_scratch_n[i] = 0;
     }
+    qh::g_scratch_epoch++;
     for (int i = 0; i < 4; i++) if (qh::g_streams[i]) { (void)hipStreamDestroy(qh::g_streams[i]); qh::g_streams[i] = nullptr; }
     qh::g_stream = nullptr;
     return QH_OK;

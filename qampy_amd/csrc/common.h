@@ -42,7 +42,8 @@ double gram_budget_gb();         // scratch the Gram tables of one call may take
 int pit_timing_mode();            // which relaxation passes of a tier-b sweep get HIP events: 0 none, 1 pass 1 (default), 2 all (qh_set_pit_timing)
 int default_tier();               // 0: tier a (exact), 1: tier b - what the drop-in host-array trainers run (qh_set_default_tier)
 double default_tier_tol();        // tolerance of the default tier b (qh_set_default_tier)
-int scratch(int slot, size_t bytes, void **p);   // grow-only device scratch, slots 0..11
+int scratch(int slot, size_t bytes, void **p);   // grow-only device scratch, slots 0..15
+unsigned scratch_epoch();        // changes whenever the calling thread's scratch slots are released (contents cached in a slot are gone)
 
 // Staging memory of the host-pointer entry points: power-of-two size classes kept in a small pool (api.hip) instead of a
 // hipMalloc / hipFree pair per call - hipFree synchronises the device, and the pilot receiver makes dozens of small calls.

@@ -138,6 +138,23 @@ class ResidentReceiver:
                     o["acq_chunk"] = self._acq_chunk_rule(power, float(self.mu0[s_]), o)
                     self._acq_asked[s_] = True
 
+    def compensate_cd(self, fs, D, L, wl0=1550e-9, N=None, next_capture=False):
+        """Take the chromatic dispersion of ``L`` metres of fibre (``D`` in s/m/m) out of the loaded capture in HBM (``self.E``, or
+        ``self.E_next`` with ``next_capture``): :func:`qampy_amd.core.filter.cd_filter_dev` with ``-L``, enqueued on stream 0 between
+        ``load()`` / ``load_next()`` and ``run()``.  ``L`` is the fibre length the capture went through, as ``add_dispersion`` takes it.
+        The filter is all-pass, so the power ``load()`` read for tier b's acquisition rule is still the capture's power."""
+        from .core.filter import cd_filter_dev
+        buf = getattr(self, "E_next", None) if next_capture else self.E
+        if buf is None:
+            raise ValueError("no capture loaded for next_capture=True (load_next first)")
+        self._filter_done()                        # (a filter on stream 2 may still be reading the buffer)
+        if getattr(self, "_cd_buf", None) is None:
+            self._cd_buf = DeviceArray((self.nmodes, self.L), self.ct)
+        cd_filter_dev(buf, self._cd_buf, fs, D, -L, wl0=wl0, N=N)
+        buf.copy_from(self._cd_buf)
+        if getattr(self, "_prep", None) is not None:
+            self.invalidate()
+
     def _acq_chunk_rule(self, power, mu, o):
         return _k.pit_acq_chunk(power, mu, self.nmodes * self.Ntaps, self.rt, o.get("gear"), o.get("acq_bound"))
 

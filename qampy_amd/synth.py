@@ -32,7 +32,7 @@ def _rrc_frequency_response(n, os, beta):
 
 
 def make_capture(M, nsym, nmodes=2, os=2, snr_db=None, theta=None, dgd=None, linewidth=0., fb=20e9, beta=0.1,
-                 seed=1000, dtype=np.complex64, shift=0, symbols=None):
+                 seed=1000, dtype=np.complex64, shift=0, symbols=None, cd=None):
     """
     Build one impaired capture.
 
@@ -41,6 +41,9 @@ def make_capture(M, nsym, nmodes=2, os=2, snr_db=None, theta=None, dgd=None, lin
 
     ``shift`` circularly delays the waveform by that many samples (used by the data-aided tests, which need symbol
     ``i`` under the centre tap of window ``i``, cf. test/test_equalisation.py:109-110).
+
+    ``cd=(D, L, wl0)`` adds the chromatic dispersion of ``L`` metres of fibre last, by one full FFT per row as the reference's
+    add_dispersion (qampy/core/impairments.py:673-703); ``None`` leaves the capture as it was.
     """
     rng = np.random.default_rng(seed)
     alphabet = theory.coded_symbols_qam(M, dtype=np.complex128)
@@ -79,6 +82,11 @@ def make_capture(M, nsym, nmodes=2, os=2, snr_db=None, theta=None, dgd=None, lin
         x = x + sigma * (rng.standard_normal(x.shape) + 1j * rng.standard_normal(x.shape)) / np.sqrt(2)
     if shift:
         x = np.roll(x, shift, axis=1)
+    if cd is not None:
+        D_, L_, wl0 = cd
+        omega = 2 * np.pi * np.fft.fftfreq(L, d=1 / fs)
+        beta2 = D_ * wl0 ** 2 / (2 * np.pi * 2.99792458e8)
+        x = np.fft.ifft(np.fft.fft(x, axis=1) * np.exp(-0.5j * beta2 * L_ * omega ** 2), axis=1)
     return SignalQAM(np.ascontiguousarray(x.astype(dtype)), M, fb=fb, fs=fs, symbols=syms.astype(dtype),
                      coded_symbols=alphabet.astype(dtype))
 
@@ -113,7 +121,7 @@ def make_pilot_capture(M=256, frame_len=2 ** 16, seq_len=2 ** 10, ins_rat=32, nf
                 frame_len=frame_len, seq_len=seq_len, ins_rat=ins_rat, nframes=nframes)
 
 
-def make_capture_dev(M, nsym, nmodes=2, os=2, snr_db=None, theta=None, dgd=None, linewidth=0., fb=20e9, beta=0.1, seed=1000, E=None):
+def make_capture_dev(M, nsym, nmodes=2, os=2, snr_db=None, theta=None, dgd=None, linewidth=0., fb=20e9, beta=0.1, seed=1000, E=None, cd=None):
     """
     :func:`make_capture` on the GPU (``qh_synth_capture_c64_dev``, csrc/synth.hip): the capture never exists on the host.
     Same impairment conventions; time-domain filters instead of FFTs and a counter-based generator instead of numpy's, so
@@ -121,7 +129,8 @@ def make_capture_dev(M, nsym, nmodes=2, os=2, snr_db=None, theta=None, dgd=None,
 
     Returns ``dict(E=(nmodes, nsym*os) complex64, symbols=(nmodes, nsym) complex64, idx_tx=(nmodes, nsym) int32, alphabet=(M,))``
     of :class:`qampy_amd._lib.DeviceArray` plus ``fb, fs, M``.  ``E``: optional preallocated ``(nmodes, nsym*os)`` DeviceArray
-    (e.g. one channel of a :class:`qampy_amd.pipeline.ChannelBank`) to synthesise into.
+    (e.g. one channel of a :class:`qampy_amd.pipeline.ChannelBank`) to synthesise into.  ``cd=(D, L, wl0)`` adds the chromatic
+    dispersion of ``L`` metres of fibre last, circularly, with :func:`qampy_amd.core.filter.cd_filter_dev` (csrc/cd.hip).
     """
     from . import _lib
     from ._lib import DeviceArray
@@ -137,6 +146,13 @@ def make_capture_dev(M, nsym, nmodes=2, os=2, snr_db=None, theta=None, dgd=None,
               float(snr_db if snr_db is not None else 0.), int(snr_db is not None), float(theta if theta is not None else 0.),
               float((dgd or 0.) * fs), int(theta is not None and nmodes == 2), float(2 * np.pi * linewidth / fs if linewidth else 0.),
               int(seed))
+    if cd is not None:
+        from .core.filter import cd_filter_dev
+        D_, L_, wl0 = cd
+        tmp = DeviceArray((nmodes, nsym * os), np.complex64)
+        cd_filter_dev(E, tmp, fs, D_, L_, wl0=wl0)
+        E.copy_from(tmp)
+        _lib.stream_sync()
     return dict(E=E, symbols=sy, idx_tx=idx, alphabet=d_al, alphabet_host=alphabet, fb=fb, fs=fs, M=M)
 
 
