@@ -2,7 +2,7 @@
 """
 bench.py - equalised MSym/s of the adaptive-equaliser + carrier-recovery hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|ns|c2|c1|c5] [--tier b|a] [--tol T] [--no-cpu-baseline] ...
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|ns|c2|c1|c5] [--tier b|a] [--tol T] [--full] [--no-cpu-baseline] ...
 
 One "step" = one pass of the hot path (dual-mode tap training -> filter application -> blind phase search, unwrap and
 de-rotation of every mode) over one synthetic dual-polarisation 2 SPS capture that is already resident in HBM.
@@ -20,27 +20,33 @@ sequential recurrence is below `tol` (default 1e-3, relative).  The timed pipeli
 `value` only if it certifies itself in this very run: every stage converged by that estimate AND, measured against the exact
 path run beside it on the same capture, the recovered output is within tol (relative rms), the taps within 3 tol (relative) and
 the symbol errors within +-3 per mode.  Otherwise, or with `--tier a`, the headline is the exact path's.  Both are always in
-the line (`tier_a`, `tier_b`, `headline_tier`), and `speedup_vs_cpu` is keyed to the tier that produced `value`.
+the line (`tier_a`, `tier_b`, `headline_tier`); with `--full`, `speedup_vs_cpu` is keyed to the tier that produced `value`.
 
-OUTPUT (round 6).  stdout carries ONE compact JSON line (`headline_line`: a whitelist, <= 6 KB enforced before it is printed) with the contract's
-keys (metric, value, unit, n_gpus, steps, warmup, ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config), `roofline`,
-`cpu_baseline`, the certificate (`tier_b.checks`, `tier_b.elementwise_summary`, `tier_b_tight`), `parity_vs_cpu`, `ser`, `ms_per_step_per_rank`,
-`comm_backend`.  The FULL result - everything listed below - is written to `--detail-out` (default gpurun_out/bench_detail.json); round 5 printed
-it all as one 30 KB line, which the driver could not parse.  The certificate at tol = 1e-4 includes the ELEMENT-WISE bar of the exact path
-(rtol = atol = 1e-4 on every tap and every equaliser-output sample).
+PLAIN AND FULL RUNS.  A plain run does what its headline needs and no more: it sets up, warms up, times the K steps, certifies tier b against
+the exact path as above (the certificate decides which tier is the headline), writes `--dump-outputs` if asked and prints the line.  `--full`
+adds everything else the benchmark measures or checks: timing runs of their own for the roofline and the one-capture / one-receiver figures,
+the other shapes and tolerances listed below, the reference's own benchmark definitions, the CPU baselines and the channel bank.  What the
+timed steps compute and how they are timed is the same in both.
+
+OUTPUT.  stdout carries ONE compact JSON line (`headline_line`: a whitelist, <= 6 KB enforced before it is printed) with the contract's keys
+(metric, value, unit, n_gpus, steps, warmup, ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config), the certificate
+(`tier_b.checks`, `tier_b.elementwise_summary`), `ser`, `ms_per_step_per_rank`, `comm_backend`, and with `--full` also `roofline`, `cpu_baseline`,
+`tier_b_tight` and `parity_vs_cpu`.  The whole result is written to `--detail-out`; round 5 printed it all as one 30 KB line, which the driver
+could not parse.  The certificate at tol = 1e-4 includes the ELEMENT-WISE bar of the exact path (rtol = atol = 1e-4 on every tap and every
+equaliser-output sample).
 
 `--dump-outputs DIR` writes what the headline path returned for its last timed step (rank 0: taps, error traces, equaliser output, phase,
 recovered output, test-angle indices, step sizes) as DIR/<name>.npy, float32 / float64, at most 64 MB (`dump_files`).  The captures depend on
 the arguments only, so two builds run with the same arguments can be compared file by file.
 
-The full result (N = 1, workload c3) additionally carries
+A --full run (N = 1, workload c3) additionally carries
   tier_b_loose  the same solver held to tol = 1e-2 (the SER-equivalent tier), informational
   cert_24dB     the same shape at 24 dB SNR, where both paths make thousands of symbol errors: counts within 3 sigma per mode
   ns, c2        the north star's 10^7-symbol shape and BASELINE configs[1]: tier b + exact path + certificate
   roofline      dominant kernel of the step (largest total kernel time): for the relaxation passes and the phase search the bound is
                 VALU issue (achieved / peak in wave instructions per second, instruction count from the PMC profile of the same
                 kernel sources when there is one), with the HBM view (algorithmic bytes / 8 TB/s) and the flop view beside it
-  cpu_baseline  the oracle's reference-flag OpenMP build ("port" of the pythran loops, exact recurrence) on this box's host cores:
+  cpu_baseline  the oracle's reference-flag OpenMP build ("port" of the pythran loops, exact recurrence) on the GPU host's cores:
                 the whole capture with all threads (3 runs) and with one thread, CPU model, H2D / D2H times
   parity_vs_cpu, channel_bank (+ its own CPU leg), stages_ms, ser
 """
@@ -613,7 +619,6 @@ def run_c5(args, cfg):
     nfr = best["frames"]
     if args.dump_outputs:
         write_dump(dump_files(best.pop("arrays")), args.dump_outputs)
-    one = pilot_chain(cap, frames=[0])                      # the same capture, first frame only (what rounds 1-3 timed)
     # the sequential heart of a frame: Niter sweeps x 3 stages x seq_len steps of the exact recurrence with the adaptive step, two modes side by side
     steps_per_frame = 3 * 30 * 1024
     out = dict(metric="equalised MSym/s (2-pol, 2 SPS; a step recovers %d frames of one capture)" % nfr, value=round(cfg["nsym"] * nfr * args.steps / el / 1e6, 4), unit="MSym/s", n_gpus=1,
@@ -625,14 +630,16 @@ def run_c5(args, cfg):
                            batching="frame sync once per capture; pre-convergence stages frame after frame (the reference hands the taps on in place), the 2 x 30 "
                                     "pilot-aided sweeps of frames 1.. together: one launch per stage over all (frame, mode) chains"),
                stages_ms={k: round(float(np.mean([r["stages_ms"][k] for r in runs])), 3) for k in best["stages_ms"]},
-               single_frame=dict(ms=round(one["seconds"] * 1e3, 3), stages_ms={k: round(v, 3) for k, v in one["stages_ms"].items()}),
                ser=dict(payload_per_mode=best["ser"], sync_ok=best["ok"]), device=_lib.device_name(),
                roofline=dict(bound="latency (dependent instruction issue)", kernel="pilot-sequence training (exact recurrence, adaptive step: 3 x 30 sweeps of 1024 steps per frame)",
                              achieved=round(steps_per_frame * nfr / (best["stages_ms"]["pilot_equaliser_and_filter"] * 1e-3) / 1e6, 3), peak=None, unit="M sequential steps/s",
                              frac=None, traffic=None,
                              note="sequential chains of 1024 steps x 30 sweeps: neither HBM nor MFMA bounds them - one dependent step costs ~130 ns on a lone "
                                   "wavefront (DESIGN.md 3.1); what the batching buys is that the chains of all frames and modes run side by side"))
-    if not args.no_cpu_baseline:
+    if args.full:
+        one = pilot_chain(cap, frames=[0])                      # the same capture, first frame only (what rounds 1-3 timed)
+        out["single_frame"] = dict(ms=round(one["seconds"] * 1e3, 3), stages_ms={k: round(v, 3) for k, v in one["stages_ms"].items()})
+    if args.full and not args.no_cpu_baseline:
         from oracle import oracle
         try:
             oracle.build(fast_native=True)
@@ -761,12 +768,15 @@ def make_pool(cfg, nsym, rx, first_seed, ncap):
     return pool
 
 
-def run_pair(cfg, sig, nsym, steps, warmup, barrier_sync, pit, exact_steps, tol_check, overlap=False, in_flight=1, pool_n=1, first_seed=1000, after=None):
+def run_pair(cfg, sig, nsym, steps, warmup, barrier_sync, pit, exact_steps, tol_check, overlap=False, in_flight=1, pool_n=1, first_seed=1000, after=None,
+             full=True):
     """Tier b (timed, `steps` passes) and the exact path beside it on the same resident capture: both blocks, the measured
     deviation and the certificate.  Returns (tier_b, tier_a, extras for the roofline).  after: timed_steps' hook, for tier b's timed passes.
 
     overlap: the timed passes are consecutive captures of a running receiver (ResidentReceiver.run(overlap=True): phase search of pass k
-    beside the training of pass k + 1); the same receiver is then timed one capture at a time as well (`one_capture_at_a_time`)."""
+    beside the training of pass k + 1); the same receiver is then timed one capture at a time as well (`one_capture_at_a_time`).
+    full: also the timing runs of their own that only the roofline and the informational figures read (every pass event-timed,
+    one capture at a time, one receiver of a group); the certificate does not depend on them."""
     overlap = bool(overlap and cfg["A"])
     group, pool = None, None
     if in_flight > 1 and overlap:
@@ -785,7 +795,7 @@ def run_pair(cfg, sig, nsym, steps, warmup, barrier_sync, pit, exact_steps, tol_
         elapsed, stage_ms, pass_ms, acq_ms = timed_steps(rx, steps, warmup, barrier_sync, overlap=overlap, pool=pool, after=after)
     reports = rx.pit_reports()
     pass_all = None
-    if group is None and not getattr(rx, "exchanges", None):
+    if full and group is None and not getattr(rx, "exchanges", None):
         # every relaxation pass timed (an event pair per pass: ~11 us of idle stream per pass - a run of its own, after the timed region, in the same
         # mode): the dominant kernel's AVERAGE launch duration for the roofline (the timed region itself times one pass per sweep, pass 1)
         from qampy_amd import _lib as _l
@@ -816,26 +826,28 @@ def run_pair(cfg, sig, nsym, steps, warmup, barrier_sync, pit, exact_steps, tol_
         same = all(np.array_equal(o[k], mine[k]) for o in others for k in ("wxy", "eq", "out"))
         conv = all(r["converged"] for rp in group.pit_reports() for r in rp)
         del others, mine
-        k0 = max(2, min(steps, 10))
         from qampy_amd import _lib as _l
-        el0, ms0, _, _ = group.map(lambda r: timed_steps(r, k0, 1, _l.sync, overlap=True), which=[0])[0]      # on the receiver's own thread (its streams, its scratch)
         tb["in_flight"] = dict(receivers=in_flight, all_receivers_identical=bool(same), all_receivers_converged=bool(conv),
                                what="%d captures on the GPU at a time, one host thread and one set of library streams per receiver (pipeline.ReceiverGroup); "
-                                    "pass_ms / stages_ms are means over all receivers inside the timed region" % in_flight,
-                               one_receiver=dict(value=round(nsym * k0 / el0 / 1e6, 4), ms_per_step=round(el0 / k0 * 1e3, 3), steps=k0,
-                                                 stages_ms={n: round(t, 3) for n, t in zip(names, ms0)}))
+                                    "pass_ms / stages_ms are means over all receivers inside the timed region" % in_flight)
+        if full:
+            k0 = max(2, min(steps, 10))
+            el0, ms0, _, _ = group.map(lambda r: timed_steps(r, k0, 1, _l.sync, overlap=True), which=[0])[0]      # on the receiver's own thread (its streams, its scratch)
+            tb["in_flight"]["one_receiver"] = dict(value=round(nsym * k0 / el0 / 1e6, 4), ms_per_step=round(el0 / k0 * 1e3, 3), steps=k0,
+                                                   stages_ms={n: round(t, 3) for n, t in zip(names, ms0)})
         tb["converged"] = bool(tb["converged"] and same and conv)
     if overlap:
-        k1 = max(2, min(steps, 5))
-        if group is not None:
-            el1, ms1, _, _ = group.map(lambda r: timed_steps(r, k1, 1, _l.sync), which=[0])[0]
-        else:
-            el1, ms1, _, _ = timed_steps(rx, k1, 1, barrier_sync)
         tb["pipelining"] = dict(
             what="consecutive captures: the phase search of pass k runs on stream 2 beside the training of pass k + 1 (same kernels, same results bit for bit); "
-                 "stages_ms are event pairs on the stream each stage ran on, so their sum exceeds ms_per_step by what ran side by side",
-            one_capture_at_a_time=dict(value=round(nsym * k1 / el1 / 1e6, 4), ms_per_step=round(el1 / k1 * 1e3, 3), steps=k1,
-                                       stages_ms={n: round(t, 3) for n, t in zip(names, ms1)}))
+                 "stages_ms are event pairs on the stream each stage ran on, so their sum exceeds ms_per_step by what ran side by side")
+        if full:
+            k1 = max(2, min(steps, 5))
+            if group is not None:
+                el1, ms1, _, _ = group.map(lambda r: timed_steps(r, k1, 1, _l.sync), which=[0])[0]
+            else:
+                el1, ms1, _, _ = timed_steps(rx, k1, 1, barrier_sync)
+            tb["pipelining"]["one_capture_at_a_time"] = dict(value=round(nsym * k1 / el1 / 1e6, 4), ms_per_step=round(el1 / k1 * 1e3, 3), steps=k1,
+                                                             stages_ms={n: round(t, 3) for n, t in zip(names, ms1)})
     ta = None
     if exact_steps > 0:
         rxa = make_receiver(cfg, sig, tier="a")
@@ -1386,20 +1398,24 @@ def main():
                     help="trainer of the timed pipeline: b = parallel-in-time solver of the recurrence held to --tol (headline only if it certifies "
                          "itself in this run, device estimate AND measurement against the exact path); a = the exact sequential recurrence")
     ap.add_argument("--tol", type=float, default=0., help="tier b: accepted relative rms deviation of the equaliser output from the sequential recurrence (0 = library default 1e-3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-sample", type=int, default=None, help="symbol periods the all-thread CPU baseline processes (default: the whole capture)")
-    ap.add_argument("--cpu-sample-1t", type=int, default=None, help="symbol periods of the one-thread CPU run (default: the whole capture)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU legs")
+    ap.add_argument("--cpu-sample", type=int, default=None, help="--full: symbol periods the all-thread CPU baseline processes (default: the whole capture)")
+    ap.add_argument("--cpu-sample-1t", type=int, default=None, help="--full: symbol periods of the one-thread CPU run (default: the whole capture)")
     ap.add_argument("--exact-steps", type=int, default=2, help="timed passes of the exact path beside tier b (N = 1)")
     ap.add_argument("--host-synth", action="store_true", help="generate the capture with the host (numpy) generator instead of on the GPU")
     ap.add_argument("--bank-trainer", default="iterative", choices=["auto", "iterative"])
-    ap.add_argument("--bank", type=int, default=128, help="channels of the informational channel-bank run at N=1 (0 = skip)")
-    ap.add_argument("--cpu-bank-workers", type=int, default=-1, help="concurrent single-threaded CPU pipelines of the bank's CPU leg (-1: min(cores, 128), 0: skip)")
+    ap.add_argument("--bank", type=int, default=128, help="--full: channels of the informational channel-bank run at N=1 (0 = skip)")
+    ap.add_argument("--cpu-bank-workers", type=int, default=-1, help="--full: concurrent single-threaded CPU pipelines of the bank's CPU leg (-1: min(cores, 128), 0: skip)")
     ap.add_argument("--pool", type=int, default=8, help="tier b, consecutive captures: resident captures rotated through the receiver (seeds 1000 + ((rank + j) mod pool)); 1 = the same "
                                                        "capture every step (rounds 1-4)")
     ap.add_argument("--in-flight", type=int, default=1, help="tier b: captures on the GPU at a time (pipeline.ReceiverGroup, one host thread per receiver); 1 = one receiver")
     ap.add_argument("--no-overlap", action="store_true", help="tier b: time one capture at a time only (default: consecutive captures, the phase search of "
                                                               "pass k on stream 2 beside the training of pass k + 1)")
-    ap.add_argument("--no-extra-shapes", action="store_true", help="skip the ns / c2 / 24 dB / loose-tolerance blocks of the default line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: timing runs of their own for the roofline and the one-capture / one-receiver "
+                         "figures, the other shapes and tolerances, the reference's benchmark definitions, the CPU baselines and the channel bank.  Without it a run "
+                         "sets up, warms up, times the K steps, certifies tier b against the exact path and prints the line")
+    ap.add_argument("--no-extra-shapes", action="store_true", help="--full: skip the ns / c2 / 24 dB / loose-tolerance blocks")
     ap.add_argument("--split-capture", action="store_true",
                     help="N > 1: ONE capture, the segments of the tier-b trainer spread over the ranks with an all-reduce of their end taps per pass "
                          "(qampy_amd.distributed; strong scaling, informational - the default is one independent capture per GPU)")
@@ -1519,7 +1535,7 @@ def main():
         for t_ in tol_ladder:
             pit, tol_check = dict(tol=t_), t_
             tier_b, tier_a, ex = run_pair(cfg, sig, nsym, args.steps, args.warmup, barrier_sync, pit, args.exact_steps if world == 1 else 0, tol_check, overlap=overlap, in_flight=args.in_flight,
-                                          pool_n=max(1, args.pool), first_seed=sharding.channel_seed(rank), after=keep_last)
+                                          pool_n=max(1, args.pool), first_seed=sharding.channel_seed(rank), after=keep_last, full=args.full)
             if tier_b["certified"] or world > 1:         # (N > 1: every rank must take the same rung - the tightest; its certificate is all-reduced below)
                 break
             tried.append(dict(tol=t_, certified=False, checks=tier_b.get("checks"), passes=[st["P"] for st in tier_b["stages"]], value=tier_b["value"],
@@ -1593,10 +1609,12 @@ def main():
             if tier_b.get("capture_pool"):
                 out["config"]["capture_pool"] = ("%d different resident captures per GPU (seeds %s), rotated: consecutive captures differ; --pool 1 feeds the same capture every step"
                                                  % (tier_b["capture_pool"]["captures"], tier_b["capture_pool"]["seeds"]))
-            out["one_capture_at_a_time"] = tier_b["pipelining"]["one_capture_at_a_time"]
+            if tier_b["pipelining"].get("one_capture_at_a_time"):
+                out["one_capture_at_a_time"] = tier_b["pipelining"]["one_capture_at_a_time"]
         if tier_b.get("in_flight"):
             out["config"]["in_flight"] = "%d captures on the GPU at a time (ReceiverGroup: one host thread + stream set per receiver); --in-flight 1 for one receiver" % tier_b["in_flight"]["receivers"]
-            out["one_receiver"] = tier_b["in_flight"]["one_receiver"]
+            if tier_b["in_flight"].get("one_receiver"):
+                out["one_receiver"] = tier_b["in_flight"]["one_receiver"]
     if tier_a is not None:
         out["tier_a"] = tier_a
 
@@ -1634,134 +1652,136 @@ def main():
     out["config"]["train_mode"] = (("parallel-in-time solver of the reference's recurrence (tier b), certified in-run against the exact path at tol %g" % tol_check) if use_b else
                                    ("parallel-in-time (tier b), NOT certified" if uncertified_b else "exact sequential recurrence (tier a)"))
 
-    # ---- roofline of the dominant kernel (largest total kernel time per step)
-    if use_b or uncertified_b:
-        # launch duration of a pass kernel: the average over ALL its launches (every pass event-timed in a run of its own, run_pair), else pass 1's
-        def _pms(st_):
-            return st_.get("pass_ms_all_launches") or st_["pass_ms"]
-        cands = [(_pms(tier_b["stages"][s]) * tier_b["stages"][s]["P"], "train%d:%s relaxation pass" % (s + 1, cfg["methods"][s]),
-                  train_bytes[s], _pms(tier_b["stages"][s])) for s in range(rx.nstage)]
-        cands.append((stage_ms[0], "gram", stage_bytes[0], stage_ms[0]))
-        if cfg["A"]:
-            # the phase search enqueued in parts between the next capture's passes (pipeline.py): the stage's event pair then spans most of a step;
-            # its kernel time is what the same kernels took one capture at a time
+    if args.full:
+        # ---- roofline of the dominant kernel (largest total kernel time per step); --full only: the launch times it rests on come from
+        # run_pair's timing runs of their own (every pass event-timed, the phase search one capture at a time)
+        if use_b or uncertified_b:
+            # launch duration of a pass kernel: the average over ALL its launches (every pass event-timed in a run of its own, run_pair), else pass 1's
+            def _pms(st_):
+                return st_.get("pass_ms_all_launches") or st_["pass_ms"]
+            cands = [(_pms(tier_b["stages"][s]) * tier_b["stages"][s]["P"], "train%d:%s relaxation pass" % (s + 1, cfg["methods"][s]),
+                      train_bytes[s], _pms(tier_b["stages"][s])) for s in range(rx.nstage)]
+            cands.append((stage_ms[0], "gram", stage_bytes[0], stage_ms[0]))
+            if cfg["A"]:
+                # the phase search enqueued in parts between the next capture's passes (pipeline.py): the stage's event pair then spans most of a step;
+                # its kernel time is what the same kernels took one capture at a time
+                one = ((tier_b.get("pipelining") or {}).get("one_capture_at_a_time") or {}).get("stages_ms") or {}
+                bps_ms = one.get("bps_recover", stage_ms[-1]) if (overlap and int(getattr(rx, "post_parts", 0)) != 1) else stage_ms[-1]
+                cands.append((bps_ms, "bps_recover", stage_bytes[-1], bps_ms))
+            tot, kname, kbytes, kms = max(cands)
+            hbm = dict(achieved=round(kbytes / (kms * 1e-3) / 1e9, 3), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(kbytes / (kms * 1e-3) / 1e9 / HBM_PEAK_GBS, 6),
+                       algorithmic_bytes=int(kbytes))
+            roofline = dict(bound="hbm", kernel=kname, achieved=hbm["achieved"], peak=HBM_PEAK_GBS, unit="GB/s", frac=hbm["frac"], traffic=None,
+                            algorithmic_bytes=int(kbytes), launch_ms=round(kms, 3), launches_per_step=None, pipeline=tier_b["pipeline_hbm"])
+            instr = pmc_json("pmc_instr", args.workload)
+            if kname == "bps_recover" and rx.ct == np.complex64 and cfg["A"] <= 64:
+                # streaming phase search: lane <-> test angle, VALU instructions per distance row and wave
+                NL = max(1, int(round(np.sqrt(cfg["M"]))) // 2)
+                per_sym, src = 20.0 + 2 * NL, "ISA count of bps_stream_kernel (20 + 2 levels per axis)"
+                hit = [v for k, v in (instr or {}).get("kernels", {}).items() if k.startswith("qh::bps_stream_kernel")]
+                C_, W = 1024, 2 * cfg["Nbps"]
+                rows = -(-nsym // C_) * (-(-(C_ + W - 1) // 16) * 16) * rx.modes.size          # distance rows incl. the 2N-1 halo of every chunk
+                if hit and hit[0].get("SQ_INSTS_VALU"):
+                    per_sym, src = float(hit[0]["SQ_INSTS_VALU"]) / rows, "SQ_INSTS_VALU / distance rows (profiles/pmc_instr_%s.json)" % args.workload
+                winstr = rows * per_sym
+                sflops = nsym * rx.modes.size * cfg["A"] * 25.0                         # slicer search ~ A x 25 flop per symbol and mode
+                roofline.update(bound="valu-fp32", achieved=round(sflops / (kms * 1e-3) / 1e12, 3), peak=VALU_PEAK_TFLOPS, unit="TFLOP/s",
+                                frac=round(sflops / (kms * 1e-3) / 1e12 / VALU_PEAK_TFLOPS, 4), algorithmic_flops=int(sflops),
+                                issue_frac=round(winstr / (kms * 1e-3) / 1e9 / VALU_PEAK_GINSTR, 4),
+                                issue=dict(achieved=round(winstr / (kms * 1e-3) / 1e9, 1), peak=VALU_PEAK_GINSTR, unit="G wave-instr/s"),
+                                hbm=hbm, valu_instr_per_symbol=round(per_sym, 2), valu_instr_source=src,
+                                note="lane <-> test angle, one wave per 1024 symbols; the stage time also holds alphabet analysis, unwrap scan and de-rotation")
+            if "relaxation pass" in kname:
+                # what bounds the pass kernel: instruction issue of the fp32 vector units, not HBM
+                st = tier_b["stages"][int(kname[5]) - 1]
+                chains = st["S"] * rx.modes.size
+                ntot = rx.nmodes * rx.Ntaps
+                flops = chains * st["seg_len"] * (2 * ntot) * 8.0           # filter + update: 2 x ntot complex multiply-adds per chain and step
+                tpl8 = 11 if rx.nmodes * -(-rx.Ntaps // 11) <= 8 and 11 * -(-rx.Ntaps // 11) - rx.Ntaps <= 3 else (6 if rx.nmodes * -(-rx.Ntaps // 6) <= 8 and 6 * -(-rx.Ntaps // 6) - rx.Ntaps <= 3 else 0)
+                lpc = 8 if chains > 4096 and tpl8 else 16                   # seg_lanes (train_seg.h)
+                waves = -(-chains // (64 // lpc))
+                ipw, src = float(SEG_INSTR_PER_WAVE_STEP[lpc]), "ISA count of the main loop incl. s_nop / s_waitcnt (DESIGN.md 3.2.2)"
+                mid = _lib.METHOD_ID[cfg["methods"][int(kname[5]) - 1]]
+                hit = [v for k, v in (instr or {}).get("kernels", {}).items() if k.startswith("qh::train_seg_kernel<float, %d," % mid)]
+                if hit and hit[0].get("SQ_INSTS_VALU") and hit[0].get("SQ_WAVES"):
+                    ipw = float(hit[0]["SQ_INSTS_VALU"]) / (float(hit[0]["SQ_WAVES"]) * st["seg_len"])
+                    src = "SQ_INSTS_VALU / (SQ_WAVES x steps per chain) of the same kernel sources (profiles/pmc_instr_%s.json)" % args.workload
+                winstr = waves * st["seg_len"] * ipw
+                # The roofline of this kernel is the packed-fp32 VECTOR peak (intensity 54 flop/B against a machine balance of ~20: the compute
+                # side binds; no GEMM shape at 2 output modes, so not MFMA): `achieved` = ALGORITHMIC flops of one launch (filter +
+                # update = 2 x nmodes x ntaps complex multiply-adds x 8 flop per chain and step) / the event-timed launch duration, `frac` = that over
+                # 157.3 TFLOP/s.  `issue_frac` beside it is the utilisation view (all vector instructions the kernel issues - DPP adds, selects,
+                # error function included - against 1024 SIMDs x 2.4 GHz / 4 cycles): how busy the issue ports are, not how much of it is useful.
+                roofline.update(bound="valu-fp32", achieved=round(flops / (kms * 1e-3) / 1e12, 3), peak=VALU_PEAK_TFLOPS, unit="TFLOP/s",
+                                frac=round(flops / (kms * 1e-3) / 1e12 / VALU_PEAK_TFLOPS, 4), algorithmic_flops=int(flops), hbm=hbm, launches_per_step=st["P"],
+                                issue_frac=round(winstr / (kms * 1e-3) / 1e9 / VALU_PEAK_GINSTR, 4),
+                                issue=dict(achieved=round(winstr / (kms * 1e-3) / 1e9, 1), peak=VALU_PEAK_GINSTR, unit="G wave-instr/s", valu_instr_per_wave_step=round(ipw, 1),
+                                           irreducible_pk_fma_per_wave_step=round((64 // lpc) * 2 * ntot * 4 / 2 / 64.0, 1), valu_instr_source=src),
+                                chains=int(chains), lanes_per_chain=lpc, waves=int(waves), waves_per_simd=round(waves / 1024.0, 2), steps_per_chain=int(st["seg_len"]),
+                                launch_ms_by_pass=st.get("pass_ms_by_pass"), launch_ms_pass1_in_timed_region=st["pass_ms"],
+                                launch_ms_source="average over ALL launches of the kernel, every pass event-timed on the library stream in a run of its own right after the timed region "
+                                                 "(same receiver, same mode: consecutive captures, phase search and next capture's preparation beside the passes); "
+                                                 "the first pass of a sweep shares the chip with them (launch_ms_by_pass)" if st.get("pass_ms_all_launches") else "pass 1 of every sweep, event-timed inside the timed region",
+                                note="one launch trains all segments of the sweep (%d lanes per chain, %d chains per wave64, one wave per SIMD); frac = algorithmic flops of the "
+                                     "recurrence / packed-fp32 vector peak; issue_frac = vector instructions issued / nominal issue rate; `hbm`: algorithmic bytes of one sweep "
+                                     "(read E, write err) against 8 TB/s" % (lpc, 64 // lpc))
+            # ---- whole step: useful arithmetic and traffic against the fused bound - what the NUMBER of passes costs
+            ntot_ = rx.nmodes * rx.Ntaps
+            useful = sum(rx.Niter[s2] * rx.TrSyms[s2] * nsel * 2 * ntot_ * 8.0 for s2 in range(rx.nstage)) + rx.N * nsel * ntot_ * 8.0 \
+                + (rx.N * nsel * cfg["A"] * 25.0 if cfg["A"] else 0.0)
+            moved = sum(tier_b["stages"][s2]["P"] * train_bytes[s2] for s2 in range(rx.nstage)) + stage_bytes[-2 if cfg["A"] else -1] + (stage_bytes[-1] if cfg["A"] else 0)
+            roofline["step"] = dict(useful_flops=int(useful), useful_flops_frac=round(useful / (ms_timed * 1e-3) / 1e12 / VALU_PEAK_TFLOPS, 4),
+                                    passes=[st_["P"] for st_ in tier_b["stages"]], sweeps_of_the_recurrence=[int(n) for n in rx.Niter],
+                                    algorithmic_bytes_moved=int(moved), fused_bound_bytes=int(FUSED_BYTES_PER_SYM * nsym),
+                                    traffic_vs_fused=round(moved / float(FUSED_BYTES_PER_SYM * nsym), 2),
+                                    note="useful flops = the sweeps of the recurrence themselves (once each) + filter + slicer phase search (SURVEY.md 8d); bytes moved = "
+                                         "every pass re-reads the capture and re-writes the error trace: passes x 48 B + filter 48 B + search 40 B per symbol against the fused 88 B")
+            roofline["useful_flops_frac"] = roofline["step"]["useful_flops_frac"]
+            roofline["traffic_vs_fused"] = roofline["step"]["traffic_vs_fused"]
+        else:
+            dom = int(np.argmax(head_ms))
+            achieved = stage_bytes[dom] / (head_ms[dom] * 1e-3) / 1e9
+            roofline = dict(bound="latency (dependent instruction issue)" if 1 <= dom <= rx.nstage else "hbm", kernel=stage_names[dom], achieved=round(achieved, 3), peak=HBM_PEAK_GBS,
+                            unit="GB/s", frac=round(achieved / HBM_PEAK_GBS, 6), traffic=None, algorithmic_bytes=int(stage_bytes[dom]),
+                            note="exact sequential LMS recurrence: dependent-issue bound, one workgroup per output mode (DESIGN.md 3.1); HBM figure for reference")
+        # measured HBM traffic of the dominant kernel: from the PMC passes of the same workload (scripts/gpu_pmc.sh ->
+        # profiles/pmc_traffic_<workload>.json), quoted only while the kernel sources are the ones that were profiled
+        pmc = pmc_json("pmc_traffic", args.workload)
+        if pmc:
+            kern = roofline["kernel"]
+            pat = None
+            if "relaxation pass" in kern:
+                pat = "qh::train_seg_kernel<float, %d," % _lib.METHOD_ID[cfg["methods"][int(kern[5]) - 1]]
+            elif kern.startswith("train"):
+                mid = _lib.METHOD_ID[cfg["methods"][int(kern[5]) - 1]]
+                pat = ("qh::train_la_kernel<float, %d," % mid, "qh::train_bi_kernel<float, %d," % mid)
+            elif kern == "bps_recover":
+                pat = ("qh::bps_stream_kernel", "qh::bps_kernel<float>")
+            elif kern == "gram":
+                pat = "qh::gram_slide_kernel<float"
+            hit = [v for k, v in pmc["kernels"].items() if pat and k.startswith(pat)]
+            if hit:
+                roofline["traffic"] = hit[0]["hbm_bytes"]
+        else:
+            roofline["traffic_note"] = "no PMC traffic profile of these kernel sources under profiles/: not quoted"
+        out["roofline"] = roofline
+        # ---- the phase search beside it (detail file): slicer flops of SURVEY.md 8d (2 A 25 per symbol period) / the fused recovery
+        # stage one capture at a time (search + unwrap + de-rotation, event pair on its stream); the search kernel's own duration and its instruction
+        # counters are in profiles/r06_bps_profile.txt (rocprofv3)
+        if cfg["A"] and tier_b is not None:
             one = ((tier_b.get("pipelining") or {}).get("one_capture_at_a_time") or {}).get("stages_ms") or {}
-            bps_ms = one.get("bps_recover", stage_ms[-1]) if (overlap and int(getattr(rx, "post_parts", 0)) != 1) else stage_ms[-1]
-            cands.append((bps_ms, "bps_recover", stage_bytes[-1], bps_ms))
-        tot, kname, kbytes, kms = max(cands)
-        hbm = dict(achieved=round(kbytes / (kms * 1e-3) / 1e9, 3), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(kbytes / (kms * 1e-3) / 1e9 / HBM_PEAK_GBS, 6),
-                   algorithmic_bytes=int(kbytes))
-        roofline = dict(bound="hbm", kernel=kname, achieved=hbm["achieved"], peak=HBM_PEAK_GBS, unit="GB/s", frac=hbm["frac"], traffic=None,
-                        algorithmic_bytes=int(kbytes), launch_ms=round(kms, 3), launches_per_step=None, pipeline=tier_b["pipeline_hbm"])
-        instr = pmc_json("pmc_instr", args.workload)
-        if kname == "bps_recover" and rx.ct == np.complex64 and cfg["A"] <= 64:
-            # streaming phase search: lane <-> test angle, VALU instructions per distance row and wave
-            NL = max(1, int(round(np.sqrt(cfg["M"]))) // 2)
-            per_sym, src = 20.0 + 2 * NL, "ISA count of bps_stream_kernel (20 + 2 levels per axis)"
-            hit = [v for k, v in (instr or {}).get("kernels", {}).items() if k.startswith("qh::bps_stream_kernel")]
-            C_, W = 1024, 2 * cfg["Nbps"]
-            rows = -(-nsym // C_) * (-(-(C_ + W - 1) // 16) * 16) * rx.modes.size          # distance rows incl. the 2N-1 halo of every chunk
-            if hit and hit[0].get("SQ_INSTS_VALU"):
-                per_sym, src = float(hit[0]["SQ_INSTS_VALU"]) / rows, "SQ_INSTS_VALU / distance rows (profiles/pmc_instr_%s.json)" % args.workload
-            winstr = rows * per_sym
-            sflops = nsym * rx.modes.size * cfg["A"] * 25.0                         # slicer search ~ A x 25 flop per symbol and mode
-            roofline.update(bound="valu-fp32", achieved=round(sflops / (kms * 1e-3) / 1e12, 3), peak=VALU_PEAK_TFLOPS, unit="TFLOP/s",
-                            frac=round(sflops / (kms * 1e-3) / 1e12 / VALU_PEAK_TFLOPS, 4), algorithmic_flops=int(sflops),
-                            issue_frac=round(winstr / (kms * 1e-3) / 1e9 / VALU_PEAK_GINSTR, 4),
-                            issue=dict(achieved=round(winstr / (kms * 1e-3) / 1e9, 1), peak=VALU_PEAK_GINSTR, unit="G wave-instr/s"),
-                            hbm=hbm, valu_instr_per_symbol=round(per_sym, 2), valu_instr_source=src,
-                            note="lane <-> test angle, one wave per 1024 symbols; the stage time also holds alphabet analysis, unwrap scan and de-rotation")
-        if "relaxation pass" in kname:
-            # what bounds the pass kernel: instruction issue of the fp32 vector units, not HBM
-            st = tier_b["stages"][int(kname[5]) - 1]
-            chains = st["S"] * rx.modes.size
-            ntot = rx.nmodes * rx.Ntaps
-            flops = chains * st["seg_len"] * (2 * ntot) * 8.0           # filter + update: 2 x ntot complex multiply-adds per chain and step
-            tpl8 = 11 if rx.nmodes * -(-rx.Ntaps // 11) <= 8 and 11 * -(-rx.Ntaps // 11) - rx.Ntaps <= 3 else (6 if rx.nmodes * -(-rx.Ntaps // 6) <= 8 and 6 * -(-rx.Ntaps // 6) - rx.Ntaps <= 3 else 0)
-            lpc = 8 if chains > 4096 and tpl8 else 16                   # seg_lanes (train_seg.h)
-            waves = -(-chains // (64 // lpc))
-            ipw, src = float(SEG_INSTR_PER_WAVE_STEP[lpc]), "ISA count of the main loop incl. s_nop / s_waitcnt (DESIGN.md 3.2.2)"
-            mid = _lib.METHOD_ID[cfg["methods"][int(kname[5]) - 1]]
-            hit = [v for k, v in (instr or {}).get("kernels", {}).items() if k.startswith("qh::train_seg_kernel<float, %d," % mid)]
-            if hit and hit[0].get("SQ_INSTS_VALU") and hit[0].get("SQ_WAVES"):
-                ipw = float(hit[0]["SQ_INSTS_VALU"]) / (float(hit[0]["SQ_WAVES"]) * st["seg_len"])
-                src = "SQ_INSTS_VALU / (SQ_WAVES x steps per chain) of the same kernel sources (profiles/pmc_instr_%s.json)" % args.workload
-            winstr = waves * st["seg_len"] * ipw
-            # The roofline of this kernel is the packed-fp32 VECTOR peak (intensity 54 flop/B against a machine balance of ~20: the compute
-            # side binds; no GEMM shape at 2 output modes, so not MFMA): `achieved` = ALGORITHMIC flops of one launch (filter +
-            # update = 2 x nmodes x ntaps complex multiply-adds x 8 flop per chain and step) / the event-timed launch duration, `frac` = that over
-            # 157.3 TFLOP/s.  `issue_frac` beside it is the utilisation view (all vector instructions the kernel issues - DPP adds, selects,
-            # error function included - against 1024 SIMDs x 2.4 GHz / 4 cycles): how busy the issue ports are, not how much of it is useful.
-            roofline.update(bound="valu-fp32", achieved=round(flops / (kms * 1e-3) / 1e12, 3), peak=VALU_PEAK_TFLOPS, unit="TFLOP/s",
-                            frac=round(flops / (kms * 1e-3) / 1e12 / VALU_PEAK_TFLOPS, 4), algorithmic_flops=int(flops), hbm=hbm, launches_per_step=st["P"],
-                            issue_frac=round(winstr / (kms * 1e-3) / 1e9 / VALU_PEAK_GINSTR, 4),
-                            issue=dict(achieved=round(winstr / (kms * 1e-3) / 1e9, 1), peak=VALU_PEAK_GINSTR, unit="G wave-instr/s", valu_instr_per_wave_step=round(ipw, 1),
-                                       irreducible_pk_fma_per_wave_step=round((64 // lpc) * 2 * ntot * 4 / 2 / 64.0, 1), valu_instr_source=src),
-                            chains=int(chains), lanes_per_chain=lpc, waves=int(waves), waves_per_simd=round(waves / 1024.0, 2), steps_per_chain=int(st["seg_len"]),
-                            launch_ms_by_pass=st.get("pass_ms_by_pass"), launch_ms_pass1_in_timed_region=st["pass_ms"],
-                            launch_ms_source="average over ALL launches of the kernel, every pass event-timed on the library stream in a run of its own right after the timed region "
-                                             "(same receiver, same mode: consecutive captures, phase search and next capture's preparation beside the passes); "
-                                             "the first pass of a sweep shares the chip with them (launch_ms_by_pass)" if st.get("pass_ms_all_launches") else "pass 1 of every sweep, event-timed inside the timed region",
-                            note="one launch trains all segments of the sweep (%d lanes per chain, %d chains per wave64, one wave per SIMD); frac = algorithmic flops of the "
-                                 "recurrence / packed-fp32 vector peak; issue_frac = vector instructions issued / nominal issue rate; `hbm`: algorithmic bytes of one sweep "
-                                 "(read E, write err) against 8 TB/s" % (lpc, 64 // lpc))
-        # ---- whole step: useful arithmetic and traffic against the fused bound - what the NUMBER of passes costs
-        ntot_ = rx.nmodes * rx.Ntaps
-        useful = sum(rx.Niter[s2] * rx.TrSyms[s2] * nsel * 2 * ntot_ * 8.0 for s2 in range(rx.nstage)) + rx.N * nsel * ntot_ * 8.0 \
-            + (rx.N * nsel * cfg["A"] * 25.0 if cfg["A"] else 0.0)
-        moved = sum(tier_b["stages"][s2]["P"] * train_bytes[s2] for s2 in range(rx.nstage)) + stage_bytes[-2 if cfg["A"] else -1] + (stage_bytes[-1] if cfg["A"] else 0)
-        roofline["step"] = dict(useful_flops=int(useful), useful_flops_frac=round(useful / (ms_timed * 1e-3) / 1e12 / VALU_PEAK_TFLOPS, 4),
-                                passes=[st_["P"] for st_ in tier_b["stages"]], sweeps_of_the_recurrence=[int(n) for n in rx.Niter],
-                                algorithmic_bytes_moved=int(moved), fused_bound_bytes=int(FUSED_BYTES_PER_SYM * nsym),
-                                traffic_vs_fused=round(moved / float(FUSED_BYTES_PER_SYM * nsym), 2),
-                                note="useful flops = the sweeps of the recurrence themselves (once each) + filter + slicer phase search (SURVEY.md 8d); bytes moved = "
-                                     "every pass re-reads the capture and re-writes the error trace: passes x 48 B + filter 48 B + search 40 B per symbol against the fused 88 B")
-        roofline["useful_flops_frac"] = roofline["step"]["useful_flops_frac"]
-        roofline["traffic_vs_fused"] = roofline["step"]["traffic_vs_fused"]
-    else:
-        dom = int(np.argmax(head_ms))
-        achieved = stage_bytes[dom] / (head_ms[dom] * 1e-3) / 1e9
-        roofline = dict(bound="latency (dependent instruction issue)" if 1 <= dom <= rx.nstage else "hbm", kernel=stage_names[dom], achieved=round(achieved, 3), peak=HBM_PEAK_GBS,
-                        unit="GB/s", frac=round(achieved / HBM_PEAK_GBS, 6), traffic=None, algorithmic_bytes=int(stage_bytes[dom]),
-                        note="exact sequential LMS recurrence: dependent-issue bound, one workgroup per output mode (DESIGN.md 3.1); HBM figure for reference")
-    # measured HBM traffic of the dominant kernel: from the PMC passes of the same workload (scripts/gpu_pmc.sh ->
-    # profiles/pmc_traffic_<workload>.json), quoted only while the kernel sources are the ones that were profiled
-    pmc = pmc_json("pmc_traffic", args.workload)
-    if pmc:
-        kern = roofline["kernel"]
-        pat = None
-        if "relaxation pass" in kern:
-            pat = "qh::train_seg_kernel<float, %d," % _lib.METHOD_ID[cfg["methods"][int(kern[5]) - 1]]
-        elif kern.startswith("train"):
-            mid = _lib.METHOD_ID[cfg["methods"][int(kern[5]) - 1]]
-            pat = ("qh::train_la_kernel<float, %d," % mid, "qh::train_bi_kernel<float, %d," % mid)
-        elif kern == "bps_recover":
-            pat = ("qh::bps_stream_kernel", "qh::bps_kernel<float>")
-        elif kern == "gram":
-            pat = "qh::gram_slide_kernel<float"
-        hit = [v for k, v in pmc["kernels"].items() if pat and k.startswith(pat)]
-        if hit:
-            roofline["traffic"] = hit[0]["hbm_bytes"]
-    else:
-        roofline["traffic_note"] = "no PMC traffic profile of these kernel sources under profiles/: not quoted"
-    out["roofline"] = roofline
-    # ---- the phase search beside it (detail file): slicer flops of SURVEY.md 8d (2 A 25 per symbol period) / the fused recovery
-    # stage one capture at a time (search + unwrap + de-rotation, event pair on its stream); the search kernel's own duration and its instruction
-    # counters are in profiles/r06_bps_profile.txt (rocprofv3)
-    if cfg["A"] and tier_b is not None:
-        one = ((tier_b.get("pipelining") or {}).get("one_capture_at_a_time") or {}).get("stages_ms") or {}
-        ms_b = one.get("bps_recover")
-        if ms_b and ms_b > 0:
-            fl = nsym * nsel * cfg["A"] * 25.0
-            by = rx.N * bps_b["bps"]
-            out["roofline_phase_search"] = dict(bound="valu-fp32", kernel="bps_recover (analysis + search + unwrap + de-rotation, all modes)", launch_ms=round(ms_b, 3),
-                                                algorithmic_flops=int(fl), achieved=round(fl / (ms_b * 1e-3) / 1e12, 3), peak=VALU_PEAK_TFLOPS, unit="TFLOP/s",
-                                                frac=round(fl / (ms_b * 1e-3) / 1e12 / VALU_PEAK_TFLOPS, 4), algorithmic_bytes=int(by),
-                                                hbm=dict(achieved=round(by / (ms_b * 1e-3) / 1e9, 1), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(by / (ms_b * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)),
-                                                note="whole stage one capture at a time; the search kernel alone: profiles/r06_bps_profile.txt (358 us at C3: 0.24 of the peak)")
+            ms_b = one.get("bps_recover")
+            if ms_b and ms_b > 0:
+                fl = nsym * nsel * cfg["A"] * 25.0
+                by = rx.N * bps_b["bps"]
+                out["roofline_phase_search"] = dict(bound="valu-fp32", kernel="bps_recover (analysis + search + unwrap + de-rotation, all modes)", launch_ms=round(ms_b, 3),
+                                                    algorithmic_flops=int(fl), achieved=round(fl / (ms_b * 1e-3) / 1e12, 3), peak=VALU_PEAK_TFLOPS, unit="TFLOP/s",
+                                                    frac=round(fl / (ms_b * 1e-3) / 1e12 / VALU_PEAK_TFLOPS, 4), algorithmic_bytes=int(by),
+                                                    hbm=dict(achieved=round(by / (ms_b * 1e-3) / 1e9, 1), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(by / (ms_b * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)),
+                                                    note="whole stage one capture at a time; the search kernel alone: profiles/r06_bps_profile.txt (358 us at C3: 0.24 of the peak)")
 
-    # ---- the other shapes and tolerances of the default line (N = 1): loose tolerance, a capture with symbol errors, ns, c2
-    if world == 1 and args.tier == "b" and not args.no_extra_shapes and not split:
+    # ---- the other shapes and tolerances of a --full run (N = 1): loose tolerance, a capture with symbol errors, ns, c2
+    if args.full and world == 1 and args.tier == "b" and not args.no_extra_shapes and not split:
         try:
             ksteps = max(2, min(args.steps, 10))
             tb2, _, ex2 = run_pair(cfg, sig, nsym, ksteps, 1, barrier_sync, dict(pit, tol=1e-2), 0, 1e-2, overlap=overlap)
@@ -1825,7 +1845,7 @@ def main():
         except Exception as e:                    # informational blocks never take the headline down
             out["extra_shapes_error"] = "%s: %s" % (type(e).__name__, e)
 
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         sample = min(nsym, args.cpu_sample or nsym)
         cb = cpu_baseline(cfg, sig, sample, min(sample, args.cpu_sample_1t or sample))
         r_cpu = cb["result"]
@@ -1867,7 +1887,7 @@ def main():
         if tier_b:
             tier_b["speedup_vs_cpu"] = round(tier_b["value"] / out["cpu_baseline"]["value"], 2)
 
-    if world == 1 and args.bank > 1:
+    if args.full and world == 1 and args.bank > 1:
         del rx
         try:
             # channels x symbol periods bounded to what 128 captures of 2^22 periods take (bank buffers + block-iterative scratch)

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 R=gpurun_out/iter; rm -rf $R; mkdir -p $R
 export TMPDIR=/tmp
 timeout 1500 python -m pytest tests -q -m gpu -x > $R/gpu_tests.txt 2>&1; tail -5 $R/gpu_tests.txt
-timeout 900 python bench.py --bank 0 --no-cpu-baseline > $R/bench_c3.json 2> $R/bench_c3.err; tail -2 $R/bench_c3.err
+timeout 900 python bench.py --full --bank 0 --no-cpu-baseline > $R/bench_c3.json 2> $R/bench_c3.err; tail -2 $R/bench_c3.err
 python scripts/show_bench.py $R/bench_c3.json > $R/bench_c3.txt 2>&1; head -12 $R/bench_c3.txt | cut -c1-400
 python - <<'PY'
 import json

@@ -5,7 +5,7 @@ R=gpurun_out/knobs; rm -rf $R; mkdir -p $R
 export TMPDIR=/tmp
 for cfg in $*; do
   cus=${cfg%%:*}; n=${cfg##*:}
-  QAMPY_HIP_RESERVED_CUS=$cus QAMPY_POST_PARTS=$n timeout 300 python bench.py --bank 0 --no-cpu-baseline --no-extra-shapes --exact-steps 1 > $R/bench_${cus}_$n.json 2> $R/bench_${cus}_$n.err
+  QAMPY_HIP_RESERVED_CUS=$cus QAMPY_POST_PARTS=$n timeout 300 python bench.py --full --bank 0 --no-cpu-baseline --no-extra-shapes --exact-steps 1 > $R/bench_${cus}_$n.json 2> $R/bench_${cus}_$n.err
   python - $cus $n <<'PY'
 import json, sys
 cus, n = sys.argv[1:3]

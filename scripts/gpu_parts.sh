@@ -5,7 +5,7 @@ R=gpurun_out/parts; rm -rf $R; mkdir -p $R
 export TMPDIR=/tmp
 timeout 600 python -m pytest tests/test_gpu_split.py tests/test_gpu_functional.py -q -m gpu -x > $R/gpu_tests.txt 2>&1; tail -3 $R/gpu_tests.txt
 for n in $*; do
-  QAMPY_POST_PARTS=$n timeout 300 python bench.py --bank 0 --no-cpu-baseline --no-extra-shapes --exact-steps 1 > $R/bench_$n.json 2> $R/bench_$n.err
+  QAMPY_POST_PARTS=$n timeout 300 python bench.py --full --bank 0 --no-cpu-baseline --no-extra-shapes --exact-steps 1 > $R/bench_$n.json 2> $R/bench_$n.err
   python - $n <<'PY'
 import json, sys
 n=sys.argv[1]

@@ -5,7 +5,7 @@ R=gpurun_out/prep; rm -rf $R; mkdir -p $R
 export TMPDIR=/tmp
 for cfg in $*; do
   g=${cfg%%:*}; n=${cfg##*:}
-  QAMPY_HIP_HOOK_BEFORE=$g QAMPY_POST_PARTS=$n timeout 300 python bench.py --bank 0 --no-cpu-baseline --no-extra-shapes --exact-steps 1 > $R/bench_${g}_$n.json 2> $R/bench_${g}_$n.err
+  QAMPY_HIP_HOOK_BEFORE=$g QAMPY_POST_PARTS=$n timeout 300 python bench.py --full --bank 0 --no-cpu-baseline --no-extra-shapes --exact-steps 1 > $R/bench_${g}_$n.json 2> $R/bench_${g}_$n.err
   python - $g $n <<'PY'
 import json, sys
 g, n = sys.argv[1:3]

@@ -11,7 +11,7 @@ bash scripts/gpu_pmc.sh > $R/pmc.log 2>&1
 cp gpurun_out/pmc_traffic_c3.json gpurun_out/pmc_instr_c3.json gpurun_out/pmc_summary.txt gpurun_out/pmc_valu_summary.txt $R/ 2>/dev/null
 cp gpurun_out/pmc_traffic_c3.json gpurun_out/pmc_instr_c3.json profiles/ 2>/dev/null      # the bench line below quotes them (same kernel sources)
 rm -rf gpurun_out/pmc_FETCH_SIZE gpurun_out/pmc_WRITE_SIZE gpurun_out/pmcv_*
-timeout 1200 python bench.py > $R/bench_c3.json 2> $R/bench_c3.err; tail -2 $R/bench_c3.err
+timeout 1200 python bench.py --full > $R/bench_c3.json 2> $R/bench_c3.err; tail -2 $R/bench_c3.err
 python scripts/show_bench.py $R/bench_c3.json > $R/bench_c3.txt 2>&1
 ( cd /tmp; timeout 900 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/$R/kt -o c3 -- python $GRAFT_REPO_ROOT/bench.py --bank 0 --no-cpu-baseline --no-extra-shapes --exact-steps 0 --steps 5 > $GRAFT_REPO_ROOT/$R/kt_bench.json 2> $GRAFT_REPO_ROOT/$R/kt.log )
 DB=$(find $R/kt -name "*results.db" | head -1)
@@ -19,7 +19,7 @@ python scripts/rocpd_stats.py $DB > $R/c3_kernel_stats.txt
 python scripts/rocpd_timeline.py $DB > $R/c3_timeline.txt
 find $R/kt -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $R/c3_rocprofv3_kernel_stats.csv
 rm -rf $R/kt
-timeout 900 python bench.py --workload c5 --steps 3 > $R/bench_c5.json 2> $R/bench_c5.err
+timeout 900 python bench.py --full --workload c5 --steps 3 > $R/bench_c5.json 2> $R/bench_c5.err
 ( python scripts/threads_probe.py c3 100 1 2 3; python scripts/dual_probe.py 1 c3 200 | tail -1; python scripts/dual_probe.py 2 c3 200 | tail -1 ) > $R/in_flight.txt 2>&1
 FULL=1 timeout 900 python scripts/pit_methods.py > $R/pit_methods.txt 2>&1
 timeout 600 python scripts/pit_survey.py > $R/pit_survey_steps.txt 2>&1

@@ -103,6 +103,41 @@ def test_two_rank_line_under_torchrun_as_the_driver_starts_it(tmp_path):
     assert res["value"] == pytest.approx(2 * res["config"]["nsym_per_channel"] * 3 / (res["ms_per_step"] * 3e-3) / 1e6, rel=1e-3)
 
 
+def test_full_flag_is_accepted_and_leaves_the_contract_alone(tmp_path):
+    """`--full` (everything beyond the headline) is an option of every run; the dry run's line carries the contract's keys with or without it."""
+    env = dict(os.environ, OMP_NUM_THREADS="1")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    for extra in ([], ["--full"]):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dry-run", "--steps", "2", "--warmup", "1",
+                              "--detail-out", str(tmp_path / "detail.json")] + extra, capture_output=True, text=True, timeout=300, env=env)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        res = json.loads(lines[0])
+        assert all(k in res for k in CONTRACT) and res["steps"] == 2 and res["warmup"] == 1
+
+
+@pytest.mark.gpu
+def test_plain_run_certifies_its_headline_and_stops_there(tmp_path):
+    """A plain run on the GPU: the headline, certified against the exact path in the same run, and nothing that only `--full` measures."""
+    detail = str(tmp_path / "detail.json")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--nsym", str(2 ** 18), "--steps", "2", "--warmup", "1",
+                          "--detail-out", detail], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    assert all(k in res for k in CONTRACT) and res["value"] > 0 and res["ms_per_step"] > 0
+    checks = res["tier_b"]["checks"]
+    assert res["tier_b"]["certified"] == all(v for k, v in checks.items() if k != "tol") and "errors_within_3" in checks
+    assert res["headline_tier"] == ("b" if res["tier_b"]["certified"] else "a") and res["tier_a"]["steps"] == 2
+    full = json.load(open(detail))
+    for k in ("roofline", "cpu_baseline", "parity_vs_cpu", "tier_b_tight", "ns", "c2", "channel_bank", "one_capture_at_a_time"):
+        assert k not in full, k
+    assert "pass_ms_all_launches" not in full["tier_b"]["stages"][0]
+
+
 def test_dump_files_are_float_bounded_and_the_same_every_run(tmp_path):
     """`--dump-outputs`: what ResidentReceiver.fetch() returns at the C3 shape (2^22 symbols, two stages) becomes float32 / float64 files within
     64 MB; long arrays are kept at a seeded sample of positions that does not change from run to run."""
