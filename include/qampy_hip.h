@@ -278,20 +278,19 @@ int qh_set_gram_budget_gb(double gb);
 int qh_get_gram_budget_gb(double *gb);
 int qh_set_default_tier(int tier, double tol);
 int qh_get_default_tier(int *tier, double *tol);
-/* Test / measurement hooks (ABI 10; rounds 1-5 read environment variables in the launch paths): each forces a kernel form the automatic choice would
- * not take at that size, none selects a different algorithm, every one is exercised through this C ABI by the -m gpu tests named.  The launch paths read
- * ONE table of atomics; the environment variables of the same meaning (QAMPY_HIP_TRAINER, QAMPY_HIP_PIT_FORM, QAMPY_HIP_SEG_LANES, QAMPY_HIP_PIT_PROBE,
- * QAMPY_HIP_BPS, QAMPY_HIP_BPS_FUSED, QAMPY_HIP_PIT_XASIDE, QAMPY_HIP_LA_PROFILE) are read ONCE, when the library is loaded, as the table's initial values.
+/* Test hooks (ABI 10; rounds 1-5 read environment variables in the launch paths): each forces a kernel form the automatic choice would not take at
+ * that size, none selects a different algorithm, every one is exercised through this C ABI by the -m gpu tests named.  The launch paths read ONE table
+ * of atomics; the environment variables of the same meaning (QAMPY_HIP_TRAINER, QAMPY_HIP_PIT_FORM, QAMPY_HIP_SEG_LANES, QAMPY_HIP_PIT_PROBE,
+ * QAMPY_HIP_BPS) are read ONCE, when the library is loaded, as the table's initial values.
  *   key          values                                        what
  *   "trainer"    auto | direct | lookahead | iterative          form of the exact trainer, like qh_set_trainer (tests/test_gpu_parity.py)
  *   "pit_form"   auto | segment | block                         parallel in time: throughput / latency form of the passes (tests/test_gpu_pit.py)
  *   "seg_lanes"  0 | 8 | 16                                     throughput form: lanes per chain (tests/test_gpu_pit.py)
  *   "pit_probe"  0 | 1                                          complex64: the complex128 analysis of a pass (probe of the capture) (tests/test_gpu_pit.py)
- *   "bps"        auto | tile | lds | fused                      phase search: tile kernel for complex64 / streaming kernel with the LDS ring only (no
- *                                                               register-ring kernel) / search + unwrap + de-rotation in one kernel (tests/test_gpu_parity.py)
- *   "pit_xaside" 0 | 1                                          start taps into the eigenbasis beside the pass (measurement)
- *   "la_profile" 0 | 1                                          developer aid: cycle split of workgroup 0 of the block trainers on stderr
- * qh_set_form returns QH_ERR_ARG for an unknown key or value; a NULL or empty value resets the key to automatic. */
+ *   "bps"        auto | tile | lds                              phase search: tile kernel for complex64 / streaming kernel with the LDS ring only (no
+ *                                                               register-ring kernel) (tests/test_gpu_parity.py)
+ * qh_set_form returns QH_ERR_ARG for an unknown key or value; a NULL or empty value resets the key to automatic.  qh_get_form returns QH_ERR_ARG
+ * for an unknown key or a NULL value. */
 int qh_set_form(const char *key, const char *value);
 int qh_get_form(const char *key, int *value);
 

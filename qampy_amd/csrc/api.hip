@@ -125,13 +125,12 @@ thread_local unsigned g_scratch_epoch = 0;
 // ---- the table of form switches (common.h FormKey; qh_set_form / qh_set_trainer).  Values:
 //   trainer    0 automatic, 1 direct, 2 lookahead, 3 iterative          pit_form   0 automatic, 1 segment (throughput form), 2 block (latency forms)
 //   seg_lanes  0 automatic, 8, 16                                       pit_probe  1: complex64 takes the complex128 analysis of a pass
-//   bps        0 automatic, 1 tile kernel for complex64, 2 streaming kernel with the LDS ring only, 3 search + unwrap + de-rotation fused, 4 plain (round 5's rows)
-//   pit_xaside 1: start taps into the eigenbasis beside the pass         la_profile 1: cycle split of workgroup 0 of the block trainers
+//   bps        0 automatic, 1 tile kernel for complex64, 2 streaming kernel with the LDS ring only
 static std::atomic<int> g_form[FORM_COUNT];
 struct FormName { const char *key, *env; };
 static const FormName FORM_NAMES[FORM_COUNT] = {
     {"trainer", "QAMPY_HIP_TRAINER"}, {"pit_form", "QAMPY_HIP_PIT_FORM"}, {"seg_lanes", "QAMPY_HIP_SEG_LANES"}, {"pit_probe", "QAMPY_HIP_PIT_PROBE"},
-    {"bps", "QAMPY_HIP_BPS"}, {"pit_xaside", "QAMPY_HIP_PIT_XASIDE"}, {"la_profile", "QAMPY_HIP_LA_PROFILE"}};
+    {"bps", "QAMPY_HIP_BPS"}};
 static int form_parse(int k, const char *v, int *out)
 {
     if (!v || !v[0]) { *out = 0; return 0; }
@@ -139,19 +138,17 @@ static int form_parse(int k, const char *v, int *out)
     case FORM_TRAINER: *out = v[0] == 'd' ? 1 : (v[0] == 'l' ? 2 : (v[0] == 'i' ? 3 : (v[0] == 'a' || v[0] == '0' ? 0 : -1))); break;
     case FORM_PIT: *out = v[0] == 's' ? 1 : (v[0] == 'b' ? 2 : (v[0] == 'a' || v[0] == '0' ? 0 : -1)); break;
     case FORM_SEG_LANES: { const int n = atoi(v); *out = (n == 8 || n == 16 || n == 0) ? n : -1; break; }
-    case FORM_BPS: *out = v[0] == 't' ? 1 : (v[0] == 'l' ? 2 : (v[0] == 'f' ? 3 : (v[0] == 'p' ? 4 : (v[0] == 'a' || v[0] == '0' ? 0 : -1)))); break;
+    case FORM_BPS: *out = v[0] == 't' ? 1 : (v[0] == 'l' ? 2 : (v[0] == 'a' || v[0] == '0' ? 0 : -1)); break;
     default: *out = atoi(v) != 0 ? 1 : 0; break;
     }
     return *out < 0 ? -1 : 0;
 }
-// the environment, ONCE, when the library is loaded (QAMPY_HIP_BPS_FUSED=1 was round 3's spelling of bps = fused)
+// the environment, ONCE, when the library is loaded
 static const int g_form_env_read = [] {
     for (int k = 0; k < FORM_COUNT; k++) {
         int v = 0;
         if (form_parse(k, getenv(FORM_NAMES[k].env), &v) == 0) g_form[k].store(v);
     }
-    const char *f = getenv("QAMPY_HIP_BPS_FUSED");
-    if (f && f[0] == '1' && g_form[FORM_BPS].load() == 0) g_form[FORM_BPS].store(3);
     return 0;
 }();
 int form(FormKey k) { return g_form[k].load(std::memory_order_relaxed); }
@@ -285,6 +282,7 @@ int qh_set_form(const char *key, const char *value)
 }
 int qh_get_form(const char *key, int *value)
 {
+    if (!value) { qh::set_error("qh_get_form: value"); return QH_ERR_ARG; }
     for (int k = 0; key && k < qh::FORM_COUNT; k++)
         if (strcmp(key, qh::FORM_NAMES[k].key) == 0) { *value = qh::g_form[k].load(); return QH_OK; }
     qh::set_error("qh_get_form: unknown key");

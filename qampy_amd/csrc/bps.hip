@@ -285,13 +285,8 @@ struct BpsStreamArgs {
     int64_t L;
     int A, M, N, C, alpha_lds;
     int chunk0;                  // chunk of block 0 (a launch may cover a part of the chunks: bps_dev's part / nparts)
-    int fast_rows;               // 0: the generic rows only (qh_set_form("bps", "plain"): measurements)
     int reg_lo, reg_hi;          // chunks [reg_lo, reg_hi) belong to bps_stream40_kernel IF the alphabet turns out to be one it takes (bs40_takes: both kernels
                                  // read the device-side descriptor and exactly one of them works on such a chunk - the host never waits for the analysis)
-    // REC (search + np.unwrap + de-rotation in this one kernel): per-symbol phase and recovered symbols out, and the look-back cells
-    float *ph;                   // (nm, L)
-    Cx<float> *Eout;             // (nm, L)
-    unsigned long long *state;   // (nm, nchunk) zeroed before the launch: flag << 32 | value (1: the chunk's jump total, 2: inclusive prefix)
 };
 
 template <int K> struct BsKind { static constexpr int value = K; };
@@ -320,7 +315,6 @@ __device__ __forceinline__ int bs_argmin16(const float *tb, int sym, int quarter
     return best;
 }
 __device__ __forceinline__ bool bs40_takes(const AlphabetDesc<float> *d);
-template <typename R> __device__ __forceinline__ int unwrap_jump(const R *angles, int kprev, int kcur);
 typedef float bs_f2 __attribute__((ext_vector_type(2)));
 // both axes at once: u = (|t.re|, |t.im|), d_k = u - (l_re[k], l_im[k]) is ONE packed subtraction per level pair; the minima are
 // per axis (no packed min).  The same values as the scalar form: subtraction and |.| are exact per component.
@@ -345,11 +339,6 @@ template <bool SMALL> __device__ __forceinline__ bs_f2 bs_axes_sym(bs_f2 t, cons
     return m;
 }
 
-// REC: the host layer's np.unwrap and de-rotation (phaserecovery.py:155-158) in the same kernel.  The chunk keeps its indices in LDS,
-// sums its unwrap jumps, and gets the jumps of everything before it through a decoupled look-back over one 64-bit cell per chunk
-// (chunks are dispatched in order, so a predecessor is resident or done; a wave reads 64 cells at a time and stops at the first
-// that already carries an inclusive prefix) - then walks the chunk once more, coalesced: phase, rotator, recovered symbol.
-template <bool REC>
 __global__ void __launch_bounds__(64) bps_stream_kernel(BpsStreamArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) char bs_smem[];
@@ -358,24 +347,19 @@ __global__ void __launch_bounds__(64) bps_stream_kernel(BpsStreamArgs a)
     float *ring = reinterpret_cast<float *>(bs_smem);                 // [W][64]
     float *tb = ring + (size_t)W * 64;                                // [BS_G][BS_TP]
     float *plev = tb + BS_G * BS_TP + 1;                              // [2][BPS_MAX_LEVELS] levels of a product alphabet
-    unsigned char *cidx = reinterpret_cast<unsigned char *>(plev + 2 * BPS_MAX_LEVELS + 1);   // REC: [C + 1] index of output c0 - 1, then of the chunk
-    char *after_idx = reinterpret_cast<char *>(cidx) + (REC ? ((a.C + 1 + 15) & ~15) : 0);
-    // REC: [C] running unwrap correction of the chunk's symbols - in the ring's memory once the search is over (the search is bound by
-    // the waves a CU holds: 5 KiB more LDS per wave cost it a fifth of its speed), behind the indices when the ring is too small
-    int *ccorr = (REC && W * 64 < a.C) ? reinterpret_cast<int *>(after_idx) : reinterpret_cast<int *>(ring);
-    Cx<float> *alpha = reinterpret_cast<Cx<float> *>(after_idx + ((REC && W * 64 < a.C) ? (size_t)a.C * sizeof(int) : 0));   // [M] any other alphabet (if it fits)
+    Cx<float> *alpha = reinterpret_cast<Cx<float> *>(plev + 2 * BPS_MAX_LEVELS + 1);   // [M] any other alphabet (if it fits)
     const int64_t L = a.L;
     const Cx<float> *E = a.E + (size_t)blockIdx.y * L;
     int32_t *idx = a.idx + (size_t)blockIdx.y * L;
     const int64_t c0 = (int64_t)(blockIdx.x + a.chunk0) * a.C;
     const int64_t c1 = c0 + a.C < L ? c0 + a.C : L;                   // outputs [c0, c1)
-    const int ngroups = (a.C + W - 1 + (REC ? 1 : 0) + BS_G - 1) / BS_G;      // REC: one output more at the front (the jump into the chunk needs index c0 - 1)
+    const int ngroups = (a.C + W - 1 + BS_G - 1) / BS_G;
     const int64_t lstart = c0 + a.C - 1 + a.N - (int64_t)ngroups * BS_G + 1;   // first distance row; row l completes the window of output l - N
 
     // ---- alphabet
     const int product = a.desc->product, symmetric = a.desc->symmetric;
     const int nre = a.desc->nre, nim = a.desc->nim;
-    if (!REC && (int)(blockIdx.x + a.chunk0) >= a.reg_lo && (int)(blockIdx.x + a.chunk0) < a.reg_hi && bs40_takes(a.desc)) return;      // (wave-uniform; before any barrier)
+    if ((int)(blockIdx.x + a.chunk0) >= a.reg_lo && (int)(blockIdx.x + a.chunk0) < a.reg_hi && bs40_takes(a.desc)) return;      // (wave-uniform; before any barrier)
     bs_f2 lev2[16];                                                   // positive halves (re, im), in SGPRs
 #pragma unroll
     for (int k = 0; k < 16; k++) {
@@ -465,7 +449,7 @@ __global__ void __launch_bounds__(64) bps_stream_kernel(BpsStreamArgs a)
         // cells and the transposed block are addressed with immediate offsets from one base register per group, and there is no bias select:
         // 17 vector instructions per row (rotation 2, |t| 2, level differences 4, minima 4, squared distance 3, window 2) against 22.
         // The same arithmetic in the same order: bit-identical distances, sums and indices.
-        if (kind == 3 && full && a.fast_rows && lg >= 0 && lg + BS_G <= L && slot + BS_G <= W) {         // wave-uniform
+        if (kind == 3 && full && lg >= 0 && lg + BS_G <= L && slot + BS_G <= W) {         // wave-uniform
             typedef const __attribute__((address_space(4))) bs_f2 *bs_cptr;
             const bs_cptr eg = (bs_cptr)(const void *)(E + lg);                          // (read-only for the whole launch: constant address space)
             bs_f2 xs[BS_G];
@@ -492,7 +476,6 @@ __global__ void __launch_bounds__(64) bps_stream_kernel(BpsStreamArgs a)
         const int64_t i = lg + sym - a.N;
         const int bo = (i >= a.N && i < L - a.N) ? best : 0;
         if (quarter == 0 && i >= c0 && i < c1) idx[i] = bo;
-        if (REC && quarter == 0 && i >= c0 - 1 && i < c1) cidx[i - c0 + 1] = (unsigned char)bo;
         __syncthreads();
     }
     };
@@ -500,71 +483,6 @@ __global__ void __launch_bounds__(64) bps_stream_kernel(BpsStreamArgs a)
     else if (symmetric) run(BsKind<0>{});
     else if (product) run(BsKind<1>{});
     else run(BsKind<2>{});
-    if (!REC) return;
-    __syncthreads();                                                    // the ring is free now
-    // ---- np.unwrap of 4 * ph over the interior [N, L - N): the correction is an integer number of quarter turns, a prefix sum of jumps
-    const int per = (a.C + 63) / 64;                                    // consecutive symbols per lane
-    int local = 0;
-    for (int r = 0; r < per; r++) {
-        const int e = lane * per + r;
-        const int64_t i = c0 + e;
-        int j = 0;
-        if (e < a.C && i < c1 && i > a.N && i < L - a.N) j = unwrap_jump<float>(a.angles, cidx[e], cidx[e + 1]);
-        local += j;
-        if (e < a.C) ccorr[e] = local;                                  // inclusive within the lane
-    }
-    int incl = local;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    const int total = __shfl(incl, 63);
-    const int lane_off = incl - local;
-    // ---- jumps of the chunks before this one
-    unsigned long long *cell = a.state + (size_t)blockIdx.y * gridDim.x;
-    const int c = blockIdx.x;
-    int before = 0;
-    if (c > 0) {
-        if (lane == 0) __hip_atomic_store(cell + c, (1ull << 32) | (unsigned)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int base = c - 1;
-        for (;;) {
-            const int k = base - lane;
-            unsigned long long v = 2ull << 32;                          // before chunk 0: an inclusive prefix of 0
-            if (k >= 0) v = __hip_atomic_load(cell + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned flag = (unsigned)(v >> 32);
-            if (__ballot(flag == 0) != 0) { __builtin_amdgcn_s_sleep(2); continue; }      // a predecessor has not published yet
-            const unsigned long long m2 = __ballot(flag == 2);
-            const int val = (int)(unsigned)v;
-            const int first2 = m2 ? __builtin_ctzll(m2) : 64;           // nearest cell with an inclusive prefix
-            int part = lane <= first2 ? val : 0;
-            for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
-            before += part;
-            if (m2) break;
-            base -= 64;
-        }
-    }
-    if (lane == 0) __hip_atomic_store(cell + c, (2ull << 32) | (unsigned)(before + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (int r = 0; r < per; r++) {
-        const int e = lane * per + r;
-        if (e < a.C) ccorr[e] += before + lane_off;
-    }
-    __syncthreads();
-    // ---- phase and de-rotation, consecutive symbols per lane
-    float *ph = a.ph + (size_t)blockIdx.y * L;
-    Cx<float> *out = a.Eout + (size_t)blockIdx.y * L;
-    const float pi = 3.14159265358979323846f;
-    for (int e = lane; e < a.C; e += 64) {
-        const int64_t i = c0 + e;
-        if (i >= c1) break;
-        const bool interior = (i >= a.N && i < L - a.N);
-        float p = a.angles[cidx[e + 1]];                                // edges keep the raw grid value of idx = 0 (phaserecovery.py:155 unwraps the interior only)
-        if (interior) p += (pi / 2) * (float)ccorr[e];
-        ph[i] = p;
-        float sn, cs;
-        sincos_<float>(p, &sn, &cs);
-        const Cx<float> x = ldg(E + i);
-        stg(out + i, Cx<float>{fma_(x.re, cs, -(x.im * sn)), fma_(x.re, sn, x.im * cs)});
-    }
 }
 
 // ---- Register-ring form of the streaming search (round 6) for the shape the path's own callers run at full size: A = 64 test angles (no idle lane),
@@ -659,7 +577,7 @@ template <typename R> static int bps_tile(int A, int N, size_t *lds)
     return (int)T;
 }
 
-// qh_set_form("bps", ...): 0 automatic, 1 tile kernel for complex64 too, 2 streaming kernel with the LDS ring only (no register-ring kernel), 3 fused
+// qh_set_form("bps", ...): 0 automatic, 1 tile kernel for complex64 too, 2 streaming kernel with the LDS ring only (no register-ring kernel)
 inline bool bps_reg_ring() { return form(FORM_BPS) == 0; }
 template <typename R> inline bool bps_stream_ok(int64_t, int, int, int) { return false; }
 template <> inline bool bps_stream_ok<float>(int64_t p, int A, int N, int M)
@@ -671,12 +589,11 @@ template <> inline bool bps_stream_ok<float>(int64_t p, int A, int N, int M)
 // nm rows of length L (consecutive in memory) against one angle grid; idx likewise
 template <typename R>
 int bps_dev(const void *E, int64_t L, const void *angles, int64_t p, int A, const void *symbols, int M, int N, int32_t *idx, int nm = 1,
-            void *ph = nullptr, void *Eout = nullptr, bool *recovered = nullptr, int part = 0, int nparts = 1)
+            int part = 0, int nparts = 1)
 {
     // part / nparts (streaming kernel only): this call searches the part-th of nparts runs of chunks - a caller that wants the search in
     // pieces (between the relaxation passes of the next capture's training, pipeline.py) makes nparts calls, each complete in itself (its own
     // alphabet analysis: the parts share no state).  Other kernels: part nparts - 1 does it all.
-    if (recovered) *recovered = false;
     int rc = ensure_init();
     if (rc) return rc;
     QH_REQUIRE(L >= 0 && A >= 1 && M >= 1 && N >= 1 && nm >= 1, "bps: bad sizes");
@@ -705,34 +622,19 @@ int bps_dev(const void *E, int64_t L, const void *angles, int64_t p, int A, cons
         int C = 1024;                                            // longer chunks: less halo (2N - 1 rows each); shorter: more waves
         while (C > 128 && ((L + C - 1) / C) * nm < 4096) C /= 2;
         s.C = C;
-        // search + unwrap + de-rotation in ONE kernel (qh_set_form("bps", "fused")).  Opt-in: measured at C3 it is slower than the search
-        // followed by the three small unwrap / de-rotation launches (0.80 against 0.70 ms) - the tail of a chunk (jump scan, look-back,
-        // sincos, second pass over the symbols) is a latency chain inside a kernel whose speed is the number of waves a CU holds.
-        const int fused = form(FORM_BPS) == 3 ? 1 : 0;
-        const bool rec = fused && ph != nullptr && Eout != nullptr && A <= 255 && nparts == 1;
         const unsigned nchunk = (unsigned)((L + C - 1) / C);
         const unsigned ch0 = (unsigned)((uint64_t)nchunk * part / nparts), ch1 = (unsigned)((uint64_t)nchunk * (part + 1) / nparts);
         s.chunk0 = (int)ch0;
-        s.ph = (float *)ph; s.Eout = (Cx<float> *)Eout; s.state = nullptr;
-        if (rec) {
-            void *st = nullptr;
-            if ((rc = scratch(12, (size_t)nm * nchunk * sizeof(unsigned long long), &st))) return rc;
-            QH_HIP(hipMemsetAsync(st, 0, (size_t)nm * nchunk * sizeof(unsigned long long), g_stream));
-            s.state = (unsigned long long *)st;
-        }
-        const size_t lds = ((size_t)2 * N * 64 + BS_G * BS_TP + 1 + 2 * BPS_MAX_LEVELS + 1) * sizeof(float) + (rec ? (2 * N * 64 < C ? (size_t)C * sizeof(int) : 0) + (((size_t)C + 1 + 15) & ~(size_t)15) : 0) +
-                           (s.alpha_lds ? (size_t)M * sizeof(Cx<float>) : 0) + 16;
+        const size_t lds = ((size_t)2 * N * 64 + BS_G * BS_TP + 1 + 2 * BPS_MAX_LEVELS + 1) * sizeof(float) + (s.alpha_lds ? (size_t)M * sizeof(Cx<float>) : 0) + 16;
         static std::atomic<bool> sattr{false};
         if (!sattr) {
-            QH_HIP(hipFuncSetAttribute((const void *)bps_stream_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-            QH_HIP(hipFuncSetAttribute((const void *)bps_stream_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+            QH_HIP(hipFuncSetAttribute((const void *)bps_stream_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
             sattr = true;
         }
         // chunks of the register-ring kernel (A = 64, N = 20, every row of the chunk inside the capture): [lo, hi) of this part
         s.reg_lo = s.reg_hi = 0;
-        s.fast_rows = form(FORM_BPS) == 4 ? 0 : 1;
         int64_t lo = 0, hi = 0;
-        if (!rec && A == 64 && N == 20 && C > 128) {
+        if (A == 64 && N == 20 && C > 128) {
             const int ngroups = (C + 2 * N - 1 + BS_G - 1) / BS_G;
             const int64_t back = (int64_t)ngroups * BS_G - (C - 1 + N + 1);            // lstart = c0 - back >= 0
             lo = back > 0 ? (back + C - 1) / C : 0;
@@ -741,8 +643,7 @@ int bps_dev(const void *E, int64_t L, const void *angles, int64_t p, int A, cons
             if (hi > (int64_t)ch1) hi = ch1;
             if (hi <= lo) lo = hi = 0;
         }
-        if (rec) hipLaunchKernelGGL(bps_stream_kernel<true>, dim3(nchunk, nm), dim3(64), lds, g_stream, s);
-        else if (ch1 > ch0 && hi > lo) {
+        if (ch1 > ch0 && hi > lo) {
             // The chunks in front of and behind that range hold rows outside the capture and take the generic rows: ONE wave per chunk of 1024 symbols would
             // be a lone, latency-bound wave of ~0.1 ms behind a search of 0.36 ms - they are searched in pieces of 128 symbols instead (8 waves side by
             // side; whatever the form, so that the forms stay bit-identical).  The range itself goes to BOTH kernels: each looks at the device-side
@@ -754,7 +655,7 @@ int bps_dev(const void *E, int64_t L, const void *angles, int64_t p, int A, cons
                 e.chunk0 = (int)(c_from * (C / 128));
                 const int64_t end = c_to * C < L ? c_to * C : L;
                 const unsigned n = (unsigned)((end - c_from * C + 127) / 128);
-                hipLaunchKernelGGL(bps_stream_kernel<false>, dim3(n, nm), dim3(64), lds, g_stream, e);
+                hipLaunchKernelGGL(bps_stream_kernel, dim3(n, nm), dim3(64), lds, g_stream, e);
             };
             edge(ch0, lo);
             edge(hi, ch1);
@@ -764,10 +665,9 @@ int bps_dev(const void *E, int64_t L, const void *angles, int64_t p, int A, cons
                 r.reg_lo = (int)lo; r.reg_hi = (int)hi;
                 hipLaunchKernelGGL(bps_stream40_kernel, dim3((unsigned)(hi - lo), nm), dim3(64), 0, g_stream, r);
             }
-            hipLaunchKernelGGL(bps_stream_kernel<false>, dim3((unsigned)(hi - lo), nm), dim3(64), lds, g_stream, r);
+            hipLaunchKernelGGL(bps_stream_kernel, dim3((unsigned)(hi - lo), nm), dim3(64), lds, g_stream, r);
         } else if (ch1 > ch0)
-            hipLaunchKernelGGL(bps_stream_kernel<false>, dim3(ch1 - ch0, nm), dim3(64), lds, g_stream, s);
-        if (recovered) *recovered = rec;
+            hipLaunchKernelGGL(bps_stream_kernel, dim3(ch1 - ch0, nm), dim3(64), lds, g_stream, s);
         QH_HIP(hipGetLastError());
         return QH_OK;
     }
@@ -980,9 +880,7 @@ int bps_recover_dev(const void *E, int nm, int64_t L, const void *angles, int A,
         dang = (char *)ring + (size_t)(grid_next++ % BPS_DESC_RING) * one;
         hipLaunchKernelGGL((linspace_kernel<R>), dim3((A + 63) / 64), dim3(64), 0, g_stream, (R *)dang, A);
     }
-    bool recovered = false;
-    if ((rc = bps_dev<R>(E, L, dang, 1, A, symbols, M, N, idx, nm, ph, Eout, &recovered, part, nparts))) return rc;
-    if (recovered) return QH_OK;                                   // the streaming kernel unwrapped and de-rotated as well
+    if ((rc = bps_dev<R>(E, L, dang, 1, A, symbols, M, N, idx, nm, part, nparts))) return rc;
     if (part != nparts - 1) return QH_OK;
     hipLaunchKernelGGL((unwrap_partial_kernel<R>), dim3((unsigned)nchunk, nm), dim3(UW_THREADS), 0, g_stream, idx, L, N, (const R *)dang,
                        (int *)dchunk, nchunk);

@@ -319,7 +319,6 @@ __global__ void __launch_bounds__(BI_NT) train_bi_kernel(LaArgs<R> a)
     // own tap slice in registers: group rr of round t <-> tap f0 + BI_RPW * t + rr (BI_MAXTAPS / 64 = 2 rounds at most)
     Cx<R> wreg[2] = {Cx<R>{0, 0}, Cx<R>{0, 0}};
     R r_blk = ADAPT ? (R)1 / K.mu : (R)0;                              // adaptive step: r = 1/mu at the start of the block, carried from sweep to sweep
-    unsigned long long pf_sweeps = 0, pf_t_sweep = 0, pf_t_upd = 0, pf_t_prior = 0;
     // The reference's Niter loop (pythran_equalisation.py:163-165) INSIDE the launch: taps and step size stay in registers / LDS from sweep
     // to sweep; what a sweep needs from scratch is its first two sample windows, the prior outputs of block 0 and the Gram rows of block 0
     // (the pilot stages of config 5 are 30 sweeps of 1024 steps: a launch per sweep was a third of their time).
@@ -352,7 +351,6 @@ __global__ void __launch_bounds__(BI_NT) train_bi_kernel(LaArgs<R> a)
     const int csrc = cl * BI_W * 4;                                     // ds_bpermute byte address of that row's group
 
     for (int k = 0; k < nblk; k++) {
-        const unsigned long long pt0 = a.prof ? clock64() : 0;
         const int64_t s0 = (int64_t)k * LA_B;
         Cx<R> sdat{0, 0};                                              // data-aided: the training symbol of this group's step
         if constexpr (METHOD == QH_M_SBD_DATA) {
@@ -378,7 +376,6 @@ __global__ void __launch_bounds__(BI_NT) train_bi_kernel(LaArgs<R> a)
             const BiEnt<R> got = pr[pb];
             y = got.v;
             group_csum(y.re, y.im);                                        // y of row rr, identical in the lanes of the group
-            if (a.prof) pf_sweeps++;
             Cx<R> c_new;
             if constexpr (ADAPT) {
                 const BiAd<R> ax = adx[(pb ? BI_W : 0) + cl];               // lane <-> wave (lane & 7): totals of the last sweep
@@ -431,7 +428,6 @@ __global__ void __launch_bounds__(BI_NT) train_bi_kernel(LaArgs<R> a)
             if (sweep(PBUF)) break;
         }
         // ---------------------------------------------------------------- results of the block
-        const unsigned long long pt1 = a.prof ? clock64() : 0;
         const Cx<R> e = errf(y, sdat, BiPlain{});
         if (vv == 0 && s0 + BI_JW * w + rr < TrSyms) eown[s0] = e;
         // taps: this wave's steps into all taps (lane <-> taps lane, lane + 64).  Steps past TrSyms (partial last block) have
@@ -468,20 +464,12 @@ __global__ void __launch_bounds__(BI_NT) train_bi_kernel(LaArgs<R> a)
         // samples of block k+2 replace block k's: every wave finished reading those before the barrier above, and the next
         // readers (prior outputs of block k+2) sit behind the sweep barriers of block k+1
         if (k + 2 < nblk) stage_store(k + 2);
-        const unsigned long long pt2c = a.prof ? clock64() : 0;
         if (k + 1 < nblk) qpart = prior_part(k + 1);                      // reads the own slice of wbuf only: no barrier needed
 #pragma unroll
         for (int r = 0; r < BI_JW; r++) g[r] = gok[r] ? gn[r] : Cx<R>{0, 0};
-        if (a.prof) {
-            const unsigned long long pt3 = clock64();
-            pf_t_sweep += pt1 - pt0; pf_t_upd += pt2c - pt1; pf_t_prior += pt3 - pt2c;
-        }
     }
     }   // sweeps
     __syncthreads();
-    if (a.prof && blockIdx.x == 0 && threadIdx.x == 0) {
-        a.prof[0] = pf_sweeps; a.prof[1] = pf_t_sweep; a.prof[2] = pf_t_upd; a.prof[3] = pf_t_prior; a.prof[4] = (unsigned long long)nblk;
-    }
     for (int f = threadIdx.x; f < ntot; f += BI_NT) wrow[f] = wbuf[f];
     if constexpr (ADAPT) if (threadIdx.x == 0) a.mu_out[ch * a.mu_cs + (int64_t)blockIdx.x * a.mu_ms] = (R)1 / r_blk;
 }

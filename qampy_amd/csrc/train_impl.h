@@ -670,12 +670,6 @@ int train_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Niter, i
             la.nch = nch; la.E_cs = Ecs; la.wx_cs = (int64_t)nmodes * ntot; la.err_cs = (int64_t)nmodes * TrSyms * Niter; la.mu_cs = 1;
             la.dd_general = f.dd_general;
             f.alphabet(la);
-            if (form(FORM_LA_PROFILE)) {                         // developer aid: cycle split of workgroup 0 (qh_set_form("la_profile", "1"))
-                void *pp = nullptr;
-                if ((rc = scratch(5, 16 * sizeof(unsigned long long), &pp))) return rc;
-                QH_HIP(hipMemsetAsync(pp, 0, 16 * sizeof(unsigned long long), g_stream));
-                la.prof = (unsigned long long *)pp;
-            }
             // adaptive = 1: mu is carried from sweep to sweep and from mode to mode -> one mode after the other;
             // adaptive = 2: every mode owns a step size (scratch array, seeded with mu) -> all modes concurrently
             R *mu_modes = nullptr;
@@ -719,19 +713,6 @@ int train_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Niter, i
             }
             if (mu_modes)        // mu out = the last selected mode's, per channel
                 hipLaunchKernelGGL((gather_kernel<R>), dim3((unsigned)((nch + 63) / 64)), dim3(64), 0, g_stream, (R *)mu_dev, (const R *)mu_modes, nsel, nch);
-            if (la.prof) {
-                unsigned long long hp[16];
-                QH_HIP(hipMemcpyAsync(hp, la.prof, sizeof(hp), hipMemcpyDeviceToHost, g_stream));
-                QH_HIP(hipStreamSynchronize(g_stream));
-                if (use_bi) {
-                    fprintf(stderr, "[bi profile] method %d blocks %llu: sweeps/block %.2f, cycles/block sweeps %.0f update %.0f prior %.0f\n", method, hp[4],
-                            (double)hp[0] / (double)hp[4], (double)hp[1] / (double)hp[4], (double)hp[2] / (double)hp[4], (double)hp[3] / (double)hp[4]);
-                } else {
-                    fprintf(stderr, "[la profile] method %d TrSyms %lld: chain work %llu wait %llu |", method, (long long)TrSyms, hp[0], hp[1]);
-                    for (int h = 1; h <= LA_NH; h++) fprintf(stderr, " helper%d update %llu prior %llu wait %llu |", h, hp[4 * h], hp[4 * h + 1], hp[4 * h + 2]);
-                    fprintf(stderr, "\n");
-                }
-            }
             return QH_OK;
         }
         QH_REQUIRE(!chan_stride && !row_pitch, "train_equaliser: strided channels need a block form of the trainer");

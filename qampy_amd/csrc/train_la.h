@@ -259,7 +259,6 @@ template <typename R> struct LaArgs {
     // channel batch: blockIdx.y = channel; element strides between the channels' arrays (0 for a single capture)
     int64_t E_cs, wx_cs, err_cs, G_cs, mu_cs, mu_ms;     // mu_ms: stride between the step sizes of the selected modes (0: one mu)
     int64_t modes[16];
-    unsigned long long *prof;   // optional [4 waves][4] cycle counters of workgroup 0 (qh_la_profile), else nullptr
     // segments of ONE sweep as the channels of a batch (parallel-in-time training, train_pit.h): seg != 0 -> channel c
     // trains the steps [c TrSyms + 64 min(c, seg_extra), ...) of the capture at E: TrSyms steps, one block more for the first
     // seg_extra segments, seg_tail (< 64) more for the last one; E, err and G are the whole sweep's arrays, wx per segment
@@ -411,7 +410,6 @@ __global__ void __launch_bounds__(64 * (1 + LA_NH)) train_la_kernel(LaArgs<R> a)
                 yn.im = fma_(cr, g.next.im, fma_(ci, g.next.re, yn.im));
             }
         };
-        unsigned long long t_wait = 0, t_work = 0, t_mark = __builtin_readcyclecounter();
         for (int it = 0; it < nsweep; it++) {
         Cx<R> *errow = aerr + (size_t)mode * a.err_pitch + a.err_off + (int64_t)it * TrSyms;
         Cx<R> ynext{0, 0};
@@ -454,13 +452,10 @@ __global__ void __launch_bounds__(64 * (1 + LA_NH)) train_la_kernel(LaArgs<R> a)
             if (lane >= nvalid) c = Cx<R>{0, 0};
             if (lane < nvalid) stg(errow + s0 + lane, e);
             lds.cbuf[k & 1][lane] = c;
-            if (a.prof) { const unsigned long long t = __builtin_readcyclecounter(); t_work += t - t_mark; t_mark = t; }
             __syncthreads();                                           // barrier k+1
-            if (a.prof) { const unsigned long long t = __builtin_readcyclecounter(); t_wait += t - t_mark; t_mark = t; }
         }
         }   // sweeps
         if constexpr (ADAPT) if (lane == 0) a.mu_out[ch * a.mu_cs + (int64_t)blockIdx.x * a.mu_ms] = mu_ad;
-        if (a.prof && blockIdx.x == 0 && lane == 0) { a.prof[0] = t_work; a.prof[1] = t_wait; }
         return;
     }
 
@@ -561,7 +556,6 @@ __global__ void __launch_bounds__(64 * (1 + LA_NH)) train_la_kernel(LaArgs<R> a)
         lds.qbuf[h][kb & 1][lane] = live ? acc : Cx<R>{0, 0};
     };
 
-    unsigned long long t_wait = 0, t_upd = 0, t_pri = 0, t_mark = __builtin_readcyclecounter();
     for (int it = 0; it < nsweep; it++) {
     stage_load(sp, 0);
     stage_store(sp, win_p);
@@ -572,18 +566,14 @@ __global__ void __launch_bounds__(64 * (1 + LA_NH)) train_la_kernel(LaArgs<R> a)
         if (k >= 1) stage_load(su, k - 1);                             // both windows' loads go out first ...
         if (k + 1 < nblk) stage_load(sp, k + 1);
         if (k >= 1) { stage_store(su, win_u); update(k - 1); }         // ... -> W_k
-        if (a.prof) { const unsigned long long t = __builtin_readcyclecounter(); t_upd += t - t_mark; t_mark = t; }
         if (k + 1 < nblk) { stage_store(sp, win_p); prior(k + 1); }    // Q_{k+1} = W_k . x
-        if (a.prof) { const unsigned long long t = __builtin_readcyclecounter(); t_pri += t - t_mark; t_mark = t; }
 #endif
         __syncthreads();                                               // barrier k+1
-        if (a.prof) { const unsigned long long t = __builtin_readcyclecounter(); t_wait += t - t_mark; t_mark = t; }
     }
     stage_load(su, nblk - 1);
     stage_store(su, win_u);
     update(nblk - 1);                                                  // taps at the end of the sweep
     }   // sweeps
-    if (a.prof && blockIdx.x == 0 && lane == 0) { a.prof[4 * wave] = t_upd; a.prof[4 * wave + 1] = t_pri; a.prof[4 * wave + 2] = t_wait; }
     if (own) stg(wrow + fl, w);
 }
 

@@ -2537,12 +2537,12 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
     // keeps the probe-based analysis, whose defect vectors are formed in double precision before they are projected
     // (qh_set_form("pit_probe", "1") forces it for complex64 too: tests compare the two)
     const bool eig = want_corr && sizeof(R) == 4 && form(FORM_PIT_PROBE) == 0;
-    const bool eig_path = eig && !(o.exchange != nullptr);        // (a capture split over processes keeps everything on one stream)
-    // Measured coarse model (pit_model_kernel): gain and the 2 x 2 block of the signal direction from the capture itself.  opts.correction = 2
-    // keeps round 3's model (one formula gain per error function, diagonal in the eigenbasis, extra damping beta) for comparisons.
+    // Measured coarse model (pit_model_kernel): gain and the 2 x 2 block of the signal direction from the capture itself.  complex128, cma2 and
+    // decision methods whose passes run in neither the segment nor the block-iterative form keep round 3's model (one formula gain per error
+    // function, diagonal in the eigenbasis, extra damping beta).
     const bool tables_ok = method == QH_M_CMA || method == QH_M_SGNCMA || method == QH_M_MCMA || method == QH_M_RDE || method == QH_M_MRDE ||
                            (decision && (use_bi || seg_form));
-    const bool ssb = eig && o.correction != 2 && tables_ok && method != QH_M_CMA2;
+    const bool ssb = eig && tables_ok && method != QH_M_CMA2;
     PitModel *model = nullptr;
     float4 *ualpha = nullptr;
     float2 *uqv = nullptr;
@@ -2697,22 +2697,6 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
                 QH_HIP(hipMemcpyAsync(X + wset, Y, (size_t)(sg.S - 1) * wbytes, hipMemcpyDeviceToDevice, g_stream));   // X[s] = end taps of s-1
                 QH_HIP(hipMemcpyAsync(Y, X, (size_t)sg.S * wbytes, hipMemcpyDeviceToDevice, g_stream));
             }                                                       // (pass 0: pit_seed_kernel wrote the start taps into X and Y)
-            // The start taps of this pass go into the eigenbasis BESIDE the pass (helper stream): they are final once the back product (or the seed
-            // kernel) has run, the product is 8-10 us on a chip the pass leaves half empty, and the analysis only needs it after the pass.
-            static thread_local hipEvent_t ev_x = nullptr, ev_xe = nullptr;
-            // (measured, C3 tol 1e-4, same box, alternating: 1021-1023 MSym/s with the product aside, 1029-1031 with it in line - the two cross-stream
-            // event waits per pass cost what the 8 us product costs.  Off; qh_set_form("pit_xaside", "1") switches it on for measurements.)
-            const bool x_aside = eig_path && form(FORM_PIT_XASIDE) != 0;
-            if (x_aside) {
-                if (!ev_x) { QH_HIP(hipEventCreateWithFlags(&ev_x, hipEventDisableTiming)); QH_HIP(hipEventCreateWithFlags(&ev_xe, hipEventDisableTiming)); }
-                hipStream_t hs = helper_stream();
-                QH_HIP(hipEventRecord(ev_x, g_stream));
-                QH_HIP(hipStreamWaitEvent(hs, ev_x, 0));
-                if (o.basis && pit_basis_sync().pending) QH_HIP(hipStreamWaitEvent(hs, pit_basis_sync().out, 0));      // (a basis still being built on the other stream)
-                hipLaunchKernelGGL((pit_basis_mfma_kernel<R, 0>), dim3((ncol + PIT_MC - 1) / PIT_MC), dim3(pit_mfma_threads(ntot)), pit_mfma_lds(ntot), hs, Vb, (const Cx<R> *)X, (const Zf *)nullptr, Xe,
-                                   ntot, ncol, (const PitCtrl *)ctrl, fz);
-                QH_HIP(hipEventRecord(ev_xe, hs));
-            }
             if (o.on_pass) {
                 // the caller's chip-wide work for other streams, to run BESIDE this pass's trainer: an event recorded here is behind everything of the
                 // pass before (its back product), so what is gated on it starts with the trainer - not in the analysis behind it, where it would share
@@ -2767,9 +2751,6 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
                     QH_HIP(hipStreamWaitEvent(g_stream, pit_basis_sync().out, 0));
                     pit_basis_sync().pending = false;
                 }
-                auto forward = [&](const Cx<R> *src, Zf *dst) {      // dst = V^H src
-                    hipLaunchKernelGGL((pit_basis_mfma_kernel<R, 0>), dim3((ncol + PIT_MC - 1) / PIT_MC), dim3(pit_mfma_threads(ntot)), pit_mfma_lds(ntot), g_stream, Vb, src, (const Zf *)nullptr, dst, ntot, ncol, (const PitCtrl *)ctrl, fz);
-                };
                 auto forward2 = [&](const Cx<R> *src, Zf *dst, const Cx<R> *src2, Zf *dst2) {      // both products in ONE launch (a launch is ~4.5 us whatever it does)
                     PitFuse<R> f2 = fz;
                     f2.T2 = src2; f2.Out2 = reinterpret_cast<float2 *>(dst2);
@@ -2782,8 +2763,7 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
                 // times the correction - ~1e-6 per boundary, the same sign from boundary to boundary - and a fixed point of the TRACKED copy
                 // leaves exactly that as a true defect at every boundary; the weakly excited directions (coefficient ~1) add them up over the
                 // whole sweep: 1.0-1.7e-3 of tap deviation at C3 whatever the tolerance, invisible to the estimate (profiles/r05_tap_floor.txt).
-                if (x_aside) { QH_HIP(hipStreamWaitEvent(g_stream, ev_xe, 0)); forward((const Cx<R> *)Y, Ye); }       // (the product of X ran beside the pass: see above)
-                else forward2((const Cx<R> *)X, Xe, (const Cx<R> *)Y, Ye);
+                forward2((const Cx<R> *)X, Xe, (const Cx<R> *)Y, Ye);
                 hipLaunchKernelGGL(pit_bound_kernel, dim3((nbnd + nsel + 3) / 4), dim3(256), 0, g_stream, (const Zf *)Xe, (const Zf *)Ye, (const Zf *)Yprev, lam, ntot, sg.S, nsel, sym,
                                    (const PitCtrl *)ctrl, dfc, pw, gph, ualpha);
                 hipLaunchKernelGGL((pit_gauge_kernel<R>), dim3(ssb ? 2 : 1), dim3(PIT_GT_THREADS), 0, g_stream, (const double *)gph, sg.S, nsel, ctrl, theta, (const double *)pw,

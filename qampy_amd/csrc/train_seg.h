@@ -360,9 +360,7 @@ __global__ void __launch_bounds__(64) train_seg_kernel(SegArgs<R> a)
     // of the same CU stay empty - each of the pair then issues every other turn (measured: 783 instead of 553 cycles per step).
     // Naming the last VGPR and one AGPR as clobbered pushes the allocation past half the register file, so that a second wave
     // never fits (any layout, any precision; with more chains than SIMDs the waves queue up and still run alone).
-#ifndef QH_SEG_DUAL                                             // (build switch for measurements: two waves may share a SIMD)
     asm volatile("" ::: "v255", "a0");                          // allocation = 256 VGPRs + the first AGPR granule > half the file
-#endif
     // What CAN share the SIMD is a narrow streaming kernel of another stream (the phase search of the previous capture, 64 registers a
     // wave: pipeline.py run(overlap=True)); this wave is the latency-bound one, so it goes first whenever both have an instruction ready.
     __builtin_amdgcn_s_setprio(3);

@@ -4,7 +4,7 @@ import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np
 from qampy_amd import _lib
-if os.environ.get("QAMPY_LIB"):                  # (measurements: another build of the library, e.g. -DQH_SEG_DUAL)
+if os.environ.get("QAMPY_LIB"):                  # (measurements: another build of the library)
     _lib.LIB_PATH = os.environ["QAMPY_LIB"]
 import bench
 key, tol = sys.argv[1], float(sys.argv[2])

@@ -59,6 +59,11 @@ def test_unknown_method_is_a_value_error_before_touching_the_device():
                           np.ones((1, 1), np.complex64), "cma")
 
 
+def test_get_form_refuses_a_null_value():
+    """qh_get_form with no place to put the value is an argument error, not a crash (no device needed: the form table is host memory)."""
+    assert _lib.load().qh_get_form(b"bps", None) == _lib.QH_ERR_ARG
+
+
 def test_header_is_plain_c(tmp_path):
     """include/qampy_hip.h is a C header (extern "C" only under __cplusplus): a C99 and a C++11 translation unit that include
     it compile, and a C program can link against the library by name."""

@@ -557,21 +557,47 @@ def test_window_batch_equals_one_call_per_window(nwin, hop, method, adaptive, dn
         np.testing.assert_allclose(wbest[m], wx[best[m]], **t)
 
 
-def test_fused_search_unwrap_derotation_equals_separate_kernels(forms):
-    """QAMPY_HIP_BPS_FUSED=1: search, np.unwrap (decoupled look-back over the chunks) and de-rotation in ONE kernel - same index, phase
-    and recovered symbols as the search followed by the three unwrap / de-rotation launches, on a capture with real phase wander
-    (the unwrapped phase leaves the grid's range many times) and at a length that is not a multiple of the chunk."""
+def _unwrap_quarter_turns(angles, idx, N):
+    """Host restatement of the unwrap in qh_bps_recover_*_dev (include/qampy_hip.h): np.unwrap of 4 * angles[idx] over the interior [N, L - N),
+    its jump decisions made with numpy's own operations in the precision of the grid, half-range case included.  Returns the running
+    correction of every interior symbol as an integer number of whole turns of 4 * ph, i.e. of quarter turns of ph."""
+    rt = angles.dtype.type
+    pi, twopi = rt(np.pi), rt(2 * np.pi)
+    p4 = rt(4) * angles[idx[N:idx.size - N]]
+    dd = np.diff(p4)
+    ddmod = np.mod(dd + pi, twopi) - pi
+    ddmod[(ddmod == -pi) & (dd > 0)] = pi
+    corr = np.where(np.abs(dd) < pi, 0, np.rint((ddmod - dd).astype(np.float64) / (2 * np.pi))).astype(np.int64)
+    return np.concatenate([[0], np.cumsum(corr)])
+
+
+def test_bps_recover_unwrap_and_derotation_equal_host_restatement():
+    """The search followed by the unwrap and de-rotation launches of qh_bps_recover_*_dev, against a host restatement built from the indices
+    the same call returns, on a capture with real phase wander (the unwrapped phase leaves the grid's range many times) and at a length that is
+    not a multiple of the chunk: every interior symbol carries exactly the restated number of quarter turns, the edges the raw grid value, and
+    the output is the capture de-rotated by the returned phase.  (The search itself: the register-ring and tile kernel tests above.)"""
     from qampy_amd._lib import DeviceArray
-    sig = synth.make_capture(16, 2 ** 17 + 333, nmodes=2, os=1, snr_db=22, linewidth=2e6, seed=11, dtype=np.complex64)
-    E = DeviceArray.from_host(np.ascontiguousarray(np.asarray(sig)))
-    alpha = DeviceArray.from_host(np.ascontiguousarray(sig.coded_symbols, dtype=np.complex64))
-    res = {}
-    for fused in ("0", "1"):
-        forms.set("bps", "fused" if fused == "1" else "auto")
-        idx, ph, out = DeviceArray(E.shape, np.int32), DeviceArray(E.shape, np.float32), DeviceArray(E.shape, np.complex64)
-        hip_dsp.bps_recover_dev(E, 32, alpha, 20, idx, ph, out, angles=DeviceArray.from_host(hip_dsp.test_angle_grid(32, np.float32)))
-        res[fused] = (idx.to_host(), ph.to_host(), out.to_host())
-    assert np.array_equal(res["0"][0], res["1"][0])
-    assert np.abs(res["0"][1]).max() > np.pi                     # the phase did wander: the unwrap correction is exercised
-    np.testing.assert_array_equal(res["0"][1], res["1"][1])
-    np.testing.assert_array_equal(res["0"][2], res["1"][2])
+    L, N = 2 ** 17 + 333, 20
+    sig = synth.make_capture(16, L, nmodes=2, os=1, snr_db=22, linewidth=2e6, seed=11, dtype=np.complex64)
+    E = np.ascontiguousarray(np.asarray(sig))
+    grid = hip_dsp.test_angle_grid(32, np.float32).ravel()
+    dE, alpha = DeviceArray.from_host(E), DeviceArray.from_host(np.ascontiguousarray(sig.coded_symbols, dtype=np.complex64))
+    idx, ph, out = DeviceArray(E.shape, np.int32), DeviceArray(E.shape, np.float32), DeviceArray(E.shape, np.complex64)
+    hip_dsp.bps_recover_dev(dE, 32, alpha, 20, idx, ph, out, angles=DeviceArray.from_host(grid))
+    idx, ph, out = idx.to_host(), ph.to_host(), out.to_host()
+    assert np.abs(ph).max() > np.pi                              # the phase did wander: the unwrap correction is exercised
+    for m in range(E.shape[0]):
+        raw = grid[idx[m]]
+        turns = np.rint((ph[m, N:L - N].astype(np.float64) - raw[N:L - N]) / (np.pi / 2)).astype(np.int64)
+        np.testing.assert_array_equal(turns, _unwrap_quarter_turns(grid, idx[m], N))
+        np.testing.assert_array_equal(ph[m, :N], raw[:N])
+        np.testing.assert_array_equal(ph[m, L - N:], raw[L - N:])
+    _close(out, E.astype(np.complex128) * np.exp(1j * ph.astype(np.float64)), "c64")
+
+
+@pytest.mark.parametrize("key,value", [("bps", "fused"), ("bps", "plain"), ("pit_xaside", "1"), ("la_profile", "1")])
+def test_set_form_rejects_retired_forms(key, value, forms):
+    """Forms that measurements rejected are gone from the table: qh_set_form answers QH_ERR_ARG and leaves the phase search automatic."""
+    with pytest.raises(ValueError):
+        forms.set(key, value)
+    assert _lib.get_form("bps") == 0
