@@ -351,7 +351,9 @@ typedef struct qh_pit_opts {
     double acq_plateau;     /* 0 = 0.8: a chunk whose mean |err|^2 exceeds this fraction of the previous one's ends the acquisition */
     int64_t acq_chunk;      /* 0 = automatic: 2 / mu_acq steps (mu_acq = the gear-shifted step size) rounded to the nearest power of two, 256 .. 4096 */
     int64_t acq_max;        /* 0 = two chunks (at most TrSyms / 2 steps) */
-    int32_t correction;     /* -1 / 1: linearised coarse correction between the passes (see below), 0: plain relaxation */
+    int32_t correction;     /* -1 / 1: linearised coarse correction between the passes (see below), 0: plain relaxation - every pass up to
+                             * max_passes runs unless the tolerance is met (no "nothing gained over two passes" stop: S passes over S segments are
+                             * the sequential recurrence, and the boundary defects need not fall before the last one) */
     int32_t head_steps;     /* fixed step: > 0 - the first head_steps steps of every sweep run in the EXACT form, the segments cover the rest; 0: none, unless
                              * the passes stall on the start of the sweep (see head_auto_off) (ABI 6) */
     void *basis;            /* NULL, or the eigenbasis of this capture's input covariance from qh_pit_basis_*_dev (device memory) */
@@ -430,6 +432,14 @@ int qh_pit_basis_c128_dev(const void *E, int nmodes, int64_t L, int os, int ntap
  * the timed relaxation passes in order (all sweeps) and the sum of the acquisition chunks.  An event idles the stream for ~5.6 us,
  * so by default ONE pass per sweep is timed (pass 1); qh_set_pit_timing(2) times every pass. */
 int qh_pit_last_timing(float *pass_ms, int max_passes, int *npass, float *acq_ms);
+/* Which kernel form took the relaxation passes of the calling thread's most recent qh_train_equaliser_*_pit_dev call (read-only, host-side
+ * values; tests pin a kernel instantiation with it).  form: 0 the exact form only (no passes were launched), 1 segment (throughput form),
+ * 2 block-iterative, 3 look-ahead, 4 direct.  For the segment form: lanes per chain (16 / 8), taps per lane, padding taps in the last lane
+ * of an input mode, size of the partition / slicer table the kernel was instantiated for, adaptive-step kernel (0 / 1); zeros otherwise.
+ * (0 for the error functions whose kernels carry no table: cma, sgncma, cma2, mcma).  A call that falls back to the exact form after its
+ * passes keeps the passes' values; a call refused on its arguments leaves zeros; a process of a split capture that owns no segment
+ * reports form 1 and no layout.  Any pointer may be NULL.  form = 0 before any call. */
+int qh_pit_last_launch(int *form, int *lanes, int *tpl, int *rag, int *npart, int *adaptive);
 /* The sequential part of a COLD sweep ahead of time (ABI 8): the gear-shifted acquisition of a capture depends on the capture, the start taps, the step
  * size and the error function only - not on anything the previous capture's training produces - so a receiver that is handed capture after capture runs
  * it for capture k + 1 on another library stream while capture k trains (pipeline.ResidentReceiver.run(prefetch=True)), and hands the result to the

@@ -92,6 +92,7 @@ SIGNATURES = {
     "qh_pit_prepare_bytes": [_i, _i, _i64, _sz, C.POINTER(_sz)],
     "qh_pit_prepare_c64_dev": [_vp, _i, _i64, _i64, _i, _vp, _vp, _i, _vp, _i, _vp, _i64, _i, _vp, _vp, _sz],
     "qh_pit_last_timing": [_pf, _i, C.POINTER(_i), _pf],
+    "qh_pit_last_launch": [C.POINTER(_i)] * 6,
     "qh_pit_basis_bytes": [_i, C.POINTER(_sz)],
     "qh_pit_basis_c64_dev": [_vp, _i, _i64, _i, _i, _i64, _vp, _i],
     "qh_pit_basis_c128_dev": [_vp, _i, _i64, _i, _i, _i64, _vp, _i],
@@ -290,6 +291,15 @@ def last_pit_report():
     r = PitReport()
     call("qh_last_pit_report", C.byref(r))
     return r.as_dict()
+
+
+def pit_last_launch():
+    """What the relaxation passes of the calling thread's most recent tier-b training call launched (``qh_pit_last_launch``): ``form`` - 0 the
+    exact form only, 1 segment, 2 block-iterative, 3 look-ahead, 4 direct - and, for the segment form, ``lanes`` per chain, taps per lane
+    (``tpl``), padding taps (``rag``), table size (``npart``) and whether the adaptive-step kernel ran."""
+    v = [_i(0) for _ in range(6)]
+    call("qh_pit_last_launch", *[C.byref(x) for x in v])
+    return dict(zip(("form", "lanes", "tpl", "rag", "npart", "adaptive"), (x.value for x in v)))
 
 
 def gram_budget_gb():

@@ -54,6 +54,17 @@ int qh_pit_last_timing(float *pass_ms, int max_passes, int *npass, float *acq_ms
     *acq_ms = t.acq_ms;
     return QH_OK;
 }
+int qh_pit_last_launch(int *form, int *lanes, int *tpl, int *rag, int *npart, int *adaptive)
+{
+    const qh::PitLaunch &l = qh::pit_last_launch();
+    if (form) *form = l.form;
+    if (lanes) *lanes = l.lanes;
+    if (tpl) *tpl = l.tpl;
+    if (rag) *rag = l.rag;
+    if (npart) *npart = l.npart;
+    if (adaptive) *adaptive = l.adaptive;
+    return QH_OK;
+}
 int qh_pit_prepare_bytes(int nmodes, int ntaps, int64_t acq_steps, size_t elem_bytes, size_t *bytes)
 {
     *bytes = elem_bytes == 16 ? qh::pit_prep_layout<double>(nmodes, ntaps, acq_steps).total : qh::pit_prep_layout<float>(nmodes, ntaps, acq_steps).total;

@@ -2332,6 +2332,7 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
                   const int64_t *modes, int nsel, const void *symbols, int64_t nsy, int method, void *err, int zero_err,
                   const void *gram, const qh_pit_opts *opts, void *report_dev, int depth = 0)
 {
+    pit_last_launch() = PitLaunch{0, 0, 0, 0, 0, 0};             // (qh_pit_last_launch: nothing but the exact form until a pass is enqueued; a refused call leaves zeros too)
     int rc = ensure_init();
     if (rc) return rc;
     if ((rc = train_args_ok("train_equaliser", method, nmodes, ntaps, os, TrSyms, Niter, nsel, nsy, modes))) return rc;
@@ -2675,7 +2676,9 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
             d.theta = theta; d.modes_dev = (const int64_t *)modes_dev; d.ntot_w = ntot; d.S = (int)sg.S; d.sym = sym; d.corr_wanted = corr_wanted;
             d.extra = adaptive ? (const float *)ad_chg : nullptr;
             d.Dfin = (ye && !adaptive) ? (const float2 *)Dz[1] : nullptr; d.Vfin = (const float2 *)Vb; d.lam_fin = lam;
-            d.stall_from = adaptive ? 5 : 2;
+            // (plain relaxation asked for - opts.correction = 0: its fixed point is reached after S passes whatever the boundary defects do on the way - from
+            // converged taps they stay at the noise level until the last pass - so "nothing gained over two passes" must not end such a sweep early)
+            d.stall_from = o.correction == 0 ? QH_PIT_MAXPASS : (adaptive ? 5 : 2);
             return d;
         };
         auto timed = [&](int p) { return timing_mode == 2 || (timing_mode == 1 && p == 1); };
@@ -2717,12 +2720,14 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
                 for (int j = 0; j < 16; j++) sa.modes[j] = j < nsel ? modes[j] : 0;
                 sa.skip = &ctrl->done;
                 sa.q_first = own_first * nsel; sa.q_count = split ? own_count * nsel : 0;
+                pit_last_launch().form = 1;                             // (launch_seg adds the layout; a process of a split capture that owns no segment launches none)
                 if (!split || own_count > 0) { int r = launch_seg<R>(sa, method, adaptive); if (r) return r; }
                 if (adaptive) hipLaunchKernelGGL((pit_adapt_scan_kernel<R>), dim3(1), dim3(1024), 0, g_stream, ad_rS, (const R *)ad_rE, ad_eS, (const Cx<R> *)ad_eE, sg.S, ad_chg, (const PitCtrl *)ctrl, ad_relax, ad_rP, ad_dP, ad_newton);
             } else if (block_form) {
                 LaArgs<R> ls = la;
                 ls.TrSyms = sg.len; ls.nch = sg.S; ls.wx = Y; ls.err_off = (int64_t)it * TrSyms; ls.seg = 1; ls.seg_extra = sg.extra; ls.seg_tail = sg.tail;
                 ls.skip = &ctrl->done;
+                pit_last_launch() = PitLaunch{use_bi ? 2 : 3, 0, 0, 0, 0, 0};
                 if (sg.begin > 0) {                                  // an exact head: the segments cover the steps from sg.begin on
                     ls.E = (const Cx<R> *)E + sg.begin * os; ls.L = L - sg.begin * os; ls.err_off += sg.begin;
                     ls.G = (const GramPair<R> *)G + sg.begin * g_per_step;
@@ -2731,6 +2736,7 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
             } else {
                 TrainArgs<R> ts = ta;
                 ts.wx = Y; ts.nseg = sg.S; ts.seg_begin = sg.begin; ts.seg_len = sg.len; ts.seg_extra = sg.extra; ts.seg_tail = sg.tail; ts.seg_iter = it; ts.skip = &ctrl->done;
+                pit_last_launch() = PitLaunch{4, 0, 0, 0, 0, 0};
                 { int r = launch_any<R>(ts); if (r) return r; }
             }
             if (timed(p)) QH_HIP(hipEventRecord(ev.t1[p], g_stream));

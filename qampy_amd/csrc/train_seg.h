@@ -854,6 +854,12 @@ QH_SEG_EXTERN(QH_M_SBD) QH_SEG_EXTERN(QH_M_MDDMA) QH_SEG_EXTERN(QH_M_DD)
 #undef QH_SEG_EXTERN
 #endif  // QH_SEG_KERNELS
 
+// What the passes of the calling thread's most recent tier-b call launched (qh_pit_last_launch): host-side values, written where train_pit_dev
+// chooses the form of its passes and - segment form - below, where the kernel instantiation is chosen.  form: 0 the exact form only (no
+// passes), 1 segment, 2 block-iterative, 3 look-ahead, 4 direct; the rest describes a segment launch (zeros otherwise).
+struct PitLaunch { int form, lanes, tpl, rag, npart, adaptive; };
+inline PitLaunch &pit_last_launch() { static thread_local PitLaunch l = {0, 0, 0, 0, 0, 0}; return l; }
+
 // `a` complete except lpm / pitch / rag; method-specific table layout as for launch_bi (slicer tables for sbd / mddma / dd)
 inline bool seg_adaptive_supported(int method) { return method == QH_M_CMA || method == QH_M_SGNCMA || method == QH_M_MCMA || method == QH_M_MDDMA || method == QH_M_SBD; }
 template <typename R> int launch_seg(SegArgs<R> a, int method, bool adaptive = false)
@@ -871,6 +877,8 @@ template <typename R> int launch_seg(SegArgs<R> a, int method, bool adaptive = f
     const size_t lds = (size_t)((adaptive ? 2 * cpw : cpw) + 1) * a.pitch * sizeof(Cx<R>);
     dim3 grid((nq + cpw - 1) / cpw);
     const int npart = (int)(a.nsy - (a.nsy + 1) / 2);
+    const bool tabled = method == QH_M_RDE || method == QH_M_MRDE || method == QH_M_SBD || method == QH_M_MDDMA || method == QH_M_DD;
+    pit_last_launch() = PitLaunch{1, lpc, tpl, a.rag, tabled ? npart : 0, adaptive ? 1 : 0};     // (the other functions' kernels carry no table: NPART = 0)
     int rc;
     if (adaptive) {
         if constexpr (sizeof(R) == 4) {

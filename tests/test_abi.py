@@ -64,6 +64,33 @@ def test_get_form_refuses_a_null_value():
     assert _lib.load().qh_get_form(b"bps", None) == _lib.QH_ERR_ARG
 
 
+def test_pit_launch_record_is_declared_exported_and_empty_before_any_call():
+    """qh_pit_last_launch (which kernel form took tier b's passes): in the header, exported, bound - additive, the ABI version stays 11 - and it
+    answers form 0 (the exact form only: no pass launched) on a thread that has made no tier-b call; any pointer may be NULL.  No device needed:
+    the record is host memory."""
+    import ctypes as C
+    import threading
+    assert "qh_pit_last_launch" in _declared() and "qh_pit_last_launch" in _lib.SIGNATURES
+    lib = _lib.load()
+    assert lib.qh_abi_version() == 11
+    got = {}
+
+    def fresh_thread():
+        v = [C.c_int(-1) for _ in range(6)]
+        got["rc"] = lib.qh_pit_last_launch(*[C.byref(x) for x in v])
+        got["all"] = [x.value for x in v]
+        form = C.c_int(-1)
+        got["rc_null"] = lib.qh_pit_last_launch(C.byref(form), None, None, None, None, None)
+        got["form"] = form.value
+        got["rc_all_null"] = lib.qh_pit_last_launch(None, None, None, None, None, None)
+    th = threading.Thread(target=fresh_thread)
+    th.start()
+    th.join()
+    assert got == dict(rc=_lib.QH_OK, all=[0] * 6, rc_null=_lib.QH_OK, form=0, rc_all_null=_lib.QH_OK), got
+    if _lib.device_count() == 0:
+        assert _lib.pit_last_launch() == dict(form=0, lanes=0, tpl=0, rag=0, npart=0, adaptive=0)
+
+
 def test_header_is_plain_c(tmp_path):
     """include/qampy_hip.h is a C header (extern "C" only under __cplusplus): a C99 and a C++11 translation unit that include
     it compile, and a C program can link against the library by name."""

@@ -39,6 +39,10 @@ def _setup(method, M, nsym=2 ** 14, ntaps=15, dtype=np.complex64, seed=41):
     return sig, E, tr, w0, np.ascontiguousarray(sy), rt
 
 
+# table size of the segment kernel's instantiation (qh_pit_last_launch): partitions of mrde at 64-QAM, slicer thresholds of sbd at 16-QAM
+_NPART = {"mcma": 0, "cma": 0, "mrde": 3, "sbd": 3}
+
+
 def _run_pit(E, tr, niter, mu, w0, sy, method, pit, rt):
     dE, dsy, dmu = DeviceArray.from_host(E), DeviceArray.from_host(sy), DeviceArray.from_host(np.array([mu], rt))
     dw, derr = DeviceArray.from_host(w0.copy()), DeviceArray((2, tr * niter), E.dtype, zero=True)
@@ -62,6 +66,11 @@ def test_relaxation_fixed_point_is_the_sequential_recurrence(method, M, form, fo
     # propagated the true start taps through every segment
     w, e, rep = _run_pit(E, tr, 2, 5e-4, w0, sy, method, dict(segments=S, max_passes=S, tol=1e-12, correction=0, phase_seed=0, acquire=0, exact_redo_off=1), rt)
     assert rep["segments"] == S and rep["passes"] == S and len(rep["defect"]) == S
+    if form.startswith("segment"):              # 2 x 15 taps: 2 taps per lane + 1 padding tap on 16 lanes, 6 + 3 on 8 lanes - and it was that kernel that ran
+        lay = dict(lanes=16, tpl=2, rag=1) if form == "segment16" else dict(lanes=8, tpl=6, rag=3)
+        assert _lib.pit_last_launch() == dict(form=1, npart=_NPART[method], adaptive=0, **lay)
+    elif form == "direct":
+        assert _lib.pit_last_launch()["form"] == 4
     np.testing.assert_allclose(w, wo, rtol=2e-4, atol=2e-5)
     np.testing.assert_allclose(e, eo, rtol=2e-4, atol=1e-4)
     assert rep["defect"][-1] < 1e-4 and rep["defect"][-1] <= rep["defect"][0]
@@ -81,6 +90,8 @@ def test_coarse_correction_converges_to_the_exact_trajectory(method, M, lanes, a
     eo, wo, _ = hk.train_equaliser(E, tr, 1, 2, rt(1e-3), w0.copy(), None, False, sy, method)
     kw = dict(segments=16, max_passes=10, tol=2e-4, phase_seed=0, acquire=0, exact_redo_off=1)       # (the iteration itself: no exact-form way out)
     w, e, rep = _run_pit(E, tr, 1, 1e-3, w0, sy, method, dict(kw, correction=1), rt)
+    lay = dict(lanes=16, tpl=4, rag=3) if lanes == "16" else dict(lanes=8, tpl=6, rag=3)          # 2 x 21 taps
+    assert _lib.pit_last_launch() == dict(form=1, npart=_NPART[method], adaptive=0, **lay)
     w2, e2, rep2 = _run_pit(E, tr, 1, 1e-3, w0, sy, method, dict(kw, correction=0), rt)
     assert rep["converged"] and rep["correction"] and rep["passes"] <= 8, rep
     assert rep2["passes"] >= rep["passes"], (rep, rep2)
@@ -97,6 +108,8 @@ def test_complex128_and_oracle(form, forms):
     sig, E, tr, w0, sy, rt = _setup("mcma", 16, dtype=np.complex128)
     eo, wo, _ = oracle.train_equaliser(E, tr, 1, 2, 5e-4, w0.copy(), None, False, sy, "mcma")
     w, e, rep = _run_pit(E, tr, 1, 5e-4, w0, sy, "mcma", dict(segments=4, max_passes=4, tol=1e-14, correction=0, phase_seed=0, acquire=0, exact_redo_off=1), rt)
+    if form == "segment":
+        assert _lib.pit_last_launch() == dict(form=1, lanes=16, tpl=2, rag=1, npart=0, adaptive=0)
     np.testing.assert_allclose(w, wo, rtol=1e-8, atol=1e-10)
     np.testing.assert_allclose(e, eo, rtol=1e-8, atol=1e-9)
 
@@ -153,6 +166,8 @@ def test_uncertified_sweep_is_redone_in_the_exact_form(method, M, niter, forms):
     pit = dict(segments=16, max_passes=1, tol=1e-9, acquire=0)
     (wa, ea, _), (wb, eb, _), rep = _exact_and_tier_b(E, tr, niter, 1e-3, w0, sy, method, False, pit, rt)
     assert rep["exact_form"] and rep["converged"] and rep["segments"] == 16, rep
+    # (the pass that was not certified ran on the segment kernel: the record of the passes survives the exact redo)
+    assert _lib.pit_last_launch() == dict(form=1, lanes=16, tpl=4, rag=3, npart=_NPART[method], adaptive=0)
     assert np.array_equal(wa, wb) and np.array_equal(ea, eb)
     (_, _, _), (wc, ec, _), rep2 = _exact_and_tier_b(E, tr, niter, 1e-3, w0, sy, method, False, dict(pit, exact_redo_off=1), rt)
     assert not rep2["converged"] and not rep2["exact_form"], rep2
@@ -292,10 +307,11 @@ def test_tier_b_through_the_mirrored_api():
     assert core_eq.last_pit_reports()[0]["exact_form"] and np.array_equal(wpa, wpb) and np.array_equal(epa, epb)
 
 
-@pytest.mark.parametrize("os_", [1])
+@pytest.mark.parametrize("os_", [1, 3])
 def test_segment_form_at_other_sampling_rates(os_, forms):
     """The throughput form shares one sample window per PAIR of steps at 2 samples per symbol; every other rate takes its plain
-    step-by-step loop: S passes of plain relaxation over S segments are the sequential recurrence there too."""
+    step-by-step loop: S passes of plain relaxation over S segments are the sequential recurrence there too.  At 3 samples per symbol
+    a chunk of 64 steps does not fit an LDS row: a latency form takes the passes (and the launch record says so) - same result."""
     forms.set("pit_form", "segment")
     sig = synth.make_capture(16, 2 ** 13, nmodes=2, os=os_, snr_db=28, theta=np.pi / 5.6, dgd=30e-12, seed=43, dtype=np.complex64)
     E = np.ascontiguousarray(np.asarray(sig))
@@ -311,6 +327,10 @@ def test_segment_form_at_other_sampling_rates(os_, forms):
                            pit=dict(segments=4, max_passes=4, tol=1e-12, correction=0, phase_seed=0, acquire=0, exact_redo_off=1), report=rep)
     r = rep.read()
     assert r["segments"] == 4 and r["passes"] == 4
+    if os_ == 1:
+        assert _lib.pit_last_launch() == dict(form=1, lanes=16, tpl=2, rag=1, npart=0, adaptive=0)      # 2 x 9 taps: 5 lanes of 2 taps per mode
+    else:
+        assert _lib.pit_last_launch()["form"] in (2, 3, 4)
     np.testing.assert_allclose(dw.to_host(), wo, rtol=2e-4, atol=2e-5)
     np.testing.assert_allclose(derr.to_host(), eo, rtol=2e-4, atol=1e-4)
 
