@@ -241,6 +241,26 @@ int qh_cd_filter_c128(const void *E, int nmodes, int64_t L, int N, double c2, do
 int qh_cd_filter_c64_dev(const void *E, int nmodes, int64_t L, int N, double c2, double c1, double c0, int mode, void *out);
 int qh_cd_filter_c128_dev(const void *E, int nmodes, int64_t L, int N, double c2, double c1, double c0, int mode, void *out);
 
+/* ---- polyphase resampling (qampy/core/resample.py:37-127 resample_poly / rrcos_resample, qampy/core/filter.py:177-212 rrcos_pulseshaping):
+ * every row of E (nmodes, L) through the rational polyphase FIR
+ *     out[k] = gain * sum_m h[k down + (ntaps - 1) / 2 - m up] E[m],   k = 0 .. Lout - 1,   E zero outside the row,
+ * h: ntaps real taps in HOST memory (double; cast to the signal's precision, accumulation in that precision).  gain = up is scipy's
+ * resample_poly(window = h), gain = 1 zero insertion + fftconvolve(.., 'same') + decimation, up = down = 1 a 'same' convolution.
+ * 1 <= up, down <= 64; 1 <= ntaps <= 8191; Lout <= ceil(L up / down); out (nmodes, Lout) must not alias E.  The phase-major table is
+ * uploaded once per distinct (taps, up, precision).  Deterministic (no atomics). */
+int qh_resample_c64(const void *E, int nmodes, int64_t L, const double *h, int ntaps, int up, int down, double gain, int64_t Lout, void *out);
+int qh_resample_c128(const void *E, int nmodes, int64_t L, const double *h, int ntaps, int up, int down, double gain, int64_t Lout, void *out);
+int qh_resample_c64_dev(const void *E, int nmodes, int64_t L, const double *h, int ntaps, int up, int down, double gain, int64_t Lout, void *out);
+int qh_resample_c128_dev(const void *E, int nmodes, int64_t L, const double *h, int ntaps, int up, int down, double gain, int64_t Lout, void *out);
+/* Per-row moments of E (nmodes, L) on the device: mom[3 row + {0, 1, 2}] = mean re, mean im, mean |.|^2, accumulated in double in a fixed
+ * order; mom is DEVICE memory (3 nmodes doubles).  qh_center_scale: X <- (X - mean) sqrt(P / (mean |X|^2 - |mean|^2)) in place, the moments
+ * of X read from device memory; P = mom_in[3 row + 2] (the moments of another array, e.g. the resampler's input: the reference's
+ * renormalise=True), or `target` when mom_in is NULL.  Enqueue only: nothing is read back. */
+int qh_row_moments_c64_dev(const void *E, int nmodes, int64_t L, double *mom);
+int qh_row_moments_c128_dev(const void *E, int nmodes, int64_t L, double *mom);
+int qh_center_scale_c64_dev(void *X, int nmodes, int64_t L, const double *mom, const double *mom_in, double target);
+int qh_center_scale_c128_dev(void *X, int nmodes, int64_t L, const double *mom, const double *mom_in, double target);
+
 /* ---- select_angles: out[i] = angles[(p > 1 ? i : 0), idx[i]] ;  idx int64 (L,) ------------------------------- */
 int qh_select_angles_f32(const void *angles, int64_t p, int A, const int64_t *idx, int64_t L, void *out);
 int qh_select_angles_f64(const void *angles, int64_t p, int A, const int64_t *idx, int64_t L, void *out);

@@ -30,6 +30,7 @@ _SELECT = [_vp, _i64, _i, _vp, _i64, _vp]
 _DECIDE = [_vp, _i64, _vp, _i, _vp, _vp, _vp]
 _LLR = [_vp, _i64, _i, C.c_double, _vp, _i, _vp]
 _CD = [_vp, _i, _i64, _i, C.c_double, C.c_double, C.c_double, _i, _vp]      # E, nmodes, L, N, c2, c1, c0, mode, out
+_RESAMPLE = [_vp, _i, _i64, _vp, _i, _i, _i, C.c_double, _i64, _vp]                  # E, nmodes, L, h (host), ntaps, up, down, gain, Lout, out
 _ALIGNED = [_vp, _i64, _vp, _i64, _vp, _i, _i, _i64, _i64]          # row, N, idx_tx, ntx, alphabet, M, rot, lag, trim
 
 
@@ -76,6 +77,9 @@ SIGNATURES = {
     "qh_comp_freq_offset_c64": [_vp, _i, _i64, _vp, _i, _vp], "qh_comp_freq_offset_c128": [_vp, _i, _i64, _vp, _i, _vp],
     "qh_pilot_phase_trace_c64": [_vp, _i, _i64, _vp, _vp, _i, _vp, _vp], "qh_pilot_phase_trace_c128": [_vp, _i, _i64, _vp, _vp, _i, _vp, _vp],
     "qh_cd_filter_c64": _CD, "qh_cd_filter_c128": _CD, "qh_cd_filter_c64_dev": _CD, "qh_cd_filter_c128_dev": _CD,
+    "qh_resample_c64": _RESAMPLE, "qh_resample_c128": _RESAMPLE, "qh_resample_c64_dev": _RESAMPLE, "qh_resample_c128_dev": _RESAMPLE,
+    "qh_row_moments_c64_dev": [_vp, _i, _i64, _vp], "qh_row_moments_c128_dev": [_vp, _i, _i64, _vp],
+    "qh_center_scale_c64_dev": [_vp, _i, _i64, _vp, _vp, C.c_double], "qh_center_scale_c128_dev": [_vp, _i, _i64, _vp, _vp, C.c_double],
     "qh_select_angles_f32": _SELECT, "qh_select_angles_f64": _SELECT,
     "qh_make_decision_c64": _DECIDE, "qh_make_decision_c128": _DECIDE,
     "qh_make_decision_c64_dev": _DECIDE, "qh_make_decision_c128_dev": _DECIDE,

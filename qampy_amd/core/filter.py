@@ -1,4 +1,4 @@
-"""Small filters used by the pilot receiver (behaviour of qampy/core/filter.py:215-237)."""
+"""Small filters used by the pilot receiver (behaviour of qampy/core/filter.py:215-237), root-raised-cosine shaping and chromatic dispersion."""
 import numpy as np
 
 
@@ -8,6 +8,18 @@ def moving_average(sig, N=3):
     acc = np.cumsum(np.insert(s2, 0, 0, axis=-1), dtype=sig.dtype, axis=-1)
     out = (acc[:, N:] - acc[:, :-N]) / N
     return out.flatten() if sig.ndim == 1 else out
+
+
+def rrcos_pulseshaping(sig, fs, T, beta, taps=1001):
+    """Root-raised-cosine filtering of every row of ``sig`` at the rate ``fs`` (qampy/core/filter.py:177-212): a 'same' convolution
+    with ``taps`` samples of the response of symbol period ``T`` and roll-off ``beta``, scaled to a peak of 1, on the GPU
+    (qh_resample_* with up = down = 1).  ``taps=None``, the reference's spectral filter, is not implemented."""
+    from . import resample as _rs
+    if taps is None:
+        raise NotImplementedError("taps=None (the whole-row spectral root-raised-cosine filter) is not implemented: give a tap count")
+    one, X = _rs._as_rows(sig)
+    out = _rs._filter_rows(X, _rs.rrcos_taps(taps, fs, T, beta), 1, 1, 1.0, False)
+    return out[0] if one else out
 
 
 # ------------------------------------------------------------------------------------------------ chromatic dispersion

@@ -155,6 +155,55 @@ class ResidentReceiver:
         if getattr(self, "_prep", None) is not None:
             self.invalidate()
 
+    def load_resampled(self, E_raw, fs_in, beta=None, taps=4001, fftconv=True, next_capture=False, fs=None):
+        """Load a capture that arrives at the converter's rate: the raw rows ``E_raw`` (nmodes, Lin) at ``fs_in`` go to HBM, are resampled there
+        to the receiver's rate ``fs`` (``os`` samples per symbol; keyword, or the attribute ``self.fs``) into ``self.E`` (``self.E_next`` with
+        ``next_capture``), of which the first ``self.L`` outputs are kept, and every mode is centred and scaled to unit mean power - three
+        launches on stream 0 with no read-back between them (:mod:`qampy_amd.core.resample`).  ``beta=None``: the default Kaiser filter of
+        ``resample_poly``; otherwise a root-raised-cosine filter of ``taps`` taps, symbol period ``os / fs`` and roll-off ``beta``, on the
+        reference's ``fftconv`` path or its ``resample_poly`` path.  ValueError if the capture yields fewer than ``self.L`` samples.
+
+        Tier b: the loaded capture has unit power by construction, so the acquisition rule of ``load()`` is given the power 1.0 - it stays a
+        function of values the host knows."""
+        from .core import resample as _rs
+        fs = getattr(self, "fs", None) if fs is None else fs
+        if fs is None:
+            raise ValueError("load_resampled needs the receiver's sampling rate: fs=..., or set rx.fs")
+        E_raw = np.ascontiguousarray(np.asarray(E_raw), dtype=self.ct)
+        if E_raw.ndim != 2 or E_raw.shape[0] != self.nmodes:
+            raise ValueError("E_raw must be (%d, Lin)" % self.nmodes)
+        Lin = E_raw.shape[1]
+        up, down = _rs._resamplingfactors(fs_in, fs)
+        if _rs.n_out(Lin, up, down) < self.L:
+            raise ValueError("%d samples at %g resample to %d at %g, fewer than the receiver's %d" % (Lin, fs_in, _rs.n_out(Lin, up, down), fs, self.L))
+        if beta is None:
+            h, gain = _rs.default_window(up, down), up
+        else:
+            if not 0 < beta <= 1:
+                raise ValueError("beta needs to be in interval (0,1]")
+            h, gain = _rs.rrcos_taps(taps, up * fs_in, self.os / fs, beta), (1 if fftconv else up)
+        if next_capture and getattr(self, "E_next", None) is None:
+            self.E_next = DeviceArray((self.nmodes, self.L), self.ct)
+        buf = self.E_next if next_capture else self.E
+        if getattr(self, "_raw_buf", None) is None or self._raw_buf.shape != E_raw.shape:
+            self._raw_buf = DeviceArray(E_raw.shape, self.ct)
+            self._raw_mom = DeviceArray((self.nmodes, 3), np.float64)
+        self._filter_done()                        # (a filter on stream 2 may still be reading the buffer)
+        self._raw_buf.set(E_raw)
+        _rs.resample_dev(self._raw_buf, buf, h, up, down, gain)
+        _rs.center_scale_dev(buf, _rs.row_moments_dev(buf, self._raw_mom), power=1.0)
+        if getattr(self, "_prep", None) is not None:
+            self.invalidate()
+        if next_capture:
+            self._next_loaded = True
+            return
+        self._acq_asked = [False] * self.nstage
+        if self.tier == "b":
+            for s_, o in enumerate(self.pit):
+                if o.get("acquire") and not self.adaptive[s_] and not o.get("_acq_chunk_user"):
+                    o["acq_chunk"] = self._acq_chunk_rule(1.0, float(self.mu0[s_]), o)
+                    self._acq_asked[s_] = True
+
     def _acq_chunk_rule(self, power, mu, o):
         return _k.pit_acq_chunk(power, mu, self.nmodes * self.Ntaps, self.rt, o.get("gear"), o.get("acq_bound"))
 

@@ -86,6 +86,22 @@ class SignalQAM(np.ndarray):
             setattr(out, k, v)
         return out
 
+    def resample(self, fnew, **kwargs):
+        """Resample every mode to the rate ``fnew`` with a root-raised-cosine filter of symbol period ``Ts`` (default ``1 / fb``) on the GPU:
+        :func:`qampy_amd.core.resample.rrcos_resample` with this signal's ``fs`` (behaviour of qampy/signals.py:223-243).  Keyword arguments
+        are those of ``rrcos_resample`` (``beta``, ``taps``, ``renormalise``, ``fftconv``).  The symbols, the metadata and the class are
+        kept and ``fs`` becomes ``fnew``; a ratio close to 1 returns a copy."""
+        from .core import resample as _rs
+        if np.isclose(fnew / self.fs, 1):
+            out = self.recreate_from_np_array(np.array(self))
+        else:
+            Ts = kwargs.pop("Ts", 1 / self.fb)
+            arr = _rs.rrcos_resample(np.asarray(self), self.fs, fnew, Ts=Ts, **kwargs)
+            out = self.recreate_from_np_array(arr.astype(self.dtype, copy=False), fs=fnew)
+        if self._symbols is not None:
+            out._symbols = self._symbols.copy()
+        return out
+
     # ---- signal-quality metrics (qampy/signals.py:245-560); rows of ``signal_rx`` are modes, results are per mode
     @property
     def Nbits(self):
