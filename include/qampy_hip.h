@@ -220,6 +220,18 @@ int qh_bps_recover_part_c64_dev(const void *E, int nm, int64_t L, const void *an
 int qh_bps_recover_part_c128_dev(const void *E, int nm, int64_t L, const void *angles, int A, const void *symbols, int M, int N, int32_t *idx,
                                  void *ph, void *Eout, int part, int nparts);
 
+/* Two-stage blind phase search (qampy/core/phaserecovery.py:222-288) of `nm` modes at once, resident in HBM: the coarse search over the
+ * grid `angles` (A,) as above, then for symbol j the B angles fine[j, a] = (R)((double)angles[idx1[j]] + off[a]) with
+ * off[a] = linspace(-B/2, B/2, B)[a] / (B A) * pi/2 (formed by the library in double), searched with the window and edge rule of the
+ * per-symbol grid of qh_bps_*; ph = unwrap(4 fine[j, idx2[j]]) / 4 over the WHOLE row (no edge exclusion; the wrap counts are an exact
+ * integer prefix sum); Eout = E * exp(1j ph).  Nothing of size L x B is formed.  E, Eout (nm, L) complex, Eout != E; ph (nm, L) real;
+ * idx1, idx2 (nm, L) int32 out; angles may be NULL (grid formed on the device).  A >= 1, 1 <= B <= 64, N >= 1; a window 2N that does not
+ * fit the kernel's LDS ring (2N * 256 B complex64, 2N * 512 B complex128, of 120 KiB) is QH_ERR_ARG. */
+int qh_bps_twostage_recover_c64_dev(const void *E, int nm, int64_t L, const void *angles, int A, int B, const void *symbols, int M, int N,
+                                    int32_t *idx1, int32_t *idx2, void *ph, void *Eout);
+int qh_bps_twostage_recover_c128_dev(const void *E, int nm, int64_t L, const void *angles, int A, int B, const void *symbols, int M, int N,
+                                     int32_t *idx1, int32_t *idx2, void *ph, void *Eout);
+
 /* ---- comp_freq_offset (pilot receiver; qampy/core/phaserecovery.py:435-473): out[k, n] = E[k, n] exp(-2 pi i (n + 1) fo[k] / os),
  * fo (nmodes,) in units of the symbol rate, E / out (nmodes, L) host arrays */
 int qh_comp_freq_offset_c64(const void *E, int nmodes, int64_t L, const double *fo, int os, void *out);

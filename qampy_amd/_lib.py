@@ -26,6 +26,7 @@ _TRAIN = [_vp, _i, _i64, _i64, _i, _i, None, _vp, _i, _vp, _i, _i, _vp, _i64, _i
 _APPLY = [_vp, _i, _i64, _i, _vp, _i, _vp, _i, _vp]
 _BPS = [_vp, _i64, _vp, _i64, _i, _vp, _i, _i, _vp]
 _RECOVER = [_vp, _i, _i64, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]
+_TWOSTAGE = [_vp, _i, _i64, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]      # E, nm, L, angles, A, B, symbols, M, N, idx1, idx2, ph, Eout
 _SELECT = [_vp, _i64, _i, _vp, _i64, _vp]
 _DECIDE = [_vp, _i64, _vp, _i, _vp, _vp, _vp]
 _LLR = [_vp, _i64, _i, C.c_double, _vp, _i, _vp]
@@ -74,6 +75,7 @@ SIGNATURES = {
     "qh_bps_c64": _BPS, "qh_bps_c128": _BPS, "qh_bps_c64_dev": _BPS, "qh_bps_c128_dev": _BPS,
     "qh_bps_recover_c64_dev": _RECOVER, "qh_bps_recover_c128_dev": _RECOVER,
     "qh_bps_recover_part_c64_dev": _RECOVER + [_i, _i], "qh_bps_recover_part_c128_dev": _RECOVER + [_i, _i],
+    "qh_bps_twostage_recover_c64_dev": _TWOSTAGE, "qh_bps_twostage_recover_c128_dev": _TWOSTAGE,
     "qh_comp_freq_offset_c64": [_vp, _i, _i64, _vp, _i, _vp], "qh_comp_freq_offset_c128": [_vp, _i, _i64, _vp, _i, _vp],
     "qh_pilot_phase_trace_c64": [_vp, _i, _i64, _vp, _vp, _i, _vp, _vp], "qh_pilot_phase_trace_c128": [_vp, _i, _i64, _vp, _vp, _i, _vp, _vp],
     "qh_cd_filter_c64": _CD, "qh_cd_filter_c128": _CD, "qh_cd_filter_c64_dev": _CD, "qh_cd_filter_c128_dev": _CD,

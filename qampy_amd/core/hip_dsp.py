@@ -123,6 +123,73 @@ def bps_recover(E, Mtestangles, symbols, N):
     return h_out, h_ph
 
 
+def twostage_offsets(Mtestangles, B):
+    """Offsets ``off[a]`` of the ``B`` fine angles of the two-stage search around a coarse estimate, in double, by the reference's
+    expression (qampy/core/phaserecovery.py:278-279): symbol ``j`` is searched at ``(rt)(float64(coarse[j]) + off[a])``.  The library forms
+    the same table with the same double operations (csrc/bps.hip); the tests hold it to this one."""
+    return np.linspace(-B / 2, B / 2, B) / (B * Mtestangles) * np.pi / 2
+
+
+def bps_twostage_recover_dev(E, Mtestangles, B, symbols, N, idx1, idx2, ph, Eout, angles=None):
+    """
+    Device-resident two-stage carrier recovery of all modes at once (host layer qampy/core/phaserecovery.py:222-288): coarse search over
+    ``Mtestangles`` angles, ``B`` fine angles around each symbol's coarse estimate (:func:`twostage_offsets`; the ``(L, B)`` grid of the
+    reference is never formed), ``np.unwrap`` of the whole row and de-rotation without leaving HBM.  All arguments except the integers are
+    DeviceArrays: E, Eout (nmodes, L) complex, not the same buffer; ph (nmodes, L) real; idx1, idx2 (nmodes, L) int32 - the coarse and the
+    fine index; ``angles`` the (A,) grid of :func:`test_angle_grid` (``None``: formed on the device in the signal's precision).
+    ``1 <= B <= 64``.
+    """
+    suf, rt, ct = _lib.suffix(E.dtype)
+    nm, L = E.shape
+    _lib.call("qh_bps_twostage_recover_c" + ("64" if suf == "32" else "128") + "_dev", E.ptr, nm, L, angles.ptr if angles is not None else None,
+              int(Mtestangles), int(B), symbols.ptr, int(np.prod(symbols.shape)), int(N), idx1.ptr, idx2.ptr, ph.ptr, Eout.ptr)
+
+
+def bps_twostage_recover(E, Mtestangles, symbols, N, B=4):
+    """
+    Two-stage carrier recovery of every row of ``E (nmodes, L)`` in one go: upload once, :func:`bps_twostage_recover_dev` in HBM,
+    ``(Eout, ph)`` back - where the composed host layer makes two uploads, two index downloads and an ``(L, B)`` grid per mode.
+    """
+    E = np.asarray(E)
+    if E.ndim != 2 or not np.iscomplexobj(E):
+        raise TypeError("bps_twostage_recover works on a 2-d complex array")
+    suf, rt, ct = _lib.suffix(E.dtype)
+    symbols = np.ascontiguousarray(symbols)
+    if symbols.dtype != ct:
+        raise TypeError("symbols must be %s" % np.dtype(ct).name)
+    nm, L = E.shape
+    if L == 0:
+        return np.zeros((nm, 0), ct), np.zeros((nm, 0), rt)
+    D = _lib.DeviceArray
+    E = np.ascontiguousarray(E)
+    dsy, dang = D.from_host(symbols), D.from_host(test_angle_grid(Mtestangles, rt))
+    dE, idx1, idx2, ph, out = D((nm, L), ct), D((nm, L), np.int32), D((nm, L), np.int32), D((nm, L), rt), D((nm, L), ct)
+    if E.nbytes < _lib.PINNED_MIN_BYTES:
+        dE.set(E)
+        bps_twostage_recover_dev(dE, Mtestangles, B, dsy, N, idx1, idx2, ph, out, angles=dang)
+        return out.to_host(), ph.to_host()
+    # row-pipelined like bps_recover: row r + 1 goes up while row r is searched and row r - 1 comes back into pooled pinned memory
+    h_out, h_ph = _lib.pinned_empty((nm, L), ct), _lib.pinned_empty((nm, L), rt)
+    ev_up, ev_done = [_lib.Event() for _ in range(nm)], [_lib.Event() for _ in range(nm)]
+    try:
+        for r in range(nm):
+            _lib.call("qh_use_stream", 1)
+            _lib.call("qh_memcpy_h2d_async", dE.row(r).ptr, E[r].ctypes.data, E[r].nbytes)
+            ev_up[r].record()
+            _lib.call("qh_use_stream", 0)
+            _lib.call("qh_stream_wait_event", ev_up[r].ptr)
+            bps_twostage_recover_dev(_row2d(dE, r), Mtestangles, B, dsy, N, _row2d(idx1, r), _row2d(idx2, r), _row2d(ph, r), _row2d(out, r), angles=dang)
+            ev_done[r].record()
+            _lib.call("qh_use_stream", 2)
+            _lib.call("qh_stream_wait_event", ev_done[r].ptr)
+            _lib.call("qh_memcpy_d2h_async", h_out[r].ctypes.data, out.row(r).ptr, h_out[r].nbytes)
+            _lib.call("qh_memcpy_d2h_async", h_ph[r].ctypes.data, ph.row(r).ptr, h_ph[r].nbytes)
+    finally:
+        _lib.call("qh_use_stream", 0)
+    _lib.sync()
+    return h_out, h_ph
+
+
 def _row2d(a, r):
     """Row ``r`` of a 2-d DeviceArray as a (1, L) view."""
     v = a.row(r)

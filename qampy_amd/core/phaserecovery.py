@@ -36,9 +36,20 @@ def bps_twostage(E, Mtestangles, symbols, N, B=4, method="pyt", **kwargs):
     Two-stage blind phase search (Zhuge et al., OFC 2011), same contract as qampy/core/phaserecovery.py:222-288: a
     coarse search over ``Mtestangles`` angles, then ``B`` angles around each symbol's coarse estimate (a per-symbol
     ``(L, B)`` grid, the ``p == L`` branch of the kernel).  Returns ``(Eout, ph)``; the whole phase track is unwrapped.
+
+    method : "pyt" / "hip" compose the search from the index kernel mode by mode, as the reference does; "fused" sends all modes through
+    one device-resident pass (``hip_dsp.bps_twostage_recover``: no ``(L, B)`` grid, no index round trips; ``1 <= B <= 64``).
     """
-    if method.lower() not in ("pyt", "hip"):
-        raise ValueError("Method needs to be 'pyt' or 'hip' (the py/pyx/af back-ends of the reference are not provided)")
+    if method.lower() not in ("pyt", "hip", "fused"):
+        raise ValueError("Method needs to be 'pyt', 'hip' or 'fused' (the py/pyx/af back-ends of the reference are not provided)")
+    if method.lower() == "fused":
+        rows = np.atleast_2d(E)
+        out, ph = _dsp.bps_twostage_recover(np.ascontiguousarray(rows), Mtestangles, np.asarray(symbols).astype(rows.dtype, copy=False), N, B=B)
+        if E.ndim == 1:
+            return out.reshape(-1), ph.reshape(-1)
+        if type(E) is not np.ndarray and hasattr(E, "recreate_from_np_array"):        # keep the signal subclass like E * exp(..) does
+            out = E.recreate_from_np_array(out)
+        return out, ph
     rdt = E.real.dtype
     rows = np.atleast_2d(E)
     alphabet = np.asarray(symbols).astype(E.dtype, copy=False)

@@ -119,8 +119,8 @@ int ensure_init()
 }
 
 // grow-only scratch slots so that the resident pipeline never allocates (and never synchronises) inside a timed region
-thread_local void *g_scratch[16] = {nullptr};
-thread_local size_t g_scratch_n[16] = {0};
+thread_local void *g_scratch[SCRATCH_SLOTS] = {nullptr};
+thread_local size_t g_scratch_n[SCRATCH_SLOTS] = {0};
 thread_local unsigned g_scratch_epoch = 0;
 // ---- the table of form switches (common.h FormKey; qh_set_form / qh_set_trainer).  Values:
 //   trainer    0 automatic, 1 direct, 2 lookahead, 3 iterative          pit_form   0 automatic, 1 segment (throughput form), 2 block (latency forms)
@@ -350,7 +350,7 @@ int qh_release_scratch(void)
     int rc = qh::ensure_init();
     if (rc) return rc;
     for (int i = 0; i < 4; i++) QH_HIP(hipStreamSynchronize(qh::g_streams[i]));
-    for (int i = 0; i < 16; i++) {
+    for (int i = 0; i < qh::SCRATCH_SLOTS; i++) {
         if (qh::g_scratch[i]) QH_HIP(hipFree(qh::g_scratch[i]));
         qh::g_scratch[i] = nullptr; qh::g_scratch_n[i] = 0;
     }
@@ -365,7 +365,7 @@ int qh_thread_release(void)
     // stream created with a CU mask must not be left to the runtime's own teardown when a profiler is attached)
     if (!qh::g_stream) return QH_OK;
     for (int i = 0; i < 4; i++) if (qh::g_streams[i]) (void)hipStreamSynchronize(qh::g_streams[i]);
-    for (int i = 0; i < 16; i++) {
+    for (int i = 0; i < qh::SCRATCH_SLOTS; i++) {
         if (qh::g_scratch[i]) (void)hipFree(qh::g_scratch[i]);
         qh::g_scratch[i] = nullptr; qh::g_scratch_n[i] = 0;
     }
@@ -498,6 +498,24 @@ int qh_memcpy_d2d(void *dst, const void *src, size_t bytes)
     if (bytes) QH_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, qh::g_stream));
     return QH_OK;
 }
+// Two-stage blind phase search on device pointers.  The arguments are checked here, before anything is enqueued.
+#define QH_TWOSTAGE_CHECK()                                                                                              \
+    QH_REQUIRE(A >= 1 && B >= 1 && B <= 64 && N >= 1 && nm >= 1 && L >= 0 && M >= 1, "bps_twostage: bad sizes (1 <= B <= 64)"); \
+    QH_REQUIRE(Eout != E, "bps_twostage: Eout must not be E");                                                           \
+    if (L == 0) return QH_OK
+int qh_bps_twostage_recover_c64_dev(const void *E, int nm, int64_t L, const void *angles, int A, int B, const void *symbols, int M, int N,
+                                    int32_t *idx1, int32_t *idx2, void *ph, void *Eout)
+{
+    QH_TWOSTAGE_CHECK();
+    return qh::bps_twostage_recover_f32(E, nm, L, angles, A, B, symbols, M, N, idx1, idx2, ph, Eout);
+}
+int qh_bps_twostage_recover_c128_dev(const void *E, int nm, int64_t L, const void *angles, int A, int B, const void *symbols, int M, int N,
+                                     int32_t *idx1, int32_t *idx2, void *ph, void *Eout)
+{
+    QH_TWOSTAGE_CHECK();
+    return qh::bps_twostage_recover_f64(E, nm, L, angles, A, B, symbols, M, N, idx1, idx2, ph, Eout);
+}
+#undef QH_TWOSTAGE_CHECK
 int qh_event_create(void **ev)
 {
     int rc = qh::ensure_init();

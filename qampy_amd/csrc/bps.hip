@@ -586,6 +586,18 @@ template <> inline bool bps_stream_ok<float>(int64_t p, int A, int N, int M)
     return !off && p == 1 && A <= 64 && 2 * N <= BS_MAXRING && M >= 1;
 }
 
+// The alphabet of a search, analysed on the device into the next of BPS_DESC_RING descriptors of the calling thread (see bps_dev)
+template <typename R> static int analyse_alphabet(const void *symbols, int M, void **desc)
+{
+    void *ring = nullptr;
+    static thread_local unsigned desc_next = 0;
+    int rc = scratch(3, BPS_DESC_RING * sizeof(AlphabetDesc<double>), &ring);
+    if (rc) return rc;
+    *desc = (char *)ring + (size_t)(desc_next++ % BPS_DESC_RING) * sizeof(AlphabetDesc<double>);
+    hipLaunchKernelGGL((analyse_alphabet_kernel<R>), dim3(1), dim3(64), 0, g_stream, (const Cx<R> *)symbols, M, (AlphabetDesc<R> *)*desc);
+    return QH_OK;
+}
+
 // nm rows of length L (consecutive in memory) against one angle grid; idx likewise
 template <typename R>
 int bps_dev(const void *E, int64_t L, const void *angles, int64_t p, int A, const void *symbols, int M, int N, int32_t *idx, int nm = 1,
@@ -607,13 +619,7 @@ int bps_dev(const void *E, int64_t L, const void *angles, int64_t p, int A, cons
     // carries no state of the part before it, and another search of the same thread in between - on this or another of its streams - cannot
     // overwrite a descriptor a kernel in flight still reads (round 5 kept ONE descriptor per thread, written by part 0 only).
     void *desc = nullptr;
-    {
-        void *ring = nullptr;
-        static thread_local unsigned desc_next = 0;
-        if ((rc = scratch(3, BPS_DESC_RING * sizeof(AlphabetDesc<double>), &ring))) return rc;
-        desc = (char *)ring + (size_t)(desc_next++ % BPS_DESC_RING) * sizeof(AlphabetDesc<double>);
-    }
-    hipLaunchKernelGGL((analyse_alphabet_kernel<R>), dim3(1), dim3(64), 0, g_stream, (const Cx<R> *)symbols, M, (AlphabetDesc<R> *)desc);
+    if ((rc = analyse_alphabet<R>(symbols, M, &desc))) return rc;
     if (stream) {
         BpsStreamArgs s;
         s.E = (const Cx<float> *)E; s.angles = (const float *)angles; s.symbols = (const Cx<float> *)symbols;
@@ -731,10 +737,10 @@ constexpr int UW_CHUNK = UW_THREADS * UW_PER_THREAD;
 template <typename R> __device__ __forceinline__ R fmod_(R a, R b);
 template <> __device__ __forceinline__ float fmod_<float>(float a, float b) { return fmodf(a, b); }
 template <> __device__ __forceinline__ double fmod_<double>(double a, double b) { return fmod(a, b); }
-template <typename R> __device__ __forceinline__ int unwrap_jump(const R *angles, int kprev, int kcur)
+template <typename R> __device__ __forceinline__ int unwrap_jump(R phprev, R phcur)
 {
     const R pi = (R)3.14159265358979323846, twopi = (R)6.28318530717958647692;
-    const R dd = (R)4 * angles[kcur] - (R)4 * angles[kprev];
+    const R dd = (R)4 * phcur - (R)4 * phprev;
     if (abs_(dd) < pi) return 0;
     R m = fmod_<R>(dd + pi, twopi);
     if (m != 0 && m < 0) m += twopi;
@@ -744,19 +750,29 @@ template <typename R> __device__ __forceinline__ int unwrap_jump(const R *angles
     return (int)rint((double)corr / 6.28318530717958647692);
 }
 
-template <typename R>
-__global__ void __launch_bounds__(UW_THREADS) unwrap_partial_kernel(const int32_t *idx, int64_t L, int N, const R *angles, int *chunk_sum,
-                                                                     int64_t nchunk)
+// Where the phase of a symbol comes from and which stretch of a row is unwrapped [lo, hi) - the three unwrap kernels are written once for both:
+//   UwGrid: single stage - the grid entry of the symbol's index, unwrapped on [N, L - N) (phaserecovery.py:155)
+//   UwFine: two stages   - entry (idx1, idx2) of the (A, B) table of fine angles, the whole row unwrapped (phaserecovery.py:283)
+template <typename R> struct UwGrid {
+    const int32_t *idx; const R *angles; int64_t L, lo, hi;
+    __device__ __forceinline__ R at(int64_t mode, int64_t i) const { return angles[idx[mode * L + i]]; }
+};
+template <typename R> struct UwFine {
+    const int32_t *idx1, *idx2; const R *fine; int64_t L, lo, hi; int B;
+    __device__ __forceinline__ R at(int64_t mode, int64_t i) const { return fine[(size_t)idx1[mode * L + i] * B + idx2[mode * L + i]]; }
+};
+
+template <typename R, typename P>
+__global__ void __launch_bounds__(UW_THREADS) unwrap_partial_kernel(P src, int *chunk_sum, int64_t nchunk)
 {
-    // sums of the jump indicators of one chunk of one mode; interior = [N, L-N), the first interior element has no jump
+    // sums of the jump indicators of one chunk of one mode; the first element of the unwrapped stretch has no jump
     __shared__ int red[UW_THREADS / 64];
     const int64_t mode = blockIdx.y;
-    const int32_t *ix = idx + mode * L;
     const int64_t base = (int64_t)blockIdx.x * UW_CHUNK;
     int s = 0;
     for (int r = 0; r < UW_PER_THREAD; r++) {
         const int64_t i = base + threadIdx.x + (int64_t)r * UW_THREADS;
-        if (i > N && i < L - N) s += unwrap_jump<R>(angles, ix[i - 1], ix[i]);
+        if (i > src.lo && i < src.hi) s += unwrap_jump<R>(src.at(mode, i - 1), src.at(mode, i));
     }
     for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
@@ -791,14 +807,13 @@ __global__ void __launch_bounds__(1024) unwrap_scan_kernel(int *chunk_sum, int64
     for (int64_t i = i0; i < i1; i++) { const int v = cs[i]; cs[i] = run; run += v; }
 }
 
-template <typename R>
-__global__ void __launch_bounds__(UW_THREADS) unwrap_apply_kernel(const Cx<R> *E, const int32_t *idx, const int *chunk_off,
-                                                                   int64_t L, int N, const R *angles, int64_t nchunk, R *ph, Cx<R> *Eout)
+template <typename R, typename P>
+__global__ void __launch_bounds__(UW_THREADS) unwrap_apply_kernel(const Cx<R> *E, P src, const int *chunk_off, int64_t nchunk, R *ph, Cx<R> *Eout)
 {
     __shared__ int wsum[UW_THREADS / 64];
     __shared__ int tsum[UW_THREADS];
     const int64_t mode = blockIdx.y;
-    const int32_t *ix = idx + mode * L;
+    const int64_t L = src.L;
     const int64_t base = (int64_t)blockIdx.x * UW_CHUNK;
     // each thread owns UW_PER_THREAD consecutive symbols so the in-chunk prefix is a short serial run + a block scan
     const int64_t t0 = base + (int64_t)threadIdx.x * UW_PER_THREAD;
@@ -808,7 +823,7 @@ __global__ void __launch_bounds__(UW_THREADS) unwrap_apply_kernel(const Cx<R> *E
     for (int r = 0; r < UW_PER_THREAD; r++) {
         const int64_t i = t0 + r;
         int j = 0;
-        if (i > N && i < L - N) j = unwrap_jump<R>(angles, ix[i - 1], ix[i]);
+        if (i > src.lo && i < src.hi) j = unwrap_jump<R>(src.at(mode, i - 1), src.at(mode, i));
         local += j;
         jmp[r] = local;                       // inclusive within the thread
     }
@@ -837,10 +852,9 @@ __global__ void __launch_bounds__(UW_THREADS) unwrap_apply_kernel(const Cx<R> *E
         const int e = r * UW_THREADS + threadIdx.x;
         const int64_t i = base + e;
         if (i < L) {
-            const bool interior = (i >= N && i < L - N);
-            const int k = ix[i];
-            // edges keep the raw grid value of idx = 0, i.e. angles[0] (phaserecovery.py:155 unwraps the interior only)
-            R p = angles[k];
+            const bool interior = (i >= src.lo && i < src.hi);
+            // single stage: the edges keep the raw grid value of idx = 0, i.e. angles[0] (phaserecovery.py:155 unwraps the interior only)
+            R p = src.at(mode, i);
             if (interior) p += (pi / 2) * (R)corr[e];
             ph[mode * L + i] = p;
             R sn, cs;
@@ -858,6 +872,19 @@ template <typename R> __global__ void linspace_kernel(R *angles, int A)
     if (j < A) angles[j] = -pi / 4 + ((pi / 2) / (R)A) * (R)j;
 }
 
+// The grid formed on the device, into the next of a ring of grids of the calling thread (see the alphabet descriptors in bps_dev)
+template <typename R> static int device_grid(int A, void **dang)
+{
+    void *ring = nullptr;
+    static thread_local unsigned grid_next = 0;
+    const size_t one = ((size_t)A * sizeof(R) + 255) & ~(size_t)255;
+    int rc = scratch(0, BPS_DESC_RING * one, &ring);
+    if (rc) return rc;
+    *dang = (char *)ring + (size_t)(grid_next++ % BPS_DESC_RING) * one;
+    hipLaunchKernelGGL((linspace_kernel<R>), dim3((A + 63) / 64), dim3(64), 0, g_stream, (R *)*dang, A);
+    return QH_OK;
+}
+
 // angles: the (A,) test-angle grid in HBM as the host layer builds it (np.linspace in double, cast to the signal's precision,
 // phaserecovery.py:145), or nullptr for a grid formed on the device in the signal's precision
 template <typename R>
@@ -872,24 +899,248 @@ int bps_recover_dev(const void *E, int nm, int64_t L, const void *angles, int A,
     const int64_t nchunk = (L + UW_CHUNK - 1) / UW_CHUNK;
     void *dang = const_cast<void *>(angles), *dchunk = nullptr;     // grow-only library scratch: no allocation / sync in the steady state
     if ((rc = scratch(1, (size_t)nm * nchunk * sizeof(int), &dchunk))) return rc;
-    if (!dang) {                                                  // (formed by every part, into the next of a ring of grids: see the alphabet descriptors in bps_dev)
-        void *ring = nullptr;
-        static thread_local unsigned grid_next = 0;
-        const size_t one = ((size_t)A * sizeof(R) + 255) & ~(size_t)255;
-        if ((rc = scratch(0, BPS_DESC_RING * one, &ring))) return rc;
-        dang = (char *)ring + (size_t)(grid_next++ % BPS_DESC_RING) * one;
-        hipLaunchKernelGGL((linspace_kernel<R>), dim3((A + 63) / 64), dim3(64), 0, g_stream, (R *)dang, A);
-    }
+    if (!dang && (rc = device_grid<R>(A, &dang))) return rc;       // (formed by every part)
     if ((rc = bps_dev<R>(E, L, dang, 1, A, symbols, M, N, idx, nm, part, nparts))) return rc;
     if (part != nparts - 1) return QH_OK;
-    hipLaunchKernelGGL((unwrap_partial_kernel<R>), dim3((unsigned)nchunk, nm), dim3(UW_THREADS), 0, g_stream, idx, L, N, (const R *)dang,
-                       (int *)dchunk, nchunk);
+    const UwGrid<R> src{idx, (const R *)dang, L, (int64_t)N, L - N};
+    hipLaunchKernelGGL((unwrap_partial_kernel<R, UwGrid<R>>), dim3((unsigned)nchunk, nm), dim3(UW_THREADS), 0, g_stream, src, (int *)dchunk, nchunk);
     hipLaunchKernelGGL(unwrap_scan_kernel, dim3(nm), dim3(1024), 0, g_stream, (int *)dchunk, nchunk);
-    hipLaunchKernelGGL((unwrap_apply_kernel<R>), dim3((unsigned)nchunk, nm), dim3(UW_THREADS), 0, g_stream, (const Cx<R> *)E, idx,
-                       (const int *)dchunk, L, N, (const R *)dang, nchunk, (R *)ph, (Cx<R> *)Eout);
+    hipLaunchKernelGGL((unwrap_apply_kernel<R, UwGrid<R>>), dim3((unsigned)nchunk, nm), dim3(UW_THREADS), 0, g_stream, (const Cx<R> *)E, src,
+                       (const int *)dchunk, nchunk, (R *)ph, (Cx<R> *)Eout);
     QH_HIP(hipGetLastError());
     return QH_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ two-stage search, second stage
+// Reference behaviour: qampy/core/phaserecovery.py:222-288 (bps_twostage).  After the coarse search over the (1, A) grid, symbol j is
+// searched again over B angles around its coarse estimate,
+//     fine[j, a] = (R)((double)angles[idx1[j]] + off[a]),   off[a] = linspace(-B/2, B/2, B)[a] / (B A) * pi/2   (:278-279),
+// with the window and edge rule of the per-symbol-grid branch of bps_kernel (p == L): idx2[i] = first arg-min over a of the sum of the
+// distances of rows i - N + 1 .. i + N for N <= i < L - N, else 0.  The reference materialises the (L, B) grid; here it never exists:
+// fine[j, .] takes one of A rows only, so the A x B fine angles and their rotators exp(j fine) are formed ONCE (twostage_table_kernel,
+// the same double sum, cast and sincos as the per-symbol branch: bit-identical distances) and a symbol looks its row up by idx1[j].
+//
+// bps_fine_kernel, one wave per workgroup and no barrier in its loop: lane <-> (run of S consecutive output symbols, fine angle).  Bp, the
+// next power of two >= B, lanes side by side hold the Bp angles of one run, so a wave carries 64 / Bp runs.  A lane streams the rows of
+// its run once: rotate, decide against the alphabet (AlphabetDesc: mirror-symmetric product / product / brute force, the arithmetic of
+// bps_kernel), keep the last 2N distances in a ring of its own in LDS (column `lane` of a [2N][64] plane: conflict free) and ONE running
+// window sum in a register - s += entering, s -= leaving, re-formed as the direct 2N-term sum at the start of every run of bps_kernel's
+// sliding sums (a lane's run of S symbols is one tile of that kernel: bit-identical sums and indices).  The arg-min over the angles is a butterfly over the Bp neighbouring lanes (ties to the lower index; nothing below 1000: index
+// 0, pythran_dsp.py:31-41).  Rows are taken eight at a time so that the loads of a block (symbol, coarse index, then the rotator that
+// index selects) are in flight together.
+// Bound: fp32 / fp64 VALU issue like the coarse search - B (not 64) rotations and decisions per symbol plus the 2N - 1 halo rows of
+// every run; HBM traffic is 16 B per symbol (E, idx1 in, idx2 out), the table stays in cache.
+constexpr int BF_ROWS = 8;               // rows per block of loads
+
+struct TwoStageOffsets { double off[64]; };
+
+template <typename R>
+__global__ void __launch_bounds__(256) twostage_table_kernel(const R *angles, int A, int B, TwoStageOffsets o, R *fine, Cx<R> *rot)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= A * B) return;
+    const int k = e / B, ja = e - k * B;
+    const R f = (R)((double)angles[k] + o.off[ja]);
+    R sn, cs;
+    sincos_<R>(f, &sn, &cs);
+    fine[e] = f;
+    rot[e] = Cx<R>{cs, sn};
+}
+
+template <typename R> struct BpsFineArgs {
+    const Cx<R> *E;              // (nm, L)
+    const Cx<R> *rot;            // (A, B) rotators of the fine angles
+    const Cx<R> *symbols;        // (M,)
+    const AlphabetDesc<R> *desc;
+    const int32_t *idx1;         // (nm, L) coarse indices
+    int32_t *idx2;               // (nm, L)
+    int64_t L;
+    int B, lgBp, M, N, S, RUN;
+};
+
+template <typename R>
+__global__ void __launch_bounds__(64) bps_fine_kernel(BpsFineArgs<R> a)
+{
+    extern __shared__ __attribute__((aligned(16))) char bf_smem[];
+    const int lane = threadIdx.x, N = a.N, W = 2 * a.N;
+    R *ring = reinterpret_cast<R *>(bf_smem);                          // [W][64]
+    R *lev = ring + (size_t)W * 64;                                    // [2][BPS_MAX_LEVELS] per-axis levels of a product alphabet
+    const int Bp = 1 << a.lgBp;
+    const int ja = lane & (Bp - 1), run = lane >> a.lgBp;
+    const bool has_angle = ja < a.B;                                   // (B no power of two: the lanes above it never win)
+    const int jc = has_angle ? ja : a.B - 1;
+    const int64_t L = a.L;
+    const Cx<R> *E = a.E + (size_t)blockIdx.y * L;
+    const int32_t *idx1 = a.idx1 + (size_t)blockIdx.y * L;
+    int32_t *idx2 = a.idx2 + (size_t)blockIdx.y * L;
+    const int64_t c0 = ((int64_t)blockIdx.x * (64 >> a.lgBp) + run) * a.S;     // outputs [c0, c0 + S) of this lane's run
+    const bool product = a.desc->product != 0, symmetric = a.desc->symmetric != 0;
+    const int nre = product ? a.desc->nre : 0, nim = product ? a.desc->nim : 0;
+    if (lane < BPS_MAX_LEVELS) {
+        lev[lane] = product && lane < nre ? a.desc->re[lane] : (R)0;
+        lev[BPS_MAX_LEVELS + lane] = product && lane < nim ? a.desc->im[lane] : (R)0;
+    }
+    for (int r = 0; r < W; r++) ring[r * 64 + lane] = 0;
+    __syncthreads();
+
+    auto distance = [&](R tr, R ti) -> R {                             // bps_kernel's three forms, one element at a time
+        R d0;
+        if (symmetric) {
+            R mr = (R)3.0e38, mi = (R)3.0e38;
+            for (int r = nre / 2; r < nre; r++) mr = min_(mr, abs_(abs_(tr) - lev[r]));
+            for (int r = nim / 2; r < nim; r++) mi = min_(mi, abs_(abs_(ti) - lev[BPS_MAX_LEVELS + r]));
+            d0 = fma_(mr, mr, mi * mi);
+        } else if (product) {
+            R mr = (R)3.0e38, mi = (R)3.0e38;
+            for (int r = 0; r < nre; r++) mr = min_(mr, abs_(tr - lev[r]));
+            for (int r = 0; r < nim; r++) mi = min_(mi, abs_(ti - lev[BPS_MAX_LEVELS + r]));
+            d0 = fma_(mr, mr, mi * mi);
+        } else {
+            d0 = (R)1000.;                                             // det_symbol: strict `<` from d0 = 1000 (:17-22)
+            for (int k = 0; k < a.M; k++) {
+                const Cx<R> sk = a.symbols[k];                         // wave-uniform -> scalar load
+                const R dr = tr - sk.re, di = ti - sk.im;
+                const R d = fma_(dr, dr, di * di);
+                d0 = d < d0 ? d : d0;
+            }
+        }
+        return d0 < (R)100. ? d0 : (R)100.;                            // dists start at 100 (:73, :83)
+    };
+
+    R s = 0;
+    int slot = 0;                                                      // ring row of the oldest distance = the next one written
+    const int nrows = a.S + W - 1;                                     // row t is symbol c0 - N + 1 + t and completes the window of output c0 + t - (W - 1)
+    for (int t0 = 0; t0 < nrows; t0 += BF_ROWS) {
+        const int64_t l0 = c0 - N + 1 + t0;
+        Cx<R> xs[BF_ROWS], cs[BF_ROWS];
+        int ks[BF_ROWS];
+#pragma unroll
+        for (int q = 0; q < BF_ROWS; q++) {
+            const int64_t l = l0 + q, lc = l < 0 ? 0 : (l < L ? l : L - 1);
+            xs[q] = ldg(E + lc);
+            ks[q] = idx1[lc];
+        }
+#pragma unroll
+        for (int q = 0; q < BF_ROWS; q++) cs[q] = ldg(a.rot + (size_t)ks[q] * a.B + jc);
+#pragma unroll
+        for (int q = 0; q < BF_ROWS; q++) {
+            const int64_t l = l0 + q;
+            const R tr = fma_(xs[q].re, cs[q].re, -(xs[q].im * cs[q].im));
+            const R ti = fma_(xs[q].re, cs[q].im, xs[q].im * cs[q].re);
+            R d = distance(tr, ti);
+            if (l < 0 || l >= L) d = 0;                                // rows outside the capture only feed outputs that are forced to 0
+            R *cell = ring + slot * 64 + lane;
+            const R old = *cell;
+            *cell = d;
+            slot = slot + 1 == W ? 0 : slot + 1;
+            const int t = t0 + q, jo = t - (W - 1);                    // jo: output of this row, counted from the start of the run
+            if (jo >= 0 && jo % a.RUN == 0) {                          // (wave-uniform) direct 2N-term sum, oldest to newest
+                R ts = 0;
+                int r = slot;
+                for (int k = 0; k < W; k++) { ts += ring[r * 64 + lane]; r = r + 1 == W ? 0 : r + 1; }
+                s = ts;
+            } else {
+                s += d;
+                s -= old;
+            }
+            if (jo < 0 || t >= nrows) continue;                        // wave-uniform: no window complete yet / past the run
+            // first arg-min over the angles (dmin starts at 1000, strict `<`, :31-41)
+            R m = has_angle ? s : (R)3.0e38;
+            int best = ja;
+            for (int o = 1; o < Bp; o <<= 1) {
+                const R m2 = __shfl_xor(m, o);
+                const int b2 = __shfl_xor(best, o);
+                const bool take = (m2 < m) | ((m2 == m) & (b2 < best));
+                m = take ? m2 : m;
+                best = take ? b2 : best;
+            }
+            const int64_t i = l - N;
+            if (ja == 0 && i < L) idx2[i] = (i >= N && i < L - N && m < (R)1000.) ? best : 0;
+        }
+    }
+}
+
+// Two-stage carrier recovery of `nm` rows in HBM (phaserecovery.py:222-288): coarse search (bps_dev, unchanged), fine search, then
+// ph = unwrap(4 fine[j, idx2[j]]) / 4 over the WHOLE row - the three unwrap kernels on the table of fine angles, wrap counts as an
+// exact integer prefix sum - and Eout = E exp(j ph).  Nothing of size L x B is formed.
+template <typename R>
+int bps_twostage_recover_dev(const void *E, int nm, int64_t L, const void *angles, int A, int B, const void *symbols, int M, int N, int32_t *idx1,
+                             int32_t *idx2, void *ph, void *Eout)
+{
+    int rc = ensure_init();
+    if (rc) return rc;
+    const size_t lds = ((size_t)2 * N * 64 + 2 * BPS_MAX_LEVELS) * sizeof(R);
+    QH_REQUIRE(lds <= BPS_LDS_BUDGET, "bps_twostage: averaging window 2N does not fit the LDS ring");
+    QH_REQUIRE((int64_t)A * B <= (1 << 24), "bps_twostage: more than 2^24 fine angles");
+    void *dang = const_cast<void *>(angles);
+    if (!dang && (rc = device_grid<R>(A, &dang))) return rc;
+    if ((rc = bps_dev<R>(E, L, dang, 1, A, symbols, M, N, idx1, nm))) return rc;
+    // off[a] as numpy forms it (linspace: arange * step + start, the last entry the stop itself; then / (B A) * pi / 2), each operation rounded on its own
+    TwoStageOffsets o;
+    {
+#pragma clang fp contract(off)
+        const double start = -(double)B / 2.0, stop = (double)B / 2.0;
+        const double step = B > 1 ? (stop - start) / (double)(B - 1) : 0.0;
+        for (int k = 0; k < 64; k++) {
+            double y = (double)k * step;
+            y = y + start;
+            if (B > 1 && k == B - 1) y = stop;
+            y = y / (double)((int64_t)B * A);
+            y = y * 3.141592653589793;
+            o.off[k] = k < B ? y / 2.0 : 0.0;
+        }
+    }
+    // table of the A x B fine angles and their rotators: the next of a ring of tables of the calling thread (see the alphabet descriptors in bps_dev)
+    void *ring = nullptr, *desc = nullptr, *dchunk = nullptr;
+    static thread_local unsigned table_next = 0;
+    const size_t n_fine = ((size_t)A * B * sizeof(R) + 255) & ~(size_t)255, n_rot = ((size_t)A * B * sizeof(Cx<R>) + 255) & ~(size_t)255;
+    if ((rc = scratch(SCRATCH_TWOSTAGE, BPS_DESC_RING * (n_fine + n_rot), &ring))) return rc;
+    R *fine = (R *)((char *)ring + (size_t)(table_next++ % BPS_DESC_RING) * (n_fine + n_rot));
+    Cx<R> *rot = (Cx<R> *)((char *)fine + n_fine);
+    hipLaunchKernelGGL((twostage_table_kernel<R>), dim3((unsigned)((A * B + 255) / 256)), dim3(256), 0, g_stream, (const R *)dang, A, B, o, fine, rot);
+    if ((rc = analyse_alphabet<R>(symbols, M, &desc))) return rc;
+    BpsFineArgs<R> f;
+    f.E = (const Cx<R> *)E; f.rot = rot; f.symbols = (const Cx<R> *)symbols; f.desc = (const AlphabetDesc<R> *)desc;
+    f.idx1 = idx1; f.idx2 = idx2; f.L = L; f.B = B; f.M = M; f.N = N;
+    f.lgBp = 0;
+    while ((1 << f.lgBp) < B) f.lgBp++;
+    const int runs = 64 >> f.lgBp;                                 // runs a wave carries
+    // A lane's run is a tile of bps_kernel on a (L, B) grid, and its window sum is re-formed where that kernel starts a run of sliding sums: the
+    // same distances summed in the same order, so idx2 is what the composed path (phaserecovery.py:48-53 on bps_kernel) selects, tie for tie.
+    // (A window the tile kernel has no tile for: runs of 512 symbols, re-formed every 128.)
+    size_t tile_lds = 0;
+    int S = bps_tile<R>(B, N, &tile_lds), RUN = 128;
+    if (S >= 8) {
+        RUN = (int)(((int64_t)S * B + BPS_THREADS - 1) / BPS_THREADS);
+        if (RUN < 8) RUN = 8;
+        if (RUN > S) RUN = S;
+    } else
+        S = 512;
+    f.S = S; f.RUN = RUN;
+    static std::atomic<bool> fattr{false};
+    if (!fattr) {
+        QH_HIP(hipFuncSetAttribute((const void *)bps_fine_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BPS_LDS_BUDGET));
+        QH_HIP(hipFuncSetAttribute((const void *)bps_fine_kernel<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BPS_LDS_BUDGET));
+        fattr = true;
+    }
+    hipLaunchKernelGGL((bps_fine_kernel<R>), dim3((unsigned)((L + (int64_t)S * runs - 1) / ((int64_t)S * runs)), nm), dim3(64), lds, g_stream, f);
+    // unwrap + de-rotation
+    const int64_t nchunk = (L + UW_CHUNK - 1) / UW_CHUNK;
+    if ((rc = scratch(1, (size_t)nm * nchunk * sizeof(int), &dchunk))) return rc;
+    const UwFine<R> src{idx1, idx2, fine, L, 0, L, B};
+    hipLaunchKernelGGL((unwrap_partial_kernel<R, UwFine<R>>), dim3((unsigned)nchunk, nm), dim3(UW_THREADS), 0, g_stream, src, (int *)dchunk, nchunk);
+    hipLaunchKernelGGL(unwrap_scan_kernel, dim3(nm), dim3(1024), 0, g_stream, (int *)dchunk, nchunk);
+    hipLaunchKernelGGL((unwrap_apply_kernel<R, UwFine<R>>), dim3((unsigned)nchunk, nm), dim3(UW_THREADS), 0, g_stream, (const Cx<R> *)E, src,
+                       (const int *)dchunk, nchunk, (R *)ph, (Cx<R> *)Eout);
+    QH_HIP(hipGetLastError());
+    return QH_OK;
+}
+int bps_twostage_recover_f32(const void *E, int nm, int64_t L, const void *angles, int A, int B, const void *symbols, int M, int N, int32_t *idx1,
+                             int32_t *idx2, void *ph, void *Eout)
+{ return bps_twostage_recover_dev<float>(E, nm, L, angles, A, B, symbols, M, N, idx1, idx2, ph, Eout); }
+int bps_twostage_recover_f64(const void *E, int nm, int64_t L, const void *angles, int A, int B, const void *symbols, int M, int N, int32_t *idx1,
+                             int32_t *idx2, void *ph, void *Eout)
+{ return bps_twostage_recover_dev<double>(E, nm, L, angles, A, B, symbols, M, N, idx1, idx2, ph, Eout); }
 
 // ------------------------------------------------------------------------------------------------ select_angles
 template <typename R>

@@ -42,8 +42,16 @@ double gram_budget_gb();         // scratch the Gram tables of one call may take
 int pit_timing_mode();            // which relaxation passes of a tier-b sweep get HIP events: 0 none, 1 pass 1 (default), 2 all (qh_set_pit_timing)
 int default_tier();               // 0: tier a (exact), 1: tier b - what the drop-in host-array trainers run (qh_set_default_tier)
 double default_tier_tol();        // tolerance of the default tier b (qh_set_default_tier)
-int scratch(int slot, size_t bytes, void **p);   // grow-only device scratch, slots 0..15
+constexpr int SCRATCH_SLOTS = 17;
+constexpr int SCRATCH_TWOSTAGE = 16;             // tables of the two-stage phase search (bps.hip)
+int scratch(int slot, size_t bytes, void **p);   // grow-only device scratch, slots 0..SCRATCH_SLOTS - 1
 unsigned scratch_epoch();        // changes whenever the calling thread's scratch slots are released (contents cached in a slot are gone)
+
+// two-stage phase search on device pointers (bps.hip); the C entry points in api.hip check the arguments
+int bps_twostage_recover_f32(const void *E, int nm, int64_t L, const void *angles, int A, int B, const void *symbols, int M, int N, int32_t *idx1,
+                             int32_t *idx2, void *ph, void *Eout);
+int bps_twostage_recover_f64(const void *E, int nm, int64_t L, const void *angles, int A, int B, const void *symbols, int M, int N, int32_t *idx1,
+                             int32_t *idx2, void *ph, void *Eout);
 
 // Staging memory of the host-pointer entry points: power-of-two size classes kept in a small pool (api.hip) instead of a
 // hipMalloc / hipFree pair per call - hipFree synchronises the device, and the pilot receiver makes dozens of small calls.

@@ -36,13 +36,15 @@ class ResidentReceiver:
 
     Parameters mirror ``dual_mode_equalisation`` + ``bps``: ``mu``, ``Niter``, ``methods``, ``adaptive_stepsize`` are
     2-tuples (pass ``methods=("mcma",)`` etc. with 1-tuples for a single stage), ``Mtestangles``/``Nbps`` the BPS
-    parameters (``Mtestangles=None`` skips carrier recovery).
+    parameters (``Mtestangles=None`` skips carrier recovery).  ``Bbps=None``: single-stage search over ``Mtestangles`` angles; an integer
+    selects the two-stage search - ``Mtestangles`` coarse angles, then ``Bbps`` fine ones around each symbol's coarse estimate
+    (``hip_dsp.bps_twostage_recover_dev``; ``idx`` then holds the coarse and ``idx2`` the fine indices) - through the same calls.
     """
 
     NONFINAL_TOL_FACTOR = _host.NONFINAL_TOL_FACTOR
 
     def __init__(self, nmodes, L, os, M, Ntaps, mu, methods=("cma", "mrde"), Niter=(1, 1), adaptive_stepsize=(False, False),
-                 TrSyms=(None, None), Mtestangles=64, Nbps=20, dtype=np.complex64, alphabet=None, modes=None, tier="a", pit=None):
+                 TrSyms=(None, None), Mtestangles=64, Nbps=20, dtype=np.complex64, alphabet=None, modes=None, tier="a", pit=None, Bbps=None):
         suf, self.rt, self.ct = _lib.suffix(dtype)
         self.nmodes, self.L, self.os, self.M, self.Ntaps = int(nmodes), int(L), int(os), int(M), int(Ntaps)
         # run(overlap=True), tier b: the pending phase search in parts between the next capture's relaxation passes.  0: as many parts as the previous
@@ -61,6 +63,9 @@ class ResidentReceiver:
         self.TrSyms = tuple(_host._cal_training_symbol_len(os, Ntaps, L) if t is None else int(t) for t in TrSyms[:self.nstage])
         self.N = (self.L - self.Ntaps + 1) // self.os
         self.Mtestangles, self.Nbps = Mtestangles, Nbps
+        self.Bbps = None if Bbps is None else int(Bbps)
+        if self.Bbps is not None and not 1 <= self.Bbps <= 64:
+            raise ValueError("Bbps: 1 .. 64 fine test angles, or None for the single-stage search")
         # tier "a" (default): the reference's exact sequential recurrence.  tier "b" (opt-in): parallel-in-time training
         #  - concurrently trained segments + waveform relaxation until the boundary defect is below `tol`; the
         # first stage is a cold start (gear-shifted acquisition), later stages start from the previous stage's taps.
@@ -103,6 +108,8 @@ class ResidentReceiver:
             self.alphabet = DeviceArray.from_host(self.alphabet_host)
             self.angles = DeviceArray.from_host(_dsp.test_angle_grid(Mtestangles, self.rt))
             self.idx = DeviceArray((self.modes.size, self.N), np.int32)
+            if self.Bbps is not None:
+                self.idx2 = DeviceArray((self.modes.size, self.N), np.int32)
             self.ph = DeviceArray((self.modes.size, self.N), self.rt)
             self.out = DeviceArray((self.modes.size, self.N), self.ct)
         if tier == "b":
@@ -326,6 +333,12 @@ class ResidentReceiver:
 
     def _recover(self, part=0, nparts=1):
         self._bound()
+        if self.Bbps is not None:
+            # two stages: there is no part-wise form - whatever the number of parts, the last one is the one launch of the whole search
+            if part == nparts - 1:
+                _dsp.bps_twostage_recover_dev(self.eq, self.Mtestangles, self.Bbps, self.alphabet, self.Nbps, self.idx, self.idx2, self.ph, self.out,
+                                              angles=self.angles)
+            return
         _dsp.bps_recover_dev(self.eq, self.Mtestangles, self.alphabet, self.Nbps, self.idx, self.ph, self.out, angles=self.angles, part=part, nparts=nparts)
 
     # ------------------------------------------------------------------------------------------ the next capture's sequential prologue, ahead of time
@@ -417,7 +430,9 @@ class ResidentReceiver:
         half of the register file and most issue slots free, the phase search is a chip-wide streaming kernel of 64 registers a
         wave that fits into them (csrc/train_seg.h; stream 2 stays off 32 of the 256 compute units, csrc/api.hip).  The results of
         a pass are complete after ``wait_post()`` (enqueues what is pending; stream 0 waits for it) or ``fetch()`` (the host waits
-        too).  Bit-identical to ``overlap=False``: the same kernels on the same data, in another order.
+        too).  Bit-identical to ``overlap=False``: the same kernels on the same data, in another order.  The two-stage search (``Bbps``) has
+        no part-wise form: where the pending search would go beside the passes in parts (tier b, ``post_parts``), it goes as one launch
+        (``nparts = 1``) with the last of them.
 
         ``prefetch=True`` (tier b, consecutive captures): the acquisition and the eigenbasis of the NEXT capture are enqueued on stream 1 at the
         start of this run and adopted by the next one (``_prepare_next``); results bit-identical to ``prefetch=False``.
@@ -593,6 +608,8 @@ class ResidentReceiver:
                    mu=tuple(m.to_host()[0] for m in self.mu))
         if self.Mtestangles:
             res.update(out=self.out.to_host(), ph=self.ph.to_host(), idx=self.idx.to_host())
+            if self.Bbps is not None:
+                res.update(idx2=self.idx2.to_host())
         return res
 
     def ser(self, symbols_tx, maxlag=256, window=4096, trim=0):
@@ -637,6 +654,8 @@ class ResidentReceiver:
         train = sum(self.Niter[s] * cs * (self.nmodes * self.os + nsel) for s in range(self.nstage))
         apply_ = cs * (self.nmodes * self.os + nsel)
         bps = nsel * (cs + cs + cs // 2) if self.Mtestangles else 0
+        if self.Mtestangles and self.Bbps is not None:
+            bps += nsel * (cs + 4 + 4 + 4 + 4)     # fine stage: E and the coarse index in, the fine index out; the unwrap reads both indices
         return dict(train=train, apply=apply_, bps=bps, total=train + apply_ + bps)
 
 
@@ -800,6 +819,8 @@ class ChannelBank:
         self.eq = DeviceArray((self.nch, nsel, self.N), self.ct)
         if r.Mtestangles:
             self.idx = DeviceArray((self.nch, nsel, self.N), np.int32)
+            if r.Bbps is not None:
+                self.idx2 = DeviceArray((self.nch, nsel, self.N), np.int32)
             self.ph = DeviceArray((self.nch, nsel, self.N), self.rt)
             self.out = DeviceArray((self.nch, nsel, self.N), self.ct)
         self._gram = None
@@ -877,7 +898,10 @@ class ChannelBank:
     def _post_stages(self, r, wxy):
         for c in range(self.nch):
             _k.apply_filter_to_signal_dev(self.E.row(c), self.os, wxy.row(c), r.modes, self.eq.row(c))
-            if r.Mtestangles:
+            if r.Mtestangles and r.Bbps is not None:
+                _dsp.bps_twostage_recover_dev(self.eq.row(c), r.Mtestangles, r.Bbps, r.alphabet, r.Nbps, self.idx.row(c), self.idx2.row(c), self.ph.row(c),
+                                              self.out.row(c), angles=r.angles)
+            elif r.Mtestangles:
                 _dsp.bps_recover_dev(self.eq.row(c), r.Mtestangles, r.alphabet, r.Nbps, self.idx.row(c), self.ph.row(c), self.out.row(c), angles=r.angles)
 
     def ser(self, ch, symbols_tx, maxlag=256, window=4096, trim=0):
@@ -904,4 +928,6 @@ class ChannelBank:
                    mu=tuple(m.to_host()[ch] for m in self.mu))
         if self.rx.Mtestangles:
             res.update(out=self.out.row(ch).to_host(), ph=self.ph.row(ch).to_host(), idx=self.idx.row(ch).to_host())
+            if self.rx.Bbps is not None:
+                res.update(idx2=self.idx2.row(ch).to_host())
         return res
