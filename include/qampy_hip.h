@@ -236,6 +236,25 @@ int qh_bps_twostage_recover_c128_dev(const void *E, int nm, int64_t L, const voi
  * fo (nmodes,) in units of the symbol rate, E / out (nmodes, L) host arrays */
 int qh_comp_freq_offset_c64(const void *E, int nmodes, int64_t L, const double *fo, int os, void *out);
 int qh_comp_freq_offset_c128(const void *E, int nmodes, int64_t L, const double *fo, int os, void *out);
+/* The same with E, fo and out in DEVICE memory (fo: what qh_find_freq_offset_*_dev wrote); out == E is allowed.  Enqueued on the current stream. */
+int qh_comp_freq_offset_c64_dev(const void *E, int nmodes, int64_t L, const double *fo, int os, void *out);
+int qh_comp_freq_offset_c128_dev(const void *E, int nmodes, int64_t L, const double *fo, int os, void *out);
+/* ---- find_freq_offset (qampy/core/phaserecovery.py:385-433): blind frequency-offset estimate of every row of E (nmodes, L) from the peak of
+ *     P[k] = sum_b |FFT_N(E[row, b N : (b + 1) N] ** 4)[k]|^2,   b = 0 .. blocks - 1,   N = fft_size,
+ * a power of two from 2^8 to 2^20 (anything else: QH_ERR_ARG).  blocks = 1 is the reference's estimator: a row shorter than N is zero-padded,
+ * of a longer one the first N samples are read.  blocks > 1 (a Welch average) needs blocks * fft_size <= L.  Per row, bin = the first maximum
+ * of P; fo_out[row] = fftfreq(N, 1 / os)[bin] / 4 in units of the symbol rate, and with average != 0 every row gets the mean over the rows.
+ * stats_out (nmodes, 3), optional: bin, P[bin], sum_k P[k].  spectrum_out (nmodes, N), optional: P in the signal's real type, in bin order.
+ * Sums are formed in a fixed order without atomics: a repeated call is bit-identical.  The _dev forms take device pointers, read nothing back
+ * and are enqueued on the current stream; the others take host pointers. */
+int qh_find_freq_offset_c64_dev(const void *E, int nmodes, int64_t L, int os, int fft_size, int blocks, int average, double *fo_out, double *stats_out,
+                                void *spectrum_out);
+int qh_find_freq_offset_c128_dev(const void *E, int nmodes, int64_t L, int os, int fft_size, int blocks, int average, double *fo_out, double *stats_out,
+                                 void *spectrum_out);
+int qh_find_freq_offset_c64(const void *E, int nmodes, int64_t L, int os, int fft_size, int blocks, int average, double *fo_out, double *stats_out,
+                            void *spectrum_out);
+int qh_find_freq_offset_c128(const void *E, int nmodes, int64_t L, int os, int fft_size, int blocks, int average, double *fo_out, double *stats_out,
+                             void *spectrum_out);
 /* Tail of pilot_based_cpe_new (qampy/core/pilotbased_receiver.py:318-327): the averaged pilot phases kph (nmodes, nk) at the symbol
  * positions knots (nk, increasing) interpolated linearly to every symbol (np.interp) and taken out: out = E exp(-1j trace); trace in the
  * signal's complex dtype like the reference returns it.  Host arrays. */

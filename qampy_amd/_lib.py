@@ -32,6 +32,7 @@ _DECIDE = [_vp, _i64, _vp, _i, _vp, _vp, _vp]
 _LLR = [_vp, _i64, _i, C.c_double, _vp, _i, _vp]
 _CD = [_vp, _i, _i64, _i, C.c_double, C.c_double, C.c_double, _i, _vp]      # E, nmodes, L, N, c2, c1, c0, mode, out
 _RESAMPLE = [_vp, _i, _i64, _vp, _i, _i, _i, C.c_double, _i64, _vp]                  # E, nmodes, L, h (host), ntaps, up, down, gain, Lout, out
+_FOE = [_vp, _i, _i64, _i, _i, _i, _i, _vp, _vp, _vp]       # E, nmodes, L, os, fft_size, blocks, average, fo_out, stats_out, spectrum_out
 _ALIGNED = [_vp, _i64, _vp, _i64, _vp, _i, _i, _i64, _i64]          # row, N, idx_tx, ntx, alphabet, M, rot, lag, trim
 
 
@@ -77,6 +78,8 @@ SIGNATURES = {
     "qh_bps_recover_part_c64_dev": _RECOVER + [_i, _i], "qh_bps_recover_part_c128_dev": _RECOVER + [_i, _i],
     "qh_bps_twostage_recover_c64_dev": _TWOSTAGE, "qh_bps_twostage_recover_c128_dev": _TWOSTAGE,
     "qh_comp_freq_offset_c64": [_vp, _i, _i64, _vp, _i, _vp], "qh_comp_freq_offset_c128": [_vp, _i, _i64, _vp, _i, _vp],
+    "qh_comp_freq_offset_c64_dev": [_vp, _i, _i64, _vp, _i, _vp], "qh_comp_freq_offset_c128_dev": [_vp, _i, _i64, _vp, _i, _vp],
+    "qh_find_freq_offset_c64": _FOE, "qh_find_freq_offset_c128": _FOE, "qh_find_freq_offset_c64_dev": _FOE, "qh_find_freq_offset_c128_dev": _FOE,
     "qh_pilot_phase_trace_c64": [_vp, _i, _i64, _vp, _vp, _i, _vp, _vp], "qh_pilot_phase_trace_c128": [_vp, _i, _i64, _vp, _vp, _i, _vp, _vp],
     "qh_cd_filter_c64": _CD, "qh_cd_filter_c128": _CD, "qh_cd_filter_c64_dev": _CD, "qh_cd_filter_c128_dev": _CD,
     "qh_resample_c64": _RESAMPLE, "qh_resample_c128": _RESAMPLE, "qh_resample_c64_dev": _RESAMPLE, "qh_resample_c128_dev": _RESAMPLE,

@@ -212,6 +212,92 @@ def comp_freq_offset(E, freq_offset, os=1):
     return out
 
 
+def comp_freq_offset_dev(E, fo, os, out):
+    """:func:`comp_freq_offset` with everything in HBM: E, out (nmodes, L) complex DeviceArrays - the same buffer for removal in place -
+    and ``fo`` the (nmodes,) float64 DeviceArray :func:`find_freq_offset_dev` wrote.  Enqueued on the current library stream."""
+    suf, rt, ct = _lib.suffix(E.dtype)
+    if len(E.shape) != 2 or np.dtype(E.dtype) != ct:
+        raise TypeError("comp_freq_offset_dev works on a 2-d complex array")
+    if tuple(out.shape) != tuple(E.shape) or np.dtype(out.dtype) != np.dtype(E.dtype):
+        raise ValueError("out must have E's shape and dtype")
+    if np.dtype(fo.dtype) != np.float64 or int(np.prod(fo.shape)) != E.shape[0]:
+        raise ValueError("fo: one float64 offset per mode")
+    _lib.call("qh_comp_freq_offset_c" + ("64" if suf == "32" else "128") + "_dev", E.ptr, E.shape[0], E.shape[1], fo.ptr, int(os), out.ptr)
+
+
+# ------------------------------------------------------------------------------------------------ blind frequency-offset estimate
+FOE_NMIN, FOE_NMAX = 2 ** 8, 2 ** 20          # transform sizes of csrc/foe.hip
+
+
+def foe_plan(L, fft_size, blocks=1):
+    """``(N, B)`` of a frequency-offset estimate over rows of ``L`` samples, checked on the host: ``fft_size`` rounded up to a power of two
+    as the reference rounds it (qampy/core/phaserecovery.py:414-415), ``blocks`` an integer or ``"all"`` (``max(1, L // N)``).  ValueError for
+    a size outside ``2**8 .. 2**20``, for ``blocks < 1`` and for more than one block with ``blocks * N > L``."""
+    if not fft_size >= 1:
+        raise ValueError("fft_size must be positive")
+    N = 2 ** int(np.ceil(np.log2(fft_size)))
+    if not FOE_NMIN <= N <= FOE_NMAX:
+        raise ValueError("fft_size %d (rounded up to a power of two) is outside %d .. %d" % (N, FOE_NMIN, FOE_NMAX))
+    L = int(L)
+    if L < 1:
+        raise ValueError("an empty signal has no frequency offset")
+    if isinstance(blocks, str):
+        if blocks != "all":
+            raise ValueError("blocks is an integer or 'all'")
+        return N, max(1, L // N)
+    B = int(blocks)
+    if B != blocks or B < 1:
+        raise ValueError("blocks is a positive integer or 'all'")
+    if B > 1 and B * N > L:
+        raise ValueError("%d blocks of %d samples do not fit a signal of %d" % (B, N, L))
+    return N, B
+
+
+def _foe_os(os):
+    if int(os) != os or os < 1:
+        raise ValueError("the device estimator takes a whole number of samples per symbol")
+    return int(os)
+
+
+def find_freq_offset_dev(E, os, fft_size, blocks, average_over_modes, fo, stats=None, spectrum=None):
+    """
+    Blind frequency-offset estimate of every row of the (nmodes, L) complex DeviceArray ``E`` in HBM (csrc/foe.hip): the peak of
+    ``sum_b |FFT_N(E[row, b N:(b + 1) N] ** 4)|**2`` over ``blocks`` blocks of ``N = fft_size`` samples (see :func:`foe_plan`), divided by 4,
+    on numpy's ``fftfreq(N, 1 / os)`` grid, written to the (nmodes,) float64 DeviceArray ``fo`` - the mean over the rows in every entry with
+    ``average_over_modes``.  Optional DeviceArrays: ``stats`` (nmodes, 3) float64 - bin, peak power, total power - and ``spectrum``
+    (nmodes, N) in the signal's real type.  Nothing is read back; enqueued on the current library stream.
+    """
+    suf, rt, ct = _lib.suffix(E.dtype)
+    if len(E.shape) != 2 or np.dtype(E.dtype) != ct:
+        raise TypeError("find_freq_offset_dev works on a 2-d complex array")
+    nm, L = E.shape
+    N, B = foe_plan(L, fft_size, blocks)
+    os = _foe_os(os)
+    if np.dtype(fo.dtype) != np.float64 or int(np.prod(fo.shape)) != nm:
+        raise ValueError("fo: one float64 offset per mode")
+    if stats is not None and (np.dtype(stats.dtype) != np.float64 or tuple(stats.shape) != (nm, 3)):
+        raise ValueError("stats must be (nmodes, 3) float64")
+    if spectrum is not None and (np.dtype(spectrum.dtype) != rt or tuple(spectrum.shape) != (nm, N)):
+        raise ValueError("spectrum must be (nmodes, %d) %s" % (N, np.dtype(rt).name))
+    _lib.call("qh_find_freq_offset_c" + ("64" if suf == "32" else "128") + "_dev", E.ptr, nm, L, os, N, B, int(bool(average_over_modes)), fo.ptr,
+              stats.ptr if stats is not None else None, spectrum.ptr if spectrum is not None else None)
+
+
+def find_freq_offset(E, os=1, fft_size=2 ** 16, blocks=1, average_over_modes=True):
+    """:func:`find_freq_offset_dev` for a host array: ``E (nmodes, L)`` up, the (nmodes,) float64 offsets back."""
+    E = np.asarray(E)
+    if E.ndim != 2 or not np.iscomplexobj(E):
+        raise TypeError("find_freq_offset works on a 2-d complex array")
+    suf, rt, ct = _lib.suffix(E.dtype)
+    N, B = foe_plan(E.shape[1], fft_size, blocks)
+    os = _foe_os(os)
+    E = np.ascontiguousarray(E)
+    fo = np.zeros(E.shape[0], dtype=np.float64)
+    _lib.call("qh_find_freq_offset_c" + ("64" if suf == "32" else "128"), _lib.ptr(E), E.shape[0], E.shape[1], os, N, B, int(bool(average_over_modes)),
+              _lib.ptr(fo), None, None)
+    return fo
+
+
 def pilot_phase_trace(E, knots, knot_phase):
     """Linear interpolation of the pilot phases ``knot_phase (nmodes, nk)`` at the symbol positions ``knots`` to every symbol of ``E
     (nmodes, L)`` (np.interp) and its removal, on the device: ``(E * exp(-1j trace), trace)``, the trace in E's complex dtype as the

@@ -68,11 +68,24 @@ def bps_twostage(E, Mtestangles, symbols, N, B=4, method="pyt", **kwargs):
     return (out.flatten(), ph.flatten()) if E.ndim == 1 else (out, ph)
 
 
-def find_freq_offset(sig, os=1, average_over_modes=True, fft_size=2 ** 16):
+def find_freq_offset(sig, os=1, average_over_modes=True, fft_size=2 ** 16, method="pyt", blocks=1):
     """
     Blind frequency-offset estimate from the spectral peak of the signal raised to the 4th power, in units of the symbol
     rate (qampy/core/phaserecovery.py:385-433).  Host-side FFT (the pilot receiver calls it on a few thousand symbols).
+
+    method : "pyt" - the host FFT below, the default - or "hip": the device estimator (``hip_dsp.find_freq_offset``; ``fft_size`` from
+    ``2**8`` to ``2**20`` after rounding, complex64 / complex128 input, the reference's ``(nmodes, 1)`` float64 result).
+    blocks : "hip" only - the spectrum is summed over that many consecutive blocks of ``fft_size`` samples (``"all"``: as many as the signal
+    holds) before the peak is taken; 1 is the reference's estimator.
     """
+    if method.lower() not in ("pyt", "hip"):
+        raise ValueError("Method needs to be 'pyt' or 'hip'")
+    if method.lower() == "hip":
+        rows = np.atleast_2d(sig)
+        _dsp.foe_plan(rows.shape[1], fft_size, blocks)                  # argument errors before the device is touched
+        return _dsp.find_freq_offset(np.asarray(rows), os, fft_size, blocks, average_over_modes).reshape(-1, 1)
+    if blocks != 1:
+        raise ValueError("the host estimator takes one block: blocks=%r needs method='hip'" % (blocks,))
     if not ((np.log2(fft_size) % 2 == 0) | (np.log2(fft_size) % 2 == 1)):
         fft_size = 2 ** (int(np.ceil(np.log2(fft_size))))
     sig = np.atleast_2d(sig)

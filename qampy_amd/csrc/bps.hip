@@ -1260,6 +1260,19 @@ template <typename R> int comp_freq_offset_host(const void *E, int nmodes, int64
     QH_HIP(hipStreamSynchronize(g_stream));
     return QH_OK;
 }
+// the same on device pointers, the offsets included (what find_freq_offset_dev leaves in HBM): nothing crosses to the host.  out == E is
+// allowed - every thread reads the one element it writes
+template <typename R> int comp_freq_offset_dev(const void *E, int nmodes, int64_t L, const double *fo, int os, void *out)
+{
+    int rc = ensure_init();
+    if (rc) return rc;
+    QH_REQUIRE(nmodes >= 1 && nmodes <= 65535 && L >= 0 && (L + 255) / 256 <= 0x7fffffffLL && os >= 1, "comp_freq_offset: bad sizes");
+    if (L == 0) return QH_OK;
+    QH_REQUIRE(E && fo && out, "comp_freq_offset: E, fo and out must be given");
+    hipLaunchKernelGGL((comp_freq_offset_kernel<R>), dim3((unsigned)((L + 255) / 256), nmodes), dim3(256), 0, g_stream, (const Cx<R> *)E, L, fo, os, (Cx<R> *)out);
+    QH_HIP(hipGetLastError());
+    return QH_OK;
+}
 
 // Pilot-aided phase trace (qampy/core/pilotbased_receiver.py:258-327, the tail of pilot_based_cpe_new): the averaged pilot phases
 // knot_phase[k, j] at the symbol positions knots[j] (increasing) are interpolated linearly to every symbol - np.interp: constant before the
@@ -1357,6 +1370,10 @@ int qh_comp_freq_offset_c64(const void *E, int nmodes, int64_t L, const double *
 { return qh::comp_freq_offset_host<float>(E, nmodes, L, fo, os, out); }
 int qh_comp_freq_offset_c128(const void *E, int nmodes, int64_t L, const double *fo, int os, void *out)
 { return qh::comp_freq_offset_host<double>(E, nmodes, L, fo, os, out); }
+int qh_comp_freq_offset_c64_dev(const void *E, int nmodes, int64_t L, const double *fo, int os, void *out)
+{ return qh::comp_freq_offset_dev<float>(E, nmodes, L, fo, os, out); }
+int qh_comp_freq_offset_c128_dev(const void *E, int nmodes, int64_t L, const double *fo, int os, void *out)
+{ return qh::comp_freq_offset_dev<double>(E, nmodes, L, fo, os, out); }
 int qh_pilot_phase_trace_c64(const void *E, int nmodes, int64_t L, const int64_t *knots, const double *kph, int nk, void *out, void *trace)
 { return qh::pilot_phase_trace_host<float>(E, nmodes, L, knots, kph, nk, out, trace); }
 int qh_pilot_phase_trace_c128(const void *E, int nmodes, int64_t L, const int64_t *knots, const double *kph, int nk, void *out, void *trace)

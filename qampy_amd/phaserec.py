@@ -18,9 +18,10 @@ def bps_twostage(E, Mtestangles, N, B=4, **kwargs):
     return core.phaserecovery.bps_twostage(E, Mtestangles, E.coded_symbols, N, B=B, **kwargs)
 
 
-def find_freq_offset(sig, average_over_modes=False, fft_size=4096):
-    """Frequency offset from the spectrum of the signal raised to the 4th power (qampy/phaserec.py:94-116)."""
-    return core.phaserecovery.find_freq_offset(sig, sig.os, average_over_modes=average_over_modes, fft_size=fft_size)
+def find_freq_offset(sig, average_over_modes=False, fft_size=4096, method="pyt", blocks=1):
+    """Frequency offset from the spectrum of the signal raised to the 4th power (qampy/phaserec.py:94-116); ``method`` and ``blocks`` as in
+    :func:`qampy_amd.core.phaserecovery.find_freq_offset`."""
+    return core.phaserecovery.find_freq_offset(sig, sig.os, average_over_modes=average_over_modes, fft_size=fft_size, method=method, blocks=blocks)
 
 
 def comp_freq_offset(sig, freq_offset):

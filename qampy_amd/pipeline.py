@@ -162,6 +162,34 @@ class ResidentReceiver:
         if getattr(self, "_prep", None) is not None:
             self.invalidate()
 
+    def compensate_foe(self, fft_size=2 ** 16, blocks="all", average_over_modes=True, next_capture=False):
+        """Estimate the frequency offset of the loaded capture in HBM (``self.E``, or ``self.E_next`` with ``next_capture``) at the receiver's
+        ``os`` and take it out in place: ``hip_dsp.find_freq_offset_dev`` and ``comp_freq_offset_dev``, enqueued on stream 0 between
+        ``load()`` / ``load_next()`` (or ``compensate_cd``) and ``run()``, with no read-back between them.  ``fft_size`` and ``blocks`` as in
+        ``hip_dsp.foe_plan`` (``"all"``: the spectrum averaged over every whole block of the capture).  The rotation leaves the power as it
+        is, so tier b's acquisition rule still holds.  The offsets and the peak statistics stay on the device: :attr:`foe` reads them."""
+        buf = getattr(self, "E_next", None) if next_capture else self.E
+        if buf is None:
+            raise ValueError("no capture loaded for next_capture=True (load_next first)")
+        N, B = _dsp.foe_plan(self.L, fft_size, blocks)
+        self._filter_done()                        # (a filter on stream 2 may still be reading the buffer)
+        if getattr(self, "_foe_fo", None) is None:
+            self._foe_fo = DeviceArray((self.nmodes,), np.float64, zero=True)
+            self._foe_stats = DeviceArray((self.nmodes, 3), np.float64, zero=True)
+        _dsp.find_freq_offset_dev(buf, self.os, N, B, average_over_modes, self._foe_fo, stats=self._foe_stats)
+        _dsp.comp_freq_offset_dev(buf, self._foe_fo, self.os, buf)
+        if getattr(self, "_prep", None) is not None:
+            self.invalidate()
+
+    @property
+    def foe(self):
+        """``(offset[nmodes], stats[nmodes, 3])`` of the last :meth:`compensate_foe`, read back after a sync: the offset taken out of every
+        mode in units of the symbol rate, and per mode the peak's bin, its power and the total power of the fourth-power spectrum."""
+        if getattr(self, "_foe_fo", None) is None:
+            raise ValueError("compensate_foe has not run")
+        _lib.sync()
+        return self._foe_fo.to_host(), self._foe_stats.to_host()
+
     def load_resampled(self, E_raw, fs_in, beta=None, taps=4001, fftconv=True, next_capture=False, fs=None):
         """Load a capture that arrives at the converter's rate: the raw rows ``E_raw`` (nmodes, Lin) at ``fs_in`` go to HBM, are resampled there
         to the receiver's rate ``fs`` (``os`` samples per symbol; keyword, or the attribute ``self.fs``) into ``self.E`` (``self.E_next`` with
