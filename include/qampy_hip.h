@@ -272,6 +272,43 @@ int qh_cd_filter_c128(const void *E, int nmodes, int64_t L, int N, double c2, do
 int qh_cd_filter_c64_dev(const void *E, int nmodes, int64_t L, int N, double c2, double c1, double c0, int mode, void *out);
 int qh_cd_filter_c128_dev(const void *E, int nmodes, int64_t L, int N, double c2, double c1, double c0, int mode, void *out);
 
+/* ---- channel impairments on a resident field (qampy/core/impairments.py:29-328; csrc/impair.hip).
+ * qh_impair_pointwise: out[m, n] = E[m, n] exp(j (phi[m, n] + 2 pi n freq)) + sigma w[m, n], every term optional, E / out (nmodes, L), out == E
+ * allowed.  w: complex Gaussian noise of unit variance split over I and Q, Philox4x32-10 keyed by `seed` with the counter (n low, n high,
+ * mode, 2) - a draw depends on (seed, mode, n) only; complex64 draws in float with the fast intrinsics, complex128 from 53-bit uniforms in
+ * double.  noise_mode 0: no noise; 1: sigma = noise; 2: sigma = noise sqrt(mean |E|^2) with the mean over ALL modes, reduced on the device
+ * (change_snr: noise = 10^(-snr / 20) sqrt(fs / fb)).  have_phase: phi is a Wiener process per mode, increments N(0, phase_var) from counter
+ * stream 1, accumulated like np.cumsum in double; trace (nmodes, L) doubles, optional, receives phi.  have_freq: freq in turns per sample
+ * (fo / fs), n freq reduced modulo one turn in double.  At most three dependent launches; no atomics, a repeated call is bit-identical.
+ * The _dev forms take device pointers, read nothing back and are enqueued on the current stream; the others take host pointers. */
+int qh_impair_pointwise_c64_dev(const void *E, int nmodes, int64_t L, int noise_mode, double noise, int have_phase, double phase_var, int have_freq,
+                                double freq, uint64_t seed, double *trace, void *out);
+int qh_impair_pointwise_c128_dev(const void *E, int nmodes, int64_t L, int noise_mode, double noise, int have_phase, double phase_var, int have_freq,
+                                 double freq, uint64_t seed, double *trace, void *out);
+int qh_impair_pointwise_c64(const void *E, int nmodes, int64_t L, int noise_mode, double noise, int have_phase, double phase_var, int have_freq, double freq,
+                            uint64_t seed, double *trace, void *out);
+int qh_impair_pointwise_c128(const void *E, int nmodes, int64_t L, int noise_mode, double noise, int have_phase, double phase_var, int have_freq, double freq,
+                             uint64_t seed, double *trace, void *out);
+/* The phase alone: out (nmodes, L) doubles in DEVICE memory receives the Wiener process of qh_impair_pointwise (cumulative != 0) or its raw
+ * increments (cumulative == 0), drawn as the complex64 (_c64) or the complex128 (_c128) pass draws them. */
+int qh_phase_noise_c64_dev(double *out, int nmodes, int64_t L, double phase_var, uint64_t seed, int cumulative);
+int qh_phase_noise_c128_dev(double *out, int nmodes, int64_t L, double phase_var, uint64_t seed, int cumulative);
+/* rotate_field: out = [[cos, -sin], [sin, cos]] E for the two rows of E (2, L); nmodes != 2 is QH_ERR_ARG; out == E allowed. */
+int qh_rotate_field_c64_dev(const void *E, int nmodes, int64_t L, double theta, void *out);
+int qh_rotate_field_c128_dev(const void *E, int nmodes, int64_t L, double theta, void *out);
+/* apply_PMD_to_field: R(-theta) diag(H, conj H) R(theta) E with H = exp(-j w dgd / 2), dgd in SAMPLES (t_dgd fs), w the digital angular
+ * frequency of the block's fftfreq grid.  L a power of two from 256 to 8192: one exact circular transform per row; any other L:
+ * overlap-save with blocks of 8192 (4096 kept, 2048 of halo on each side, the input taken modulo L), which truncates the tail of a
+ * fractional delay.  nmodes != 2 is QH_ERR_ARG; out must not alias E.  Two launches. */
+int qh_apply_pmd_c64_dev(const void *E, int nmodes, int64_t L, double theta, double dgd, void *out);
+int qh_apply_pmd_c128_dev(const void *E, int nmodes, int64_t L, double theta, double dgd, void *out);
+int qh_apply_pmd_c64(const void *E, int nmodes, int64_t L, double theta, double dgd, void *out);
+int qh_apply_pmd_c128(const void *E, int nmodes, int64_t L, double theta, double dgd, void *out);
+/* add_modal_delay: row m of out is row m of E rolled by delays[m] whole samples (np.roll); delays (nmodes,) in HOST memory; out must not
+ * alias E.  Two copies per row on the current stream. */
+int qh_modal_delay_c64_dev(const void *E, int nmodes, int64_t L, const int64_t *delays, void *out);
+int qh_modal_delay_c128_dev(const void *E, int nmodes, int64_t L, const int64_t *delays, void *out);
+
 /* ---- polyphase resampling (qampy/core/resample.py:37-127 resample_poly / rrcos_resample, qampy/core/filter.py:177-212 rrcos_pulseshaping):
  * every row of E (nmodes, L) through the rational polyphase FIR
  *     out[k] = gain * sum_m h[k down + (ntaps - 1) / 2 - m up] E[m],   k = 0 .. Lout - 1,   E zero outside the row,

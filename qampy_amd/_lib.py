@@ -33,6 +33,8 @@ _LLR = [_vp, _i64, _i, C.c_double, _vp, _i, _vp]
 _CD = [_vp, _i, _i64, _i, C.c_double, C.c_double, C.c_double, _i, _vp]      # E, nmodes, L, N, c2, c1, c0, mode, out
 _RESAMPLE = [_vp, _i, _i64, _vp, _i, _i, _i, C.c_double, _i64, _vp]                  # E, nmodes, L, h (host), ntaps, up, down, gain, Lout, out
 _FOE = [_vp, _i, _i64, _i, _i, _i, _i, _vp, _vp, _vp]       # E, nmodes, L, os, fft_size, blocks, average, fo_out, stats_out, spectrum_out
+_IMPAIR = [_vp, _i, _i64, _i, C.c_double, _i, C.c_double, _i, C.c_double, C.c_uint64, _vp, _vp]    # E, nmodes, L, noise_mode, noise, have_phase, var, have_freq, freq, seed, trace, out
+_PMD = [_vp, _i, _i64, C.c_double, C.c_double, _vp]                 # E, nmodes, L, theta, dgd (samples), out
 _ALIGNED = [_vp, _i64, _vp, _i64, _vp, _i, _i, _i64, _i64]          # row, N, idx_tx, ntx, alphabet, M, rot, lag, trim
 
 
@@ -82,6 +84,11 @@ SIGNATURES = {
     "qh_find_freq_offset_c64": _FOE, "qh_find_freq_offset_c128": _FOE, "qh_find_freq_offset_c64_dev": _FOE, "qh_find_freq_offset_c128_dev": _FOE,
     "qh_pilot_phase_trace_c64": [_vp, _i, _i64, _vp, _vp, _i, _vp, _vp], "qh_pilot_phase_trace_c128": [_vp, _i, _i64, _vp, _vp, _i, _vp, _vp],
     "qh_cd_filter_c64": _CD, "qh_cd_filter_c128": _CD, "qh_cd_filter_c64_dev": _CD, "qh_cd_filter_c128_dev": _CD,
+    "qh_impair_pointwise_c64": _IMPAIR, "qh_impair_pointwise_c128": _IMPAIR, "qh_impair_pointwise_c64_dev": _IMPAIR, "qh_impair_pointwise_c128_dev": _IMPAIR,
+    "qh_phase_noise_c64_dev": [_vp, _i, _i64, C.c_double, C.c_uint64, _i], "qh_phase_noise_c128_dev": [_vp, _i, _i64, C.c_double, C.c_uint64, _i],
+    "qh_rotate_field_c64_dev": [_vp, _i, _i64, C.c_double, _vp], "qh_rotate_field_c128_dev": [_vp, _i, _i64, C.c_double, _vp],
+    "qh_apply_pmd_c64": _PMD, "qh_apply_pmd_c128": _PMD, "qh_apply_pmd_c64_dev": _PMD, "qh_apply_pmd_c128_dev": _PMD,
+    "qh_modal_delay_c64_dev": [_vp, _i, _i64, _vp, _vp], "qh_modal_delay_c128_dev": [_vp, _i, _i64, _vp, _vp],
     "qh_resample_c64": _RESAMPLE, "qh_resample_c128": _RESAMPLE, "qh_resample_c64_dev": _RESAMPLE, "qh_resample_c128_dev": _RESAMPLE,
     "qh_row_moments_c64_dev": [_vp, _i, _i64, _vp], "qh_row_moments_c128_dev": [_vp, _i, _i64, _vp],
     "qh_center_scale_c64_dev": [_vp, _i, _i64, _vp, _vp, C.c_double], "qh_center_scale_c128_dev": [_vp, _i, _i64, _vp, _vp, C.c_double],

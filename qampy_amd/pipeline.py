@@ -140,6 +140,7 @@ class ResidentReceiver:
         if self.tier == "b":
             npow = min(self.L, 4096)
             power = float(np.mean(np.abs(E[:, :npow].astype(np.complex128)) ** 2))
+            self._load_power = power                   # (impair(snr=...) scales it)
             for s_, o in enumerate(self.pit):
                 if o.get("acquire") and not self.adaptive[s_] and not o.get("_acq_chunk_user"):
                     o["acq_chunk"] = self._acq_chunk_rule(power, float(self.mu0[s_]), o)
@@ -180,6 +181,47 @@ class ResidentReceiver:
         _dsp.comp_freq_offset_dev(buf, self._foe_fo, self.os, buf)
         if getattr(self, "_prep", None) is not None:
             self.invalidate()
+
+    def impair(self, fs, snr=None, freq_off=None, lwdth=None, dgd=None, theta=np.pi / 3.731, modal_delay=None, seed=0, source=None,
+               next_capture=False, power=None):
+        """Impair the loaded capture in HBM (``self.E``, or ``self.E_next`` with ``next_capture``) in place, between ``load()`` / ``load_next()``
+        and ``run()``: ``hip_dsp.simulate_transmission_dev`` at the sampling rate ``fs`` (symbol rate ``fs / os``) - phase noise of linewidth
+        ``lwdth``, carrier offset ``freq_off``, noise to the SNR ``snr`` (dB), ``modal_delay``, PMD of ``dgd`` seconds at ``theta`` - enqueued on
+        stream 0 with nothing read back; the noise is a function of ``seed``.  ``source``: a resident (nmodes, L) DeviceArray holding a clean
+        field, which is read instead and left as it is - the capture buffer receives its impaired copy, so one clean capture serves a whole
+        sweep without crossing PCIe.
+
+        Every stage but the noise keeps the power.  Tier b with ``snr``: the acquisition chunk of a cold stage is re-derived by the rule of
+        ``load()`` from the clean power times ``hip_dsp.snr_power_factor(snr, os)``.  The clean power is ``power`` if given, else what the
+        last ``load()`` read - with ``source`` that is the power of whatever ``load()`` saw last, so give ``power`` (the mean ``|source|**2``)
+        unless the source is a copy of that capture; with neither, ValueError.  The factor is applied to the clean power, not compounded:
+        impair a loaded capture once."""
+        buf = getattr(self, "E_next", None) if next_capture else self.E
+        if buf is None:
+            raise ValueError("no capture loaded for next_capture=True (load_next first)")
+        src = buf if source is None else source
+        if tuple(src.shape) != (self.nmodes, self.L) or np.dtype(src.dtype) != np.dtype(self.ct):
+            raise ValueError("source must be a (%d, %d) %s DeviceArray" % (self.nmodes, self.L, np.dtype(self.ct).name))
+        if source is not None and source.ptr == buf.ptr:
+            raise ValueError("source is the capture buffer itself: leave it out to impair in place")
+        clean = power
+        if self.tier == "b" and snr is not None and not next_capture:
+            clean = getattr(self, "_load_power", None) if power is None else float(power)
+            if clean is None:
+                raise ValueError("tier b needs the clean capture's power for its acquisition rule: power=..., or load() first")
+        self._filter_done()                        # (a filter on stream 2 may still be reading the buffer)
+        if (modal_delay is not None or dgd is not None) and getattr(self, "_cd_buf", None) is None:
+            self._cd_buf = DeviceArray((self.nmodes, self.L), self.ct)
+        _dsp.simulate_transmission_dev(src, buf, fs / self.os, fs, snr=snr, freq_off=freq_off, lwdth=lwdth, dgd=dgd, theta=theta, modal_delay=modal_delay,
+                                       seed=seed, tmp=getattr(self, "_cd_buf", None))
+        if getattr(self, "_prep", None) is not None:
+            self.invalidate()
+        if self.tier == "b" and snr is not None and not next_capture:
+            noisy = clean * _dsp.snr_power_factor(snr, self.os)
+            for s_, o in enumerate(self.pit):
+                if o.get("acquire") and not self.adaptive[s_] and not o.get("_acq_chunk_user"):
+                    o["acq_chunk"] = self._acq_chunk_rule(noisy, float(self.mu0[s_]), o)
+                    self._acq_asked[s_] = True
 
     @property
     def foe(self):
