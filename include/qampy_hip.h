@@ -309,6 +309,37 @@ int qh_apply_pmd_c128(const void *E, int nmodes, int64_t L, double theta, double
 int qh_modal_delay_c64_dev(const void *E, int nmodes, int64_t L, const int64_t *delays, void *out);
 int qh_modal_delay_c128_dev(const void *E, int nmodes, int64_t L, const int64_t *delays, void *out);
 
+/* ---- transmitter response on a resident field (qampy/core/impairments.py:370-671, qampy/core/filter.py:86-147; csrc/txresp.hip).  All
+ * entry points below work on (nmodes, L) complex fields in DEVICE memory, enqueue on the calling thread's current stream, read nothing back
+ * and do not synchronise; out == E is allowed everywhere.
+ * qh_row_extrema: ext[2 m] = max |re|, ext[2 m + 1] = max |im| of row m, doubles in DEVICE memory; 1 to 1024 modes, L >= 1.  Two launches,
+ * bit-reproducible. */
+int qh_row_extrema_c64_dev(const void *E, int nmodes, int64_t L, double *ext);
+int qh_row_extrema_c128_dev(const void *E, int nmodes, int64_t L, double *ext);
+/* The DAC's point-wise part, stages a mask of 1 (clip), 2 (quantise), 4 (ENOB noise), applied in that order (sim_DAC_response):
+ *   clip      every row scaled to +-1 / clip_rat by its own maximum max(max |re|, max |im|), re and im clamped to +-1
+ *   quantise  every row scaled to +-1 by its own maximum; level index = number of thresholds -1 + k d, k = 1 .. 2^bits - 1, d = 2 / 2^bits,
+ *             that are <= the value; out = (-1 + d / 2 + index d) times the maximum over ALL rows of the quantiser's input (1 to 16 bits)
+ *   noise     sigma = sqrt(2 (x_max / 2^(enob - 1))^2 / 12), x_max over all rows of this stage's input, added as
+ *             qh_impair_pointwise(noise_mode 1, sigma, seed) adds it
+ * ext: the row extrema of E (qh_row_extrema), or NULL: formed here (two more launches).  stages = 0 copies E to out. */
+int qh_dac_pointwise_c64_dev(const void *E, int nmodes, int64_t L, const double *ext, int stages, double clip_rat, int quant_bits, double enob, uint64_t seed,
+                             void *out);
+int qh_dac_pointwise_c128_dev(const void *E, int nmodes, int64_t L, const double *ext, int stages, double clip_rat, int quant_bits, double enob, uint64_t seed,
+                              void *out);
+/* scipy.signal.sosfilt(sos, E, axis=-1) with zero initial state, every row on its own, exact and parallel in time.  sos: nsec (1 to 4) rows
+ * of b0 b1 b2 a0 a1 a2 with a0 = 1, doubles in HOST memory.  P: the (2 nsec) x (2 nsec) matrix, row-major doubles in HOST memory, that maps
+ * the cascade's state (z0, z1 of section 0, then of section 1, ...) over *chunk zero-input samples (qh_sos_geometry).  Coefficients and state
+ * are double in both precisions.  Three launches (one for L <= *tile). */
+int qh_sosfilt_c64_dev(const void *E, int nmodes, int64_t L, const double *sos, int nsec, const double *P, void *out);
+int qh_sosfilt_c128_dev(const void *E, int nmodes, int64_t L, const double *sos, int nsec, const double *P, void *out);
+/* Samples per lane (*chunk) and per workgroup (*tile) of qh_sosfilt; either pointer may be NULL.  No device needed. */
+int qh_sos_geometry(int *chunk, int *tile);
+/* ideal_amplifier_response (have_amp != 0: x / max * tgt_v, the maximum over all rows from ext, or formed here when ext is NULL), then
+ * modulator_response.  prm: 8 doubles in HOST memory - dcbias (I, Q), gfactr (I, Q), cfactr (I, Q), dcbias_out, gfactr_out. */
+int qh_modulator_c64_dev(const void *E, int nmodes, int64_t L, const double *ext, int have_amp, double tgt_v, const double *prm, void *out);
+int qh_modulator_c128_dev(const void *E, int nmodes, int64_t L, const double *ext, int have_amp, double tgt_v, const double *prm, void *out);
+
 /* ---- polyphase resampling (qampy/core/resample.py:37-127 resample_poly / rrcos_resample, qampy/core/filter.py:177-212 rrcos_pulseshaping):
  * every row of E (nmodes, L) through the rational polyphase FIR
  *     out[k] = gain * sum_m h[k down + (ntaps - 1) / 2 - m up] E[m],   k = 0 .. Lout - 1,   E zero outside the row,

@@ -35,6 +35,8 @@ _RESAMPLE = [_vp, _i, _i64, _vp, _i, _i, _i, C.c_double, _i64, _vp]             
 _FOE = [_vp, _i, _i64, _i, _i, _i, _i, _vp, _vp, _vp]       # E, nmodes, L, os, fft_size, blocks, average, fo_out, stats_out, spectrum_out
 _IMPAIR = [_vp, _i, _i64, _i, C.c_double, _i, C.c_double, _i, C.c_double, C.c_uint64, _vp, _vp]    # E, nmodes, L, noise_mode, noise, have_phase, var, have_freq, freq, seed, trace, out
 _PMD = [_vp, _i, _i64, C.c_double, C.c_double, _vp]                 # E, nmodes, L, theta, dgd (samples), out
+_DAC = [_vp, _i, _i64, _vp, _i, C.c_double, _i, C.c_double, C.c_uint64, _vp]      # E, nmodes, L, ext, stages, clip_rat, quant_bits, enob, seed, out
+_MOD = [_vp, _i, _i64, _vp, _i, C.c_double, _vp, _vp]                            # E, nmodes, L, ext, have_amp, tgt_v, prm (host), out
 _ALIGNED = [_vp, _i64, _vp, _i64, _vp, _i, _i, _i64, _i64]          # row, N, idx_tx, ntx, alphabet, M, rot, lag, trim
 
 
@@ -89,6 +91,11 @@ SIGNATURES = {
     "qh_rotate_field_c64_dev": [_vp, _i, _i64, C.c_double, _vp], "qh_rotate_field_c128_dev": [_vp, _i, _i64, C.c_double, _vp],
     "qh_apply_pmd_c64": _PMD, "qh_apply_pmd_c128": _PMD, "qh_apply_pmd_c64_dev": _PMD, "qh_apply_pmd_c128_dev": _PMD,
     "qh_modal_delay_c64_dev": [_vp, _i, _i64, _vp, _vp], "qh_modal_delay_c128_dev": [_vp, _i, _i64, _vp, _vp],
+    "qh_row_extrema_c64_dev": [_vp, _i, _i64, _vp], "qh_row_extrema_c128_dev": [_vp, _i, _i64, _vp],
+    "qh_dac_pointwise_c64_dev": _DAC, "qh_dac_pointwise_c128_dev": _DAC,
+    "qh_sosfilt_c64_dev": [_vp, _i, _i64, _vp, _i, _vp, _vp], "qh_sosfilt_c128_dev": [_vp, _i, _i64, _vp, _i, _vp, _vp],       # E, nmodes, L, sos (host), nsec, P (host), out
+    "qh_sos_geometry": [C.POINTER(_i), C.POINTER(_i)],
+    "qh_modulator_c64_dev": _MOD, "qh_modulator_c128_dev": _MOD,
     "qh_resample_c64": _RESAMPLE, "qh_resample_c128": _RESAMPLE, "qh_resample_c64_dev": _RESAMPLE, "qh_resample_c128_dev": _RESAMPLE,
     "qh_row_moments_c64_dev": [_vp, _i, _i64, _vp], "qh_row_moments_c128_dev": [_vp, _i, _i64, _vp],
     "qh_center_scale_c64_dev": [_vp, _i, _i64, _vp, _vp, C.c_double], "qh_center_scale_c128_dev": [_vp, _i, _i64, _vp, _vp, C.c_double],

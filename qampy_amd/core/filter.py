@@ -1,4 +1,5 @@
-"""Small filters used by the pilot receiver (behaviour of qampy/core/filter.py:215-237), root-raised-cosine shaping and chromatic dispersion."""
+"""Small filters used by the pilot receiver (behaviour of qampy/core/filter.py:215-237), root-raised-cosine shaping, the digital low-pass
+of ``filter_signal`` and chromatic dispersion."""
 import numpy as np
 
 
@@ -20,6 +21,20 @@ def rrcos_pulseshaping(sig, fs, T, beta, taps=1001):
     one, X = _rs._as_rows(sig)
     out = _rs._filter_rows(X, _rs.rrcos_taps(taps, fs, T, beta), 1, 1, 1.0, False)
     return out[0] if one else out
+
+
+def filter_signal(signal, fs, cutoff, ftype="bessel", order=2, analog=False):
+    """Low-pass every row of ``signal`` (1-d or 2-d, the dtype kept; anything but complex64 / complex128 is promoted to complex128) by a
+    digital Bessel (``norm='mag'``) or Butterworth filter of ``order`` 1 to 8 with the 3 dB ``cutoff`` (qampy/core/filter.py:86-147): the
+    sections of ``scipy.signal.bessel`` / ``butter`` run on the GPU as ``scipy.signal.sosfilt`` does, exact and parallel in time
+    (:func:`qampy_amd.core.hip_dsp.sosfilt_dev`).  ``ftype`` 'gauss' and 'exp' and ``analog=True`` need a transform of the whole row of
+    arbitrary length, or ``lsim``: NotImplementedError."""
+    from . import hip_dsp as _dsp
+    from . import impairments as _imp
+    if analog:
+        raise NotImplementedError("analog=True integrates the analog prototype with lsim, which is not implemented: use the digital filter")
+    sos = _dsp.design_lowpass_sos(fs, cutoff, ftype, order)
+    return _imp._on_device(signal, lambda E, out: _dsp.sosfilt_dev(E, out, sos))
 
 
 # ------------------------------------------------------------------------------------------------ chromatic dispersion

@@ -1,4 +1,5 @@
-"""Channel impairments on plain ndarrays (qampy/core/impairments.py:63-328 and :673-703 add_dispersion), through the GPU's kernels.
+"""Channel and transmitter impairments on plain ndarrays (qampy/core/impairments.py:63-328, :370-671 and :673-703 add_dispersion), through
+the GPU's kernels.
 
 Every function takes complex64 or complex128 input, 1-d or 2-d, and keeps its dtype; anything else is promoted to complex128.  The random
 ones take an extra keyword ``seed``: the noise is counter-based (Philox4x32-10), a function of (seed, mode, sample index).  ``seed=None``
@@ -148,3 +149,99 @@ def add_dispersion(sig, fs, D, L, wl0=1550e-9):
     N = n if (n & (n - 1)) == 0 and _filter.CD_NMIN <= n <= _filter.CD_NMAX else _filter.cd_block_size(_filter.cd_spread(fs, D, L, wl0))
     out = _filter.cd_filter_host(X, N, _filter.cd_coeffs_exact(fs, D, L, wl0))
     return out[0] if one else out
+
+
+# ------------------------------------------------------------------------------------------------ transmitter response
+# qampy/core/impairments.py:370-671 through csrc/txresp.hip.  Real input is promoted to complex128 like everywhere in this module, and the
+# result is complex: the reference's real-in, real-out paths (quantize_signal_New, apply_enob_as_awgn, filter_signal) are not reproduced.
+def _recreate(sig, arr):
+    return sig.recreate_from_np_array(arr) if hasattr(sig, "recreate_from_np_array") else arr
+
+
+def er_to_g(ext_rat):
+    """Gain factor of a Mach-Zehnder modulator of extinction ratio ``ext_rat`` (dB): ``(10**(er/20) - 1) / (10**(er/20) + 1)``."""
+    return (10 ** (ext_rat / 20) - 1) / (10 ** (ext_rat / 20) + 1)
+
+
+def clipper(sig, clipping_level):
+    """Clamp re and im to ``+-clipping_level`` (qampy/core/digital_pre_compensation.py:30-38), on the host: ``np.clip`` of both parts."""
+    x = np.asarray(sig)
+    lv = float(clipping_level)
+    if not np.iscomplexobj(x):
+        return np.clip(x, -lv, lv)
+    return (np.clip(x.real, -lv, lv) + 1j * np.clip(x.imag, -lv, lv)).astype(x.dtype if x.dtype in (np.complex64, np.complex128) else np.complex128)
+
+
+def quantize_signal_New(sig_in, nbits=6, rescale_in=True, rescale_out=True):
+    """Quantise to ``2**nbits`` levels with the thresholds midway between the output levels (``quantize_signal_New`` of the reference with
+    its defaults: every row scaled to +-1 by its own maximum, the result scaled back by the maximum over all rows); a value on a threshold
+    goes up.  Works on plain ndarrays and on signal objects (the subclass is kept).  Real input is promoted to complex128 and comes back
+    complex.  Other values of ``rescale_in`` / ``rescale_out`` are not implemented."""
+    if not (rescale_in and rescale_out):
+        raise NotImplementedError("quantize_signal_New runs with rescale_in=True and rescale_out=True only")
+    _dsp._dac_stages(1, nbits, 0)
+    if np.isclose(float(nbits), 0):
+        raise ValueError("nbits must be a whole number from 1 to 16")
+    return _recreate(sig_in, _on_device(sig_in, lambda E, out: _dsp.dac_pointwise_dev(E, out, quant_bits=nbits)))
+
+
+def apply_enob_as_awgn(sig, enob, verbose=False, seed=None):
+    """Noise of a converter of ``enob`` effective bits as white Gaussian noise: ``sigma = sqrt(2 (x_max / 2**(enob - 1))**2 / 12)`` with
+    ``x_max`` the largest ``|re|`` or ``|im|`` over all modes, read on the device.  ``verbose``: also the SNR in dB that corresponds to the
+    ENOB, ``10 log10(mean |sig|**2 / 2 / (delta**2 / 12))``, computed on the host.  Real input is promoted to complex128."""
+    seed = _fresh_seed(seed)
+    _dsp._dac_stages(1, 0, enob)
+    out = _on_device(sig, lambda E, o: _dsp.dac_pointwise_dev(E, o, enob=enob, seed=seed))
+    if not verbose:
+        return out
+    x = np.asarray(sig)
+    x_max = max(np.abs(x.real).max(), np.abs(x.imag).max())
+    return out, 10 * np.log10(np.mean(np.abs(x) ** 2) / 2 / ((x_max / 2 ** (float(enob) - 1)) ** 2 / 12))
+
+
+def apply_DAC_filter(sig, fs, cutoff=18e9, fn=None, ch=1):
+    """The DAC's frequency response as a second-order Bessel low-pass at ``cutoff`` (:func:`qampy_amd.core.filter.filter_signal`).  A measured
+    response (``fn``) multiplies the spectrum of the whole row: NotImplementedError."""
+    if fn is not None:
+        raise NotImplementedError("a measured DAC response (fn=...) multiplies the spectrum of the whole row, which is not implemented")
+    return _filter.filter_signal(sig, fs, cutoff, ftype="bessel", order=2)
+
+
+def sim_DAC_response(sig, fs, enob=5, clip_rat=1, quant_bits=0, seed=None, **dac_params):
+    """Clip, quantise, add ENOB noise and - if any ``dac_params`` are given - low-pass: ``sim_DAC_response`` of the reference on the device
+    (:func:`qampy_amd.core.hip_dsp.sim_dac_response_dev`).  Real input is promoted to complex128."""
+    seed = _fresh_seed(seed)
+    _dsp._dac_stages(clip_rat, quant_bits, enob)
+    if _dsp._dac_filter(dac_params) is not None:
+        _dsp.design_lowpass_sos(fs, _dsp._dac_filter(dac_params), "bessel", 2)
+    return _on_device(sig, lambda E, out: _dsp.sim_dac_response_dev(E, out, fs, enob=enob, clip_rat=clip_rat, quant_bits=quant_bits, seed=seed, **dac_params))
+
+
+def ideal_amplifier_response(sig, out_volt):
+    """``sig / max * out_volt`` with the largest ``|re|`` or ``|im|`` over all modes, on the host (one pass of numpy; on the device the
+    amplifier is part of the modulator's launch)."""
+    x = np.asarray(sig)
+    return x / max(np.abs(x.real).max(), np.abs(x.imag).max()) * out_volt
+
+
+def modulator_response(rfsig, dcbias=1, gfactr=1, cfactr=0, dcbias_out=0.5, gfactr_out=1):
+    """Response of an IQ modulator to the drive voltages ``rfsig`` (I in the real part, Q in the imaginary part, in fractions of Vpi):
+    ``modulator_response`` of the reference on the device.  Real input is promoted to complex128."""
+    _dsp._mod_params(dcbias, gfactr, cfactr, dcbias_out, gfactr_out)
+    return _on_device(rfsig, lambda E, out: _dsp.modulator_response_dev(E, out, dcbias=dcbias, gfactr=gfactr, cfactr=cfactr, dcbias_out=dcbias_out,
+                                                                         gfactr_out=gfactr_out))
+
+
+def sim_tx_response(sig, fs, enob=6, tgt_v=1, clip_rat=1, quant_bits=0, dac_params=_dsp._DAC_DEFAULT, seed=None, **mod_prms):
+    """A transmitter: DAC (clip, quantise, ENOB noise, Bessel low-pass), ideal amplifier to ``tgt_v`` (fractions of Vpi) and IQ modulator -
+    ``sim_tx_response`` of the reference in one visit to the device (:func:`qampy_amd.core.hip_dsp.sim_tx_response_dev`).  Real input is
+    promoted to complex128."""
+    seed = _fresh_seed(seed)
+    _dsp._dac_stages(clip_rat, quant_bits, enob)
+    _dsp._mod_params(**mod_prms)
+    if not np.isfinite(float(tgt_v)):
+        raise ValueError("tgt_v must be finite")
+    if _dsp._dac_filter(dac_params) is not None:
+        _dsp.design_lowpass_sos(fs, _dsp._dac_filter(dac_params), "bessel", 2)
+    return _on_device(sig, lambda E, out: _dsp.sim_tx_response_dev(E, out, fs, enob=enob, tgt_v=tgt_v, clip_rat=clip_rat, quant_bits=quant_bits,
+                                                                   dac_params=dac_params, seed=seed, **mod_prms))

@@ -1,4 +1,4 @@
-// Counter-based random numbers shared by the generators (synth.hip, impair.hip): Philox4x32-10 and Box-Muller.  A draw is a function of
+// Counter-based random numbers shared by the generators (synth.hip, impair.hip, txresp.hip): Philox4x32-10 and Box-Muller.  A draw is a function of
 // (key, counter) alone, never of the launch geometry.
 #pragma once
 #include "common.h"
@@ -26,6 +26,28 @@ __device__ __forceinline__ void gauss2(unsigned a, unsigned b, float &g0, float 
     const float r = sqrtf(-2.0f * __logf(u));
     float s, c;
     __sincosf(6.283185307179586f * v, &s, &c);
+    g0 = r * c; g1 = r * s;
+}
+
+// The impairments' draws (impair.hip, txresp.hip): counter (sample index low word, high word, mode, stream), key = the seed.
+constexpr unsigned IMP_STREAM_PHASE = 1u, IMP_STREAM_NOISE = 2u;
+constexpr double IMP_TWO_PI = 6.283185307179586476925;
+
+// two independent standard normals of sample n of a mode, in the precision of the signal
+__device__ __forceinline__ void imp_gauss(int64_t n, int mode, unsigned stream, unsigned k0, unsigned k1, float &g0, float &g1)
+{
+    const Philox p = philox4x32_10((unsigned)n, (unsigned)((uint64_t)n >> 32), (unsigned)mode, stream, k0, k1);
+    gauss2(p.x, p.y, g0, g1);
+}
+__device__ __forceinline__ void imp_gauss(int64_t n, int mode, unsigned stream, unsigned k0, unsigned k1, double &g0, double &g1)
+{
+    const Philox p = philox4x32_10((unsigned)n, (unsigned)((uint64_t)n >> 32), (unsigned)mode, stream, k0, k1);
+    const uint64_t a = (((uint64_t)p.x << 32) | p.y) >> 11, b = (((uint64_t)p.z << 32) | p.w) >> 11;
+    const double u = ((double)a + 1.0) * 0x1p-53;                          // (0, 1]
+    const double v = (double)b * 0x1p-53;                                  // [0, 1)
+    const double r = sqrt(-2.0 * log(u));
+    double s, c;
+    sincos(IMP_TWO_PI * v, &s, &c);
     g0 = r * c; g1 = r * s;
 }
 

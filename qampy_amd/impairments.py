@@ -50,3 +50,22 @@ def simulate_transmission(sig, snr=None, freq_off=None, lwdth=None, dgd=None, th
     if dgd is not None:
         out = apply_PMD(out, theta, dgd)
     return out
+
+
+def sim_tx_response(sig, enob=6, tgt_v=1, clip_rat=1, quant_bits=0, dac_params=_core._dsp._DAC_DEFAULT, seed=None, **mod_prms):
+    """A transmitter - DAC, ideal amplifier to ``tgt_v``, IQ modulator - on a signal object at its own ``fs``: see
+    :func:`qampy_amd.core.impairments.sim_tx_response`."""
+    return sig.recreate_from_np_array(_core.sim_tx_response(sig, sig.fs, enob=enob, tgt_v=tgt_v, clip_rat=clip_rat, quant_bits=quant_bits,
+                                                            dac_params=dac_params, seed=seed, **mod_prms))
+
+
+def sim_DAC_response(sig, enob=5, clip_rat=1, quant_bits=0, seed=None, **dac_params):
+    """Clip, quantise, ENOB noise and the DAC's low-pass on a signal object at its own ``fs``: see
+    :func:`qampy_amd.core.impairments.sim_DAC_response`."""
+    return sig.recreate_from_np_array(_core.sim_DAC_response(sig, sig.fs, enob=enob, clip_rat=clip_rat, quant_bits=quant_bits, seed=seed, **dac_params))
+
+
+def sim_mod_response(sig, dcbias=1, gfactr=1, cfactr=0, dcbias_out=0.5, gfactr_out=1):
+    """Response of an IQ modulator to a signal object: see :func:`qampy_amd.core.impairments.modulator_response`."""
+    return sig.recreate_from_np_array(_core.modulator_response(sig, dcbias=dcbias, gfactr=gfactr, cfactr=cfactr, dcbias_out=dcbias_out,
+                                                               gfactr_out=gfactr_out))

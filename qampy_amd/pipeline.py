@@ -183,7 +183,7 @@ class ResidentReceiver:
             self.invalidate()
 
     def impair(self, fs, snr=None, freq_off=None, lwdth=None, dgd=None, theta=np.pi / 3.731, modal_delay=None, seed=0, source=None,
-               next_capture=False, power=None):
+               next_capture=False, power=None, tx=None):
         """Impair the loaded capture in HBM (``self.E``, or ``self.E_next`` with ``next_capture``) in place, between ``load()`` / ``load_next()``
         and ``run()``: ``hip_dsp.simulate_transmission_dev`` at the sampling rate ``fs`` (symbol rate ``fs / os``) - phase noise of linewidth
         ``lwdth``, carrier offset ``freq_off``, noise to the SNR ``snr`` (dB), ``modal_delay``, PMD of ``dgd`` seconds at ``theta`` - enqueued on
@@ -195,7 +195,13 @@ class ResidentReceiver:
         ``load()`` from the clean power times ``hip_dsp.snr_power_factor(snr, os)``.  The clean power is ``power`` if given, else what the
         last ``load()`` read - with ``source`` that is the power of whatever ``load()`` saw last, so give ``power`` (the mean ``|source|**2``)
         unless the source is a copy of that capture; with neither, ValueError.  The factor is applied to the clean power, not compounded:
-        impair a loaded capture once."""
+        impair a loaded capture once.
+
+        ``tx``: a dict of ``hip_dsp.sim_tx_response_dev`` keywords (``enob``, ``tgt_v``, ``clip_rat``, ``quant_bits``, ``dac_params``, the
+        modulator's parameters, ``seed`` - default ``seed + 1``, so that the ENOB noise is not the channel's noise).  The transmitter is
+        applied first, to the source or in place, and every mode is then centred and scaled to unit mean power (``row_moments_dev`` /
+        ``center_scale_dev``): the modulator's output carries about a tenth of unit power, and the trainers' radii assume unit power.  The
+        channel impairments follow on that field; tier b's clean power is then 1."""
         buf = getattr(self, "E_next", None) if next_capture else self.E
         if buf is None:
             raise ValueError("no capture loaded for next_capture=True (load_next first)")
@@ -204,14 +210,27 @@ class ResidentReceiver:
             raise ValueError("source must be a (%d, %d) %s DeviceArray" % (self.nmodes, self.L, np.dtype(self.ct).name))
         if source is not None and source.ptr == buf.ptr:
             raise ValueError("source is the capture buffer itself: leave it out to impair in place")
+        if tx is not None:
+            tx = dict(tx)
+            tx.setdefault("seed", int(seed) + 1)
+            _dsp.sim_tx_response_check(src, buf, fs, **tx)
         clean = power
-        if self.tier == "b" and snr is not None and not next_capture:
+        if tx is not None:
+            clean = 1.0
+        elif self.tier == "b" and snr is not None and not next_capture:
             clean = getattr(self, "_load_power", None) if power is None else float(power)
             if clean is None:
                 raise ValueError("tier b needs the clean capture's power for its acquisition rule: power=..., or load() first")
         self._filter_done()                        # (a filter on stream 2 may still be reading the buffer)
         if (modal_delay is not None or dgd is not None) and getattr(self, "_cd_buf", None) is None:
             self._cd_buf = DeviceArray((self.nmodes, self.L), self.ct)
+        if tx is not None:
+            from .core import resample as _rs
+            if getattr(self, "_tx_mom", None) is None:
+                self._tx_mom = DeviceArray((self.nmodes, 3), np.float64)
+            _dsp.sim_tx_response_dev(src, buf, fs, **tx)
+            _rs.center_scale_dev(buf, _rs.row_moments_dev(buf, self._tx_mom), power=1.0)
+            src = buf
         _dsp.simulate_transmission_dev(src, buf, fs / self.os, fs, snr=snr, freq_off=freq_off, lwdth=lwdth, dgd=dgd, theta=theta, modal_delay=modal_delay,
                                        seed=seed, tmp=getattr(self, "_cd_buf", None))
         if getattr(self, "_prep", None) is not None:
