@@ -48,6 +48,50 @@ def peak_ratio(P):
     return np.where(s[:, -1] == 0, 1.0, r)
 
 
+def four_step_split(N):
+    """``(N1, N2)`` of the kernel's transform of N = 2^8 .. 2^20 points: one transform, (1, N), up to 2^13; above, N = N1 N2 with
+    N1 = 2^floor(lg N / 2)."""
+    lg = int(N).bit_length() - 1
+    assert N == 1 << lg
+    if lg <= 13:
+        return 1, N
+    N1 = 1 << (lg // 2)
+    return N1, N // N1
+
+
+def split_bins(N):
+    """Line bins of the rows of a size's test.  Four-step sizes: bins whose k1 = k mod N1 and k2 = k div N1 differ, so that a spectrum stored
+    or read back with N1 and N2 exchanged moves them (N - 1 apart, which both forms keep; duplicates at the square sizes dropped)."""
+    N1, N2 = four_step_split(N)
+    if N1 == 1:
+        cand = [1, N - 1, N // 2 + 3, 5, N // 4 + 2, N // 2 - 7, 3 * N // 4 + 1]
+    else:
+        cand = [N1, N2, N1 + 1, N - 1, (N1 - 1) + N1, 3 + 5 * N1, N // 2 + N1 + 2]
+    bins = []
+    for k in cand:
+        if k not in bins:
+            bins.append(k)
+    assert all(0 < k < N for k in bins)
+    return bins
+
+
+def swapped_readback(P, N1, N2):
+    """What a kernel returns for the spectrum ``P (rows, N1 N2)`` in bin order that stores bin k = k1 + N1 k2 at position k1 N2 + k2, as
+    csrc/foe.hip does, and reads position q back with N1 and N2 exchanged: as bin (q div N1) + N2 (q mod N1) in the peak search, or, which
+    is the same permutation, out[k] = S[(k mod N2) N1 + k div N2] in the spectrum kernel.  The identity when N1 = N2."""
+    P = np.atleast_2d(P)
+    S = P.reshape(-1, N2, N1).transpose(0, 2, 1).reshape(P.shape)                    # S[k1 N2 + k2] = P[k1 + N1 k2]
+    return S.reshape(-1, N2, N1).transpose(0, 2, 1).reshape(P.shape)                 # out[b N2 + a] = S[a N1 + b]
+
+
+def swapped_store(P, N1, N2):
+    """The other way round: a kernel that stores with N1 and N2 exchanged - bin k = k1' + N2 k2' at position k1' N1 + k2' - and reads
+    back correctly, out[k] = S[(k mod N1) N2 + k div N1].  The inverse permutation of :func:`swapped_readback`."""
+    P = np.atleast_2d(P)
+    S = P.reshape(-1, N1, N2).transpose(0, 2, 1).reshape(P.shape)                    # S[a N1 + b] = P[a + N2 b]
+    return S.reshape(-1, N1, N2).transpose(0, 2, 1).reshape(P.shape)                 # out[b N1 + a] = S[a N2 + b]
+
+
 def comp_freq_offset(x, fo, os=1):
     x = np.atleast_2d(np.asarray(x)).astype(np.complex128)
     t = np.arange(1, x.shape[1] + 1, dtype=float)

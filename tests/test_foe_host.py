@@ -104,6 +104,58 @@ def test_restatement_blocks_padding_and_first_maximum():
     assert list(foe_ref.find_freq_offset(two, 1, N, 1, True)) == [-2 / (4 * N)] * 2
 
 
+def test_split_helpers_follow_the_kernel_rule():
+    assert [foe_ref.four_step_split(2 ** lg) for lg in (8, 13, 14, 15, 16, 17, 18, 19, 20)] == \
+        [(1, 256), (1, 8192), (128, 128), (128, 256), (256, 256), (256, 512), (512, 512), (512, 1024), (1024, 1024)]
+    for lg in range(8, 21):
+        N = 2 ** lg
+        N1, N2 = foe_ref.four_step_split(N)
+        bins = foe_ref.split_bins(N)
+        assert len(set(bins)) == len(bins) and all(0 < k < N for k in bins)
+        if N1 == 1:
+            assert {1, N - 1, N // 2 + 3} <= set(bins)
+        else:
+            assert set(bins) == {N1, N2, N1 + 1, N - 1, 2 * N1 - 1, 3 + 5 * N1, N // 2 + N1 + 2}
+            assert len(bins) == (7 if N1 != N2 else 6)
+    # the two permutations against the index formulas they stand for, at a small non-square split
+    N1, N2 = 4, 8
+    N = N1 * N2
+    P = np.arange(2 * N, dtype=np.float64).reshape(2, N)
+    S = np.empty_like(P)
+    for k in range(N):
+        S[:, (k % N1) * N2 + k // N1] = P[:, k]                     # the kernel's store
+    rb = np.stack([S[:, (k % N2) * N1 + k // N2] for k in range(N)], axis=1)
+    assert np.array_equal(foe_ref.swapped_readback(P, N1, N2), rb)
+    by_peak_search = np.empty_like(P)
+    for q in range(N):
+        by_peak_search[:, (q // N1) + N2 * (q % N1)] = S[:, q]      # the peak search's bin of position q, exchanged
+    assert np.array_equal(by_peak_search, rb)
+    for k in range(N):
+        S[:, (k % N2) * N1 + k // N2] = P[:, k]                     # the store, exchanged
+    st = np.stack([S[:, (k % N1) * N2 + k // N1] for k in range(N)], axis=1)
+    assert np.array_equal(foe_ref.swapped_store(P, N1, N2), st)
+    assert np.array_equal(foe_ref.swapped_store(rb, N1, N2), P) and not np.array_equal(rb, P) and not np.array_equal(st, P)
+
+
+@pytest.mark.parametrize("lg", range(14, 21))
+def test_exchanged_split_moves_the_bins_only_at_non_square_sizes(lg):
+    """The inputs of the GPU tests can fail: a spectrum stored at k1 N2 + k2 and read back with N1 and N2 exchanged (or stored exchanged and
+    read back correctly) puts the lines of ``split_bins`` elsewhere at 2^15, 2^17 and 2^19 - every row but the one at N - 1 - and nowhere else at
+    the square sizes, where the exchange is the identity: the sizes the suite compared values at before (2^14, 2^16, 2^20) could not tell."""
+    N = 2 ** lg
+    N1, N2 = foe_ref.four_step_split(N)
+    bins = foe_ref.split_bins(N)
+    x = foe_ref.qam_tone(4, len(bins), N, np.asarray(bins, dtype=np.float64) / (4.0 * N), lg)
+    _, got, _, P = foe_ref.find_freq_offset(x, 1, N, 1, False, full=True)
+    assert list(got) == bins and foe_ref.peak_ratio(P).min() >= 1.2, (got, foe_ref.peak_ratio(P))
+    for form in (foe_ref.swapped_readback, foe_ref.swapped_store):
+        moved = np.argmax(form(P, N1, N2), axis=1) != np.asarray(bins)
+        if N1 == N2:
+            assert np.array_equal(form(P, N1, N2), P) and not moved.any()
+        else:
+            assert list(moved) == [k != N - 1 for k in bins], (form.__name__, moved)
+
+
 class _Stub:
     """A stand-in with a DeviceArray's attributes: the checks must fire before any library call."""
     def __init__(self, shape, dtype, ptr=1):

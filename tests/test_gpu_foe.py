@@ -6,7 +6,12 @@ its largest bin exceeds the second largest by a factor of 1.2 or more (the all-z
 sides).  The spectrum is compared as sqrt(P), max-abs relative to the restatement's rms: 1e-5 (complex64) and 1e-11 (complex128) up to
 N = 8192 - the bar of tests/test_gpu_cd.py for the same transform - times log2(N) / 13 above; peak and total power to twice that.  The
 spectrum of a rotated constellation is a line on a floor: the line stands sqrt(N) above the rms while its rounding error grows with its own
-size, so the comparison relative to the rms is made at 16-QAM up to the default size 2^16 and not at 2^20."""
+size, so the comparison relative to the rms is made at 16-QAM up to the default size 2^16 and not at 2^20.
+
+The sizes of this file are 256, 512, 1024, 4096, 8192, 2^14, 2^16 and 2^20: every four-step size among them is a square split (128^2, 256^2,
+1024^2), where a kernel that exchanged N1 and N2 in its store or its read-back would compute the same.  tests/test_gpu_foe_sizes.py runs
+every size 2^8 .. 2^20 with the helpers of this file, the non-square splits 2^15, 2^17 and 2^19 among them, and calls that need more than
+one chunk of blocks; the bars it measured at 2^17 .. 2^19 are in its docstring."""
 import ctypes as C
 
 import numpy as np
