@@ -255,6 +255,20 @@ int qh_find_freq_offset_c64(const void *E, int nmodes, int64_t L, int os, int ff
                             void *spectrum_out);
 int qh_find_freq_offset_c128(const void *E, int nmodes, int64_t L, int os, int fft_size, int blocks, int average, double *fo_out, double *stats_out,
                              void *spectrum_out);
+/* ---- viterbiviterbi (qampy/core/phaserecovery.py:40-79): Viterbi-Viterbi carrier recovery of every row of E (nmodes, L), M-PSK, 2 <= M <= 64,
+ * over windows of N samples, 1 <= N <= min(L, 1024) (anything else: QH_ERR_ARG).  z = (E / |E|)^M in the signal's precision (a zero sample
+ * counts as 1), window sums in double, their angles unwrapped as numpy does; trace (nmodes, L - N + 1), in the signal's real type, is
+ * (unwrapped - pi) / M formed in double, and Eout[row, o + k] = E[row, o + k] exp(-j trace[row, k]) with o = (N - 1) / 2; the other N - 1
+ * samples of every row of Eout are zero.  Device pointers, nothing read back, enqueued on the current stream. */
+int qh_vv_recover_c64_dev(const void *E, int nmodes, int64_t L, int N, int M, void *trace, void *Eout);
+int qh_vv_recover_c128_dev(const void *E, int nmodes, int64_t L, int N, int M, void *trace, void *Eout);
+/* ---- phase_partition_16qam (qampy/core/phaserecovery.py:292-382): 16-QAM carrier recovery by QPSK partitioning of every row of E (nmodes, L)
+ * in blocks of Nblock samples, 1 <= Nblock <= 4096 (the last block may be short).  Ring thresholds from cal_s0(E, 1.32) of the row and the class
+ * of a sample in double, fourth powers in the signal's precision, block sums in double.  trace (nmodes, L), in the signal's real type, is the
+ * reference's, mode for mode: unwrap(theta) / 4 - pi / 4.  Eout = E exp(-j trace), every mode by its own trace - NOT the reference's field,
+ * which rotates every mode by four times the last mode's estimate.  Device pointers, nothing read back, current stream. */
+int qh_partition16_recover_c64_dev(const void *E, int nmodes, int64_t L, int Nblock, void *trace, void *Eout);
+int qh_partition16_recover_c128_dev(const void *E, int nmodes, int64_t L, int Nblock, void *trace, void *Eout);
 /* Tail of pilot_based_cpe_new (qampy/core/pilotbased_receiver.py:318-327): the averaged pilot phases kph (nmodes, nk) at the symbol
  * positions knots (nk, increasing) interpolated linearly to every symbol (np.interp) and taken out: out = E exp(-1j trace); trace in the
  * signal's complex dtype like the reference returns it.  Host arrays. */

@@ -84,6 +84,8 @@ SIGNATURES = {
     "qh_comp_freq_offset_c64": [_vp, _i, _i64, _vp, _i, _vp], "qh_comp_freq_offset_c128": [_vp, _i, _i64, _vp, _i, _vp],
     "qh_comp_freq_offset_c64_dev": [_vp, _i, _i64, _vp, _i, _vp], "qh_comp_freq_offset_c128_dev": [_vp, _i, _i64, _vp, _i, _vp],
     "qh_find_freq_offset_c64": _FOE, "qh_find_freq_offset_c128": _FOE, "qh_find_freq_offset_c64_dev": _FOE, "qh_find_freq_offset_c128_dev": _FOE,
+    "qh_vv_recover_c64_dev": [_vp, _i, _i64, _i, _i, _vp, _vp], "qh_vv_recover_c128_dev": [_vp, _i, _i64, _i, _i, _vp, _vp],      # E, nmodes, L, N, M, trace, Eout
+    "qh_partition16_recover_c64_dev": [_vp, _i, _i64, _i, _vp, _vp], "qh_partition16_recover_c128_dev": [_vp, _i, _i64, _i, _vp, _vp],      # E, nmodes, L, Nblock, trace, Eout
     "qh_pilot_phase_trace_c64": [_vp, _i, _i64, _vp, _vp, _i, _vp, _vp], "qh_pilot_phase_trace_c128": [_vp, _i, _i64, _vp, _vp, _i, _vp, _vp],
     "qh_cd_filter_c64": _CD, "qh_cd_filter_c128": _CD, "qh_cd_filter_c64_dev": _CD, "qh_cd_filter_c128_dev": _CD,
     "qh_impair_pointwise_c64": _IMPAIR, "qh_impair_pointwise_c128": _IMPAIR, "qh_impair_pointwise_c64_dev": _IMPAIR, "qh_impair_pointwise_c128_dev": _IMPAIR,

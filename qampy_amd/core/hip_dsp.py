@@ -298,6 +298,99 @@ def find_freq_offset(E, os=1, fft_size=2 ** 16, blocks=1, average_over_modes=Tru
     return fo
 
 
+# ------------------------------------------------------------------------------------------------ feed-forward carrier recovery
+VV_NMAX, VV_MMAX, P16_NBLOCK_MAX = 1024, 64, 4096          # limits of csrc/cpr.hip
+
+
+def _cpr_check(name, E, trace, Eout, trace_len):
+    suf, rt, ct = _lib.suffix(E.dtype)
+    if len(E.shape) != 2 or np.dtype(E.dtype) != ct:
+        raise ValueError("%s works on a 2-d complex array" % name)
+    if tuple(Eout.shape) != tuple(E.shape) or np.dtype(Eout.dtype) != np.dtype(E.dtype):
+        raise ValueError("Eout must have E's shape and dtype")
+    if tuple(trace.shape) != (E.shape[0], trace_len) or np.dtype(trace.dtype) != rt:
+        raise ValueError("trace must be (%d, %d) %s" % (E.shape[0], trace_len, np.dtype(rt).name))
+    return "64" if suf == "32" else "128"
+
+
+def vv_recover_dev(E, N, M, trace, Eout):
+    """
+    Viterbi-Viterbi carrier recovery of every row of the (nmodes, L) complex DeviceArray ``E`` in HBM (csrc/cpr.hip; host layer
+    qampy/core/phaserecovery.py:40-79): ``M``-PSK, ``2 <= M <= 64``, windows of ``N`` samples, ``1 <= N <= min(L, 1024)``.  ``trace``:
+    (nmodes, L - N + 1) DeviceArray in the signal's real type, ``(unwrap(angle(window sums)) - pi) / M``; ``Eout``: (nmodes, L) like ``E``,
+    ``E[:, o + k] * exp(-1j * trace[:, k])`` with ``o = (N - 1) // 2`` and zeros on the other ``N - 1`` samples.  ValueError for sizes out
+    of range and for wrong shapes or dtypes.  Nothing is read back; enqueued on the current library stream.
+    """
+    N, M = int(N), int(M)
+    if len(E.shape) != 2:
+        raise ValueError("vv_recover_dev works on a 2-d complex array")
+    L = E.shape[1]
+    if not 1 <= N <= VV_NMAX:
+        raise ValueError("N must be between 1 and %d" % VV_NMAX)
+    if N > L:
+        raise ValueError("a window of %d samples does not fit a signal of %d" % (N, L))
+    if not 2 <= M <= VV_MMAX:
+        raise ValueError("M must be between 2 and %d" % VV_MMAX)
+    c = _cpr_check("vv_recover_dev", E, trace, Eout, L - N + 1)
+    _lib.call("qh_vv_recover_c%s_dev" % c, E.ptr, E.shape[0], L, N, M, trace.ptr, Eout.ptr)
+
+
+def partition16_recover_dev(E, Nblock, trace, Eout):
+    """
+    16-QAM carrier recovery by QPSK partitioning of every row of the (nmodes, L) complex DeviceArray ``E`` in HBM (csrc/cpr.hip; host layer
+    qampy/core/phaserecovery.py:292-382) in blocks of ``Nblock`` samples, ``1 <= Nblock <= 4096``.  ``trace``: (nmodes, L) DeviceArray in
+    the signal's real type, the reference's trace; ``Eout = E * exp(-1j * trace)``, every mode by its own trace (the reference rotates every
+    mode by four times the last mode's raw estimate: INTEGRATION.md).  ValueError for ``Nblock`` out of range and for wrong shapes or dtypes.
+    Nothing is read back; enqueued on the current library stream.
+    """
+    Nblock = int(Nblock)
+    if not 1 <= Nblock <= P16_NBLOCK_MAX:
+        raise ValueError("Nblock must be between 1 and %d" % P16_NBLOCK_MAX)
+    if len(E.shape) != 2 or E.shape[1] < 1:
+        raise ValueError("partition16_recover_dev works on a 2-d complex array")
+    c = _cpr_check("partition16_recover_dev", E, trace, Eout, E.shape[1])
+    _lib.call("qh_partition16_recover_c%s_dev" % c, E.ptr, E.shape[0], E.shape[1], Nblock, trace.ptr, Eout.ptr)
+
+
+def _cpr_host(E, run, trace_len):
+    """Rows of a host array up, ``run(dE, trace, out)``, ``(Eout, trace)`` back."""
+    E = np.asarray(E)
+    if E.ndim != 2 or not np.iscomplexobj(E):
+        raise TypeError("carrier recovery works on a 2-d complex array")
+    suf, rt, ct = _lib.suffix(E.dtype)
+    D = _lib.DeviceArray
+    dE = D.from_host(np.ascontiguousarray(E))
+    trace, out = D((E.shape[0], trace_len), rt), D(E.shape, ct)
+    run(dE, trace, out)
+    return out.to_host(), trace.to_host()
+
+
+def vv_recover(E, N, M):
+    """:func:`vv_recover_dev` for a host array ``E (nmodes, L)``: ``(Eout, trace)`` with the trace of every row."""
+    E = np.asarray(E)
+    N, M = int(N), int(M)
+    if E.ndim != 2:
+        raise TypeError("vv_recover works on a 2-d complex array")
+    if not 1 <= N <= VV_NMAX:
+        raise ValueError("N must be between 1 and %d" % VV_NMAX)
+    if N > E.shape[1]:
+        raise ValueError("a window of %d samples does not fit a signal of %d" % (N, E.shape[1]))
+    if not 2 <= M <= VV_MMAX:
+        raise ValueError("M must be between 2 and %d" % VV_MMAX)
+    return _cpr_host(E, lambda dE, tr, out: vv_recover_dev(dE, N, M, tr, out), E.shape[1] - N + 1)
+
+
+def partition16_recover(E, Nblock):
+    """:func:`partition16_recover_dev` for a host array ``E (nmodes, L)``: ``(Eout, trace)``."""
+    E = np.asarray(E)
+    Nblock = int(Nblock)
+    if E.ndim != 2 or E.shape[1] < 1:
+        raise TypeError("partition16_recover works on a non-empty 2-d complex array")
+    if not 1 <= Nblock <= P16_NBLOCK_MAX:
+        raise ValueError("Nblock must be between 1 and %d" % P16_NBLOCK_MAX)
+    return _cpr_host(E, lambda dE, tr, out: partition16_recover_dev(dE, Nblock, tr, out), E.shape[1])
+
+
 def pilot_phase_trace(E, knots, knot_phase):
     """Linear interpolation of the pilot phases ``knot_phase (nmodes, nk)`` at the symbol positions ``knots`` to every symbol of ``E
     (nmodes, L)`` (np.interp) and its removal, on the device: ``(E * exp(-1j trace), trace)``, the trace in E's complex dtype as the

@@ -2,6 +2,7 @@
 Host layer of blind-phase-search carrier recovery, mirror of ``qampy.core.phaserecovery.bps`` (qampy/core/phaserecovery.py:
 93-159) and ``bps_twostage`` (:222-288): test-angle grid, per-mode index search on the GPU, ``np.unwrap`` and de-rotation.
 The index search (one grid or a per-symbol grid) and the angle gather are the HIP kernels of :mod:`.hip_dsp`.
+The feed-forward estimators ``viterbiviterbi`` (:40-79) and ``phase_partition_16qam`` (:328-382) are one device pass each.
 """
 import numpy as np
 
@@ -66,6 +67,37 @@ def bps_twostage(E, Mtestangles, symbols, N, B=4, method="pyt", **kwargs):
     ph = np.asarray([track(r) for r in rows], dtype=rdt)
     out = rows * np.exp(1.j * ph)
     return (out.flatten(), ph.flatten()) if E.ndim == 1 else (out, ph)
+
+
+def viterbiviterbi(E, N, M, all_modes=False):
+    """
+    Viterbi-Viterbi blind phase recovery of an M-PSK signal, contract of qampy/core/phaserecovery.py:40-79: ``(Eout, phase_est)`` with
+    ``phase_est = (unwrap(angle(sums of exp(1j angle(E)) ** M over every window of N samples)) - pi) / M`` and ``Eout`` the window centres
+    de-rotated by it, zero on the ``N - 1`` samples that are no window's centre.  All modes in one device pass (``hip_dsp.vv_recover``;
+    ``1 <= N <= min(L, 1024)``, ``2 <= M <= 64``).
+
+    1-d input: flat outputs.  2-d input: the field of every mode and, as the reference returns it, the trace of the LAST mode -
+    ``all_modes=True`` returns the (nmodes, L - N + 1) traces of all of them.
+    """
+    rows = np.atleast_2d(E)
+    out, ph = _dsp.vv_recover(np.ascontiguousarray(rows), N, M)
+    if np.ndim(E) == 1:
+        return out.reshape(-1), ph.reshape(-1)
+    return out, (ph if all_modes else ph[-1])
+
+
+def phase_partition_16qam(E, Nblock):
+    """
+    16-QAM blind phase recovery by QPSK partitioning (Fatadin et al. 2010), qampy/core/phaserecovery.py:328-382: ``(Eout, phase)`` with the
+    reference's (nmodes, L) trace (flat for 1-d input; float64 for complex128 input), one estimate per block of ``Nblock`` samples,
+    ``1 <= Nblock <= 4096``.  ``Eout = E * exp(-1j * phase)``, every mode by its own trace: the reference's field, which rotates every mode
+    by the raw fourth-power angle of the last one, is not reproduced.  One device pass (``hip_dsp.partition16_recover``).
+    """
+    rows = np.atleast_2d(E)
+    out, ph = _dsp.partition16_recover(np.ascontiguousarray(rows), Nblock)
+    if np.ndim(E) == 1:
+        return out.reshape(-1), ph.reshape(-1)
+    return out, ph
 
 
 def find_freq_offset(sig, os=1, average_over_modes=True, fft_size=2 ** 16, method="pyt", blocks=1):

@@ -18,6 +18,7 @@
 //     short run, sliding for the rest, written to a padded LDS plane;
 //   * one thread per symbol scans the A sums for the first strict minimum (tie -> lowest angle, like the reference).
 #include "common.h"
+#include "unwrap_scan.h"
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
@@ -725,9 +726,7 @@ int bps_host(const void *E, int64_t L, const void *angles, int64_t p, int A, con
 // Device form of phaserecovery.py:145-159 for the resident pipeline.  With the linspace grid 4*ph = -pi + 2*pi*k/A, so
 // np.unwrap's correction is -2*pi when k jumps by more than A/2, +2*pi when it drops by more than A/2 and 0 otherwise
 // (|jump| == A/2 maps to 0: numpy keeps dd = +-pi).  The running correction is an integer prefix sum - exact.
-constexpr int UW_THREADS = 256;
-constexpr int UW_PER_THREAD = 4;
-constexpr int UW_CHUNK = UW_THREADS * UW_PER_THREAD;
+// (chunk constants and the scan of the chunk sums: unwrap_scan.h, shared with cpr.hip)
 
 // np.unwrap's decision for the step from grid entry kprev to kcur of 4 * ph, evaluated with the operations numpy applies to
 // the array (numpy/lib/_function_base_impl.py unwrap: dd = diff(p); ddmod = mod(dd + pi, 2 pi) - pi; ddmod = pi where it is
@@ -782,29 +781,6 @@ __global__ void __launch_bounds__(UW_THREADS) unwrap_partial_kernel(P src, int *
         for (int w = 0; w < UW_THREADS / 64; w++) t += red[w];
         chunk_sum[mode * nchunk + blockIdx.x] = t;
     }
-}
-
-__global__ void __launch_bounds__(1024) unwrap_scan_kernel(int *chunk_sum, int64_t nchunk)
-{
-    // exclusive scan of the chunk sums of one mode by one workgroup: a run of consecutive chunks per thread (loaded together), wave
-    // scans of the run totals, the 16 wave totals through LDS.  (A single wave walking the array 64 entries at a time was a chain of
-    // 64 dependent global round trips: 32 us for 4096 chunks.)
-    __shared__ int wtot[16];
-    int *cs = chunk_sum + (int64_t)blockIdx.x * nchunk;
-    const int64_t len = (nchunk + 1023) / 1024;
-    const int64_t i0 = (int64_t)threadIdx.x * len, i1 = i0 + len < nchunk ? i0 + len : nchunk;
-    int tot = 0;
-    for (int64_t i = i0; i < i1; i++) tot += cs[i];
-    int incl = tot;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o);
-        if ((int)(threadIdx.x & 63) >= o) incl += t;
-    }
-    if ((threadIdx.x & 63) == 63) wtot[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    int run = incl - tot;
-    for (int w = 0; w < (int)(threadIdx.x >> 6); w++) run += wtot[w];
-    for (int64_t i = i0; i < i1; i++) { const int v = cs[i]; cs[i] = run; run += v; }
 }
 
 template <typename R, typename P>

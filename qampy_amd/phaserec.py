@@ -18,6 +18,24 @@ def bps_twostage(E, Mtestangles, N, B=4, **kwargs):
     return core.phaserecovery.bps_twostage(E, Mtestangles, E.coded_symbols, N, B=B, **kwargs)
 
 
+def _keep_class(E, out):
+    return E.recreate_from_np_array(out) if type(E) is not np.ndarray and hasattr(E, "recreate_from_np_array") else out
+
+
+def viterbiviterbi(E, N):
+    """Viterbi-Viterbi phase recovery on an M-PSK signal object, ``M`` from ``E.M`` (qampy/phaserec.py viterbiviterbi): ``(Eout, ph)``; see
+    :func:`qampy_amd.core.phaserecovery.viterbiviterbi`."""
+    out, ph = core.phaserecovery.viterbiviterbi(np.asarray(E), N, E.M)
+    return _keep_class(E, out), ph
+
+
+def phase_partition_16qam(E, Nblock):
+    """16-QAM phase recovery by QPSK partitioning on a signal object (qampy/phaserec.py phase_partition_16qam): ``(Eout, ph)``; see
+    :func:`qampy_amd.core.phaserecovery.phase_partition_16qam`."""
+    out, ph = core.phaserecovery.phase_partition_16qam(np.asarray(E), Nblock)
+    return _keep_class(E, out), ph
+
+
 def find_freq_offset(sig, average_over_modes=False, fft_size=4096, method="pyt", blocks=1):
     """Frequency offset from the spectrum of the signal raised to the 4th power (qampy/phaserec.py:94-116); ``method`` and ``blocks`` as in
     :func:`qampy_amd.core.phaserecovery.find_freq_offset`."""

@@ -39,13 +39,26 @@ class ResidentReceiver:
     parameters (``Mtestangles=None`` skips carrier recovery).  ``Bbps=None``: single-stage search over ``Mtestangles`` angles; an integer
     selects the two-stage search - ``Mtestangles`` coarse angles, then ``Bbps`` fine ones around each symbol's coarse estimate
     (``hip_dsp.bps_twostage_recover_dev``; ``idx`` then holds the coarse and ``idx2`` the fine indices) - through the same calls.
+
+    ``carrier``: the carrier-recovery stage - ``"bps"`` (default), the blind phase search above; ``"vv"``, Viterbi-Viterbi for QPSK (``M == 4``)
+    with ``Nbps`` as the window (``hip_dsp.vv_recover_dev``): ``out`` keeps its (modes, N) shape with ``Nbps - 1`` zero edge samples and ``ph`` is
+    (modes, N - Nbps + 1); ``"partition"``, QPSK partitioning for 16-QAM (``M == 16``) with ``Nbps`` as the block length
+    (``hip_dsp.partition16_recover_dev``).  Neither has a test-angle grid or an index array; ``Mtestangles=None`` still skips the stage.
     """
 
     NONFINAL_TOL_FACTOR = _host.NONFINAL_TOL_FACTOR
 
     def __init__(self, nmodes, L, os, M, Ntaps, mu, methods=("cma", "mrde"), Niter=(1, 1), adaptive_stepsize=(False, False),
-                 TrSyms=(None, None), Mtestangles=64, Nbps=20, dtype=np.complex64, alphabet=None, modes=None, tier="a", pit=None, Bbps=None):
+                 TrSyms=(None, None), Mtestangles=64, Nbps=20, dtype=np.complex64, alphabet=None, modes=None, tier="a", pit=None, Bbps=None,
+                 carrier="bps"):
         suf, self.rt, self.ct = _lib.suffix(dtype)
+        self.carrier = str(carrier).lower()
+        if self.carrier not in ("bps", "vv", "partition"):
+            raise ValueError("carrier must be 'bps', 'vv' or 'partition'")
+        if self.carrier != "bps" and int(M) != {"vv": 4, "partition": 16}[self.carrier]:
+            raise ValueError("carrier='vv' recovers QPSK (M = 4) and carrier='partition' 16-QAM (M = 16); M = %d takes carrier='bps'" % int(M))
+        if self.carrier != "bps" and Bbps is not None:
+            raise ValueError("Bbps belongs to carrier='bps'")
         self.nmodes, self.L, self.os, self.M, self.Ntaps = int(nmodes), int(L), int(os), int(M), int(Ntaps)
         # run(overlap=True), tier b: the pending phase search in parts between the next capture's relaxation passes.  0: as many parts as the previous
         # capture had passes, less one; 1: one launch beside the first passes (rounds 3-4); n > 1: n parts.  (QAMPY_POST_PARTS: initial value, measurements)
@@ -104,7 +117,14 @@ class ResidentReceiver:
             self.symbols.append(DeviceArray.from_host(sy))
         self.err = [DeviceArray((nmodes, self.TrSyms[s] * self.Niter[s]), self.ct, zero=True) for s in range(self.nstage)]
         self.eq = DeviceArray((self.modes.size, self.N), self.ct)
-        if Mtestangles:
+        if Mtestangles and self.carrier != "bps":
+            lim = min(self.N, _dsp.VV_NMAX) if self.carrier == "vv" else _dsp.P16_NBLOCK_MAX
+            if not 1 <= int(Nbps) <= lim:
+                raise ValueError("carrier=%r takes Nbps from 1 to %d here" % (self.carrier, lim))
+            self.alphabet = DeviceArray.from_host(self.alphabet_host)
+            self.ph = DeviceArray((self.modes.size, self.N - int(Nbps) + 1 if self.carrier == "vv" else self.N), self.rt)
+            self.out = DeviceArray((self.modes.size, self.N), self.ct)
+        elif Mtestangles:
             self.alphabet = DeviceArray.from_host(self.alphabet_host)
             self.angles = DeviceArray.from_host(_dsp.test_angle_grid(Mtestangles, self.rt))
             self.idx = DeviceArray((self.modes.size, self.N), np.int32)
@@ -422,6 +442,13 @@ class ResidentReceiver:
 
     def _recover(self, part=0, nparts=1):
         self._bound()
+        if self.carrier != "bps":
+            # one pass over the whole row, like the two-stage search: whatever the number of parts, the last one launches it
+            if part == nparts - 1 and self.carrier == "vv":
+                _dsp.vv_recover_dev(self.eq, self.Nbps, 4, self.ph, self.out)
+            elif part == nparts - 1:
+                _dsp.partition16_recover_dev(self.eq, self.Nbps, self.ph, self.out)
+            return
         if self.Bbps is not None:
             # two stages: there is no part-wise form - whatever the number of parts, the last one is the one launch of the whole search
             if part == nparts - 1:
@@ -696,7 +723,9 @@ class ResidentReceiver:
         res = dict(wxy=self.wxy.to_host(), err=tuple(e.to_host() for e in self.err), eq=self.eq.to_host(),
                    mu=tuple(m.to_host()[0] for m in self.mu))
         if self.Mtestangles:
-            res.update(out=self.out.to_host(), ph=self.ph.to_host(), idx=self.idx.to_host())
+            res.update(out=self.out.to_host(), ph=self.ph.to_host())
+            if self.carrier == "bps":
+                res.update(idx=self.idx.to_host())
             if self.Bbps is not None:
                 res.update(idx2=self.idx2.to_host())
         return res
@@ -743,6 +772,9 @@ class ResidentReceiver:
         train = sum(self.Niter[s] * cs * (self.nmodes * self.os + nsel) for s in range(self.nstage))
         apply_ = cs * (self.nmodes * self.os + nsel)
         bps = nsel * (cs + cs + cs // 2) if self.Mtestangles else 0
+        if self.Mtestangles and self.carrier != "bps":
+            # the field in twice and out once, the trace; V&V: one double angle per sample out and in (the partition keeps one per block)
+            bps = nsel * (3 * cs + cs // 2 + (16 if self.carrier == "vv" else 0))
         if self.Mtestangles and self.Bbps is not None:
             bps += nsel * (cs + 4 + 4 + 4 + 4)     # fine stage: E and the coarse index in, the fine index out; the unwrap reads both indices
         return dict(train=train, apply=apply_, bps=bps, total=train + apply_ + bps)
@@ -894,6 +926,8 @@ class ChannelBank:
         r = self.rx
         if r.tier != "a":
             raise ValueError("a channel bank runs the exact recurrence (tier A)")
+        if r.carrier != "bps":
+            raise ValueError("a channel bank recovers the carrier by blind phase search (carrier='bps')")
         self.nmodes, self.L, self.os, self.Ntaps, self.ct, self.rt = int(nmodes), int(L), int(os), int(Ntaps), r.ct, r.rt
         TrSyms = kw.get("TrSyms", (None,) * r.nstage)
         self.TrSyms = tuple(_host._cal_training_symbol_len(os, Ntaps, L) if t is None else int(t) for t in TrSyms[:r.nstage])
