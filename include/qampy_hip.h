@@ -669,6 +669,33 @@ int qh_synth_capture_c64_dev(void *E, void *symbols, int32_t *idx_tx, const void
                              int os, double beta, double snr_db, int have_snr, double theta, double dgd_samples, int have_pmd,
                              double phase_var, uint64_t seed);
 
+/* ---- whole-row transforms (csrc/fft.hip): DFT (inverse != 0: inverse DFT, with numpy's 1 / L) along the last axis of E (nmodes, L) into
+ * out (nmodes, L); out may be E itself.  L: a power of two from 2^8 to 2^24, or any other length from 2 to 2^23 (Bluestein); anything else:
+ * QH_ERR_ARG before a launch.  Device pointers, nothing read back, enqueued on the current stream; a repeated call is bit-identical. */
+int qh_fft_c64_dev(const void *E, int nmodes, int64_t L, int inverse, void *out);
+int qh_fft_c128_dev(const void *E, int nmodes, int64_t L, int inverse, void *out);
+/* out = ifft(H . fft(E)) of every row, same lengths, H (L bins in numpy's fftfreq order) formed on the device in double.  kind:
+ *   1 brick wall  keep the bins whose position after fftshift lies in [i0, i1) (core/filter.py:28-49 pre_filter)
+ *   2 band        keep |k p0 - p1| < p2, k the signed bin number: p0 = 1 / (L d) of fftfreq(L, d), p1 the centre, p2 half the width
+ *   3 two rails   Hi = exp(-2 pi i p1 f), Hq = exp(-2 pi i p2 f), f = k p0: out = Re(D_p1{Re E}) + i Re(D_p2{Im E}), one transform pair
+ *   4 delay       H = exp(-2 pi i p1 f), f = k p0
+ *   5 / 6         H: a device table of L values, real in the field's real type / complex in the field's type
+ * out may be E itself. */
+int qh_spectral_filter_c64_dev(const void *E, int nmodes, int64_t L, int kind, double p0, double p1, double p2, int64_t i0, int64_t i1,
+                               const void *H, void *out);
+int qh_spectral_filter_c128_dev(const void *E, int nmodes, int64_t L, int kind, double p0, double p1, double p2, int64_t i0, int64_t i1,
+                                const void *H, void *out);
+/* ---- IQ conditioning (csrc/iq.hip; qampy/core/analog_frontend.py).  mom (nmodes, 10) doubles: sum I, sum Q, sum I^2, sum Q^2, sum I Q of every
+ * row of E (nmodes, L) over all samples, then the same five over every os-th sample; two launches, bit-reproducible. */
+int qh_iq_moments_c64_dev(const void *E, int nmodes, int64_t L, int os, double *mom);
+int qh_iq_moments_c128_dev(const void *E, int nmodes, int64_t L, int os, double *mom);
+/* coef (nmodes, 6) doubles (a00, a01, a10, a11, b0, b1) of y = A (I, Q)^T + b from mom.  kind 0: orthonormalize_signal(E, os), row by row;
+ * 1: comp_IQ_inbalance, moments pooled over all rows; 2: the centring of comp_IQ_inbalance alone.  Device pointers, one workgroup. */
+int qh_iq_coeffs_dev(const double *mom, int nmodes, int64_t L, int os, int kind, double *coef);
+/* out = A (Re E, Im E)^T + b per row, evaluated in double; out may be E. */
+int qh_iq_affine_c64_dev(const void *E, int nmodes, int64_t L, const double *coef, void *out);
+int qh_iq_affine_c128_dev(const void *E, int nmodes, int64_t L, const double *coef, void *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@ qampy_amd - MI355X-native (gfx950) implementation of QAMpy's adaptive-equaliser 
 Python host code calling hand-written HIP kernels through the ctypes C ABI of include/qampy_hip.h.  No PyTorch, no
 Triton, no CPU fallback.
 """
-from . import core, equalisation, filtering, impairments, phaserec, signals, theory  # noqa: F401
+from . import analog_frontend, core, equalisation, filtering, impairments, phaserec, signals, theory  # noqa: F401
 from ._lib import set_default_tier, get_default_tier  # noqa: F401   (tier a = exact recurrence, the default; tier b = parallel in time, INTEGRATION.md 1)
 
 __version__ = "0.1.0"

@@ -37,6 +37,7 @@ _IMPAIR = [_vp, _i, _i64, _i, C.c_double, _i, C.c_double, _i, C.c_double, C.c_ui
 _PMD = [_vp, _i, _i64, C.c_double, C.c_double, _vp]                 # E, nmodes, L, theta, dgd (samples), out
 _DAC = [_vp, _i, _i64, _vp, _i, C.c_double, _i, C.c_double, C.c_uint64, _vp]      # E, nmodes, L, ext, stages, clip_rat, quant_bits, enob, seed, out
 _MOD = [_vp, _i, _i64, _vp, _i, C.c_double, _vp, _vp]                            # E, nmodes, L, ext, have_amp, tgt_v, prm (host), out
+_SPECTRAL = [_vp, _i, _i64, _i, C.c_double, C.c_double, C.c_double, _i64, _i64, _vp, _vp]      # E, nmodes, L, kind, p0, p1, p2, i0, i1, H, out
 _ALIGNED = [_vp, _i64, _vp, _i64, _vp, _i, _i, _i64, _i64]          # row, N, idx_tx, ntx, alphabet, M, rot, lag, trim
 
 
@@ -101,6 +102,11 @@ SIGNATURES = {
     "qh_resample_c64": _RESAMPLE, "qh_resample_c128": _RESAMPLE, "qh_resample_c64_dev": _RESAMPLE, "qh_resample_c128_dev": _RESAMPLE,
     "qh_row_moments_c64_dev": [_vp, _i, _i64, _vp], "qh_row_moments_c128_dev": [_vp, _i, _i64, _vp],
     "qh_center_scale_c64_dev": [_vp, _i, _i64, _vp, _vp, C.c_double], "qh_center_scale_c128_dev": [_vp, _i, _i64, _vp, _vp, C.c_double],
+    "qh_fft_c64_dev": [_vp, _i, _i64, _i, _vp], "qh_fft_c128_dev": [_vp, _i, _i64, _i, _vp],                                   # E, nmodes, L, inverse, out
+    "qh_spectral_filter_c64_dev": _SPECTRAL, "qh_spectral_filter_c128_dev": _SPECTRAL,
+    "qh_iq_moments_c64_dev": [_vp, _i, _i64, _i, _vp], "qh_iq_moments_c128_dev": [_vp, _i, _i64, _i, _vp],                     # E, nmodes, L, os, mom
+    "qh_iq_coeffs_dev": [_vp, _i, _i64, _i, _i, _vp],                                                                           # mom, nmodes, L, os, kind, coef
+    "qh_iq_affine_c64_dev": [_vp, _i, _i64, _vp, _vp], "qh_iq_affine_c128_dev": [_vp, _i, _i64, _vp, _vp],                     # E, nmodes, L, coef, out
     "qh_select_angles_f32": _SELECT, "qh_select_angles_f64": _SELECT,
     "qh_make_decision_c64": _DECIDE, "qh_make_decision_c128": _DECIDE,
     "qh_make_decision_c64_dev": _DECIDE, "qh_make_decision_c128_dev": _DECIDE,

@@ -1,5 +1,5 @@
 """Small filters used by the pilot receiver (behaviour of qampy/core/filter.py:215-237), root-raised-cosine shaping, the digital low-pass
-of ``filter_signal`` and chromatic dispersion."""
+of ``filter_signal``, the brick-wall pre-filters and chromatic dispersion."""
 import numpy as np
 
 
@@ -35,6 +35,42 @@ def filter_signal(signal, fs, cutoff, ftype="bessel", order=2, analog=False):
         raise NotImplementedError("analog=True integrates the analog prototype with lsim, which is not implemented: use the digital filter")
     sos = _dsp.design_lowpass_sos(fs, cutoff, ftype, order)
     return _imp._on_device(signal, lambda E, out: _dsp.sosfilt_dev(E, out, sos))
+
+
+def _spectral_rows(signal, run, what):
+    from .. import _lib
+    x = np.asarray(signal)
+    if x.ndim not in (1, 2):
+        raise ValueError("%s works on 1-d or 2-d arrays" % what)
+    X = np.atleast_2d(x)
+    if X.dtype not in (np.complex64, np.complex128):
+        X = X.astype(np.complex128)
+    E = _lib.DeviceArray.from_host(np.ascontiguousarray(X))
+    run(E)
+    res = E.to_host()
+    return res.flatten() if x.ndim < 2 else res
+
+
+def pre_filter(signal, bw):
+    """Brick-wall pre-filter of every row of ``signal`` (qampy/core/filter.py:28-49), on the GPU as one whole-row transform pair
+    (:func:`qampy_amd.core.hip_dsp.pre_filter_dev`).  As written in the reference, ``bw`` is not a fraction: after ``fftshift`` the positions
+    ``int(L / (bw / 2)) <= j < L - int(L / (bw / 2))`` are kept, so ``bw=0.01`` - and any ``bw`` whose count is 0 - gives all zeros.
+    complex64 stays complex64, complex128 stays complex128, anything else is promoted to complex128; 1-d input gives 1-d output."""
+    from . import hip_dsp as _dsp
+    _dsp.fft_plan(np.asarray(signal).shape[-1])
+    _dsp.pre_filter_bins(np.asarray(signal).shape[-1], float(bw))
+    return _spectral_rows(signal, lambda E: _dsp.pre_filter_dev(E, E, bw), "pre_filter")
+
+
+def pre_filter_wdm(signal, bw, os, center_freq=0):
+    """Ideal band selection: keep the bins where ``abs(fftfreq(L, 1 / os) - center_freq) < bw / 2``.  The reference function
+    (qampy/core/filter.py:51-84) raises NameError - it sizes its window from an undefined ``sig`` - so this restates it with that one name
+    read as ``signal``, for rows along the last axis; dtypes and shapes as :func:`pre_filter`."""
+    from . import hip_dsp as _dsp
+    if not (np.isfinite(os) and os > 0 and np.isfinite(bw) and np.isfinite(center_freq)):
+        raise ValueError("os must be positive, bw and center_freq finite")
+    _dsp.fft_plan(np.asarray(signal).shape[-1])
+    return _spectral_rows(signal, lambda E: _dsp.pre_filter_wdm_dev(E, E, bw, os, center_freq), "pre_filter_wdm")
 
 
 # ------------------------------------------------------------------------------------------------ chromatic dispersion

@@ -16,3 +16,8 @@ def rrcos_pulseshaping(sig, beta, T=None):
     if T is None:
         T = 1 / sig.fb
     return sig.recreate_from_np_array(_core.rrcos_pulseshaping(sig, sig.fs, T, beta))
+
+
+def pre_filter(signal, bw):
+    """Brick-wall pre-filter of a signal object: :func:`qampy_amd.core.filter.pre_filter`, handed to ``signal.recreate_from_np_array``."""
+    return signal.recreate_from_np_array(_core.pre_filter(signal, bw))

@@ -183,6 +183,59 @@ class ResidentReceiver:
         if getattr(self, "_prep", None) is not None:
             self.invalidate()
 
+    def frontend(self, orthonormalize=True, skew=None, sampling_rate=None, pre_filter_bw=None, next_capture=False):
+        """Condition the loaded capture in HBM (``self.E``, or ``self.E_next`` with ``next_capture``) as the analog front end does, between
+        ``load()`` / ``load_next()`` and the other compensations, enqueued on stream 0: first the skew between the rails - ``skew=(delay_i,
+        delay_q)`` in seconds at ``sampling_rate``, :func:`qampy_amd.core.hip_dsp.skew_dev` - then the brick-wall pre-filter
+        ``pre_filter(E, pre_filter_bw)``, then ``orthonormalize_signal(E, os)`` at the receiver's ``os``.  The two filters are whole-row
+        transforms (a row of ``L`` samples must be a length csrc/fft.hip takes: ValueError otherwise) into a private buffer.
+
+        This stage changes the power.  Tier b: ``_load_power`` and the acquisition chunk of every cold stage are re-derived by the rule of
+        ``load()`` from a read-back of the first ``min(L, 4096)`` conditioned samples of every mode, which waits for the stage (not with
+        ``next_capture``, as in ``impair``)."""
+        buf = getattr(self, "E_next", None) if next_capture else self.E
+        if buf is None:
+            raise ValueError("no capture loaded for next_capture=True (load_next first)")
+        if skew is not None:
+            skew = tuple(float(v) for v in np.atleast_1d(skew))
+            if len(skew) != 2 or not all(np.isfinite(skew)):
+                raise ValueError("skew is (delay_i, delay_q) in seconds")
+            if sampling_rate is None:
+                raise ValueError("skew needs the sampling_rate of the capture")
+            _dsp._skew_step(self.L, sampling_rate)
+        if pre_filter_bw is not None:
+            _dsp.pre_filter_bins(self.L, float(pre_filter_bw))
+        if skew is not None or pre_filter_bw is not None:
+            _dsp.fft_plan(self.L)
+        self._filter_done()                        # (a filter on stream 2 may still be reading the buffer)
+        if (skew is not None or pre_filter_bw is not None) and getattr(self, "_fe_buf", None) is None:
+            self._fe_buf = DeviceArray((self.nmodes, self.L), self.ct)
+        cur = buf
+        if skew is not None:
+            cur = _dsp.skew_dev(cur, self._fe_buf, skew[0], skew[1], sampling_rate)
+        if pre_filter_bw is not None:
+            cur = _dsp.pre_filter_dev(cur, buf if cur is not buf else self._fe_buf, pre_filter_bw)
+        if orthonormalize:
+            if getattr(self, "_fe_mom", None) is None:
+                self._fe_mom = DeviceArray((self.nmodes, 10), np.float64)
+                self._fe_coef = DeviceArray((self.nmodes, 6), np.float64)
+            _dsp.orthonormalize_dev(cur, buf, self.os, mom=self._fe_mom, coef=self._fe_coef)
+        elif cur is not buf:
+            buf.copy_from(cur)
+        if getattr(self, "_prep", None) is not None:
+            self.invalidate()
+        if self.tier == "b" and not next_capture:
+            npow = min(self.L, 4096)
+            head = np.empty((self.nmodes, npow), self.ct)
+            for m in range(self.nmodes):
+                _lib.call("qh_memcpy_d2h", head[m].ctypes.data, buf.ptr + m * self.L * head.itemsize, npow * head.itemsize)
+            power = float(np.mean(np.abs(head.astype(np.complex128)) ** 2))
+            self._load_power = power
+            for s_, o in enumerate(self.pit):
+                if o.get("acquire") and not self.adaptive[s_] and not o.get("_acq_chunk_user"):
+                    o["acq_chunk"] = self._acq_chunk_rule(power, float(self.mu0[s_]), o)
+                    self._acq_asked[s_] = True
+
     def compensate_foe(self, fft_size=2 ** 16, blocks="all", average_over_modes=True, next_capture=False):
         """Estimate the frequency offset of the loaded capture in HBM (``self.E``, or ``self.E_next`` with ``next_capture``) at the receiver's
         ``os`` and take it out in place: ``hip_dsp.find_freq_offset_dev`` and ``comp_freq_offset_dev``, enqueued on stream 0 between
