@@ -414,7 +414,7 @@ int qh_get_default_tier(int *tier, double *tol);
 /* Test hooks (ABI 10; rounds 1-5 read environment variables in the launch paths): each forces a kernel form the automatic choice would not take at
  * that size, none selects a different algorithm, every one is exercised through this C ABI by the -m gpu tests named.  The launch paths read ONE table
  * of atomics; the environment variables of the same meaning (QAMPY_HIP_TRAINER, QAMPY_HIP_PIT_FORM, QAMPY_HIP_SEG_LANES, QAMPY_HIP_PIT_PROBE,
- * QAMPY_HIP_BPS) are read ONCE, when the library is loaded, as the table's initial values.
+ * QAMPY_HIP_BPS, QAMPY_HIP_PIT_TAIL) are read ONCE, when the library is loaded, as the table's initial values.
  *   key          values                                        what
  *   "trainer"    auto | direct | lookahead | iterative          form of the exact trainer, like qh_set_trainer (tests/test_gpu_parity.py)
  *   "pit_form"   auto | segment | block                         parallel in time: throughput / latency form of the passes (tests/test_gpu_pit.py)
@@ -422,6 +422,10 @@ int qh_get_default_tier(int *tier, double *tol);
  *   "pit_probe"  0 | 1                                          complex64: the complex128 analysis of a pass (probe of the capture) (tests/test_gpu_pit.py)
  *   "bps"        auto | tile | lds                              phase search: tile kernel for complex64 / streaming kernel with the LDS ring only (no
  *                                                               register-ring kernel) (tests/test_gpu_parity.py)
+ *   "pit_tail"   auto | split                                   parallel in time, eigen-space analysis: auto ends a pass with ONE launch - estimate, decision and
+ *                                                               the back product for the next pass - where the sweep allows it (throughput form, fixed
+ *                                                               step, whole capture); split keeps the two launches every other sweep uses.  Same
+ *                                                               operations on the same values either way (tests/test_gpu_pit_tail.py)
  * qh_set_form returns QH_ERR_ARG for an unknown key or value; a NULL or empty value resets the key to automatic.  qh_get_form returns QH_ERR_ARG
  * for an unknown key or a NULL value. */
 int qh_set_form(const char *key, const char *value);

@@ -257,7 +257,8 @@ def call(name, *args):
 
 def set_form(key, value=None):
     """Test hook (``qh_set_form``, include/qampy_hip.h): force a kernel form - ``set_form("trainer", "direct")``,
-    ``set_form("pit_form", "segment")``, ``set_form("seg_lanes", 8)``, ``set_form("pit_probe", 1)``, ``set_form("bps", "tile")`` (or ``"lds"``);
+    ``set_form("pit_form", "segment")``, ``set_form("seg_lanes", 8)``, ``set_form("pit_probe", 1)``, ``set_form("bps", "tile")`` (or ``"lds"``),
+    ``set_form("pit_tail", "split")``;
     ``None`` / ``""`` / ``0``: automatic.  Any other key or value raises."""
     v = "" if value is None else str(value)
     call("qh_set_form", str(key).encode(), v.encode())

@@ -126,11 +126,12 @@ thread_local unsigned g_scratch_epoch = 0;
 //   trainer    0 automatic, 1 direct, 2 lookahead, 3 iterative          pit_form   0 automatic, 1 segment (throughput form), 2 block (latency forms)
 //   seg_lanes  0 automatic, 8, 16                                       pit_probe  1: complex64 takes the complex128 analysis of a pass
 //   bps        0 automatic, 1 tile kernel for complex64, 2 streaming kernel with the LDS ring only
+//   pit_tail   0 automatic (estimate, decision and the next pass's back product in one launch where the sweep allows it), 1 split (always two launches)
 static std::atomic<int> g_form[FORM_COUNT];
 struct FormName { const char *key, *env; };
 static const FormName FORM_NAMES[FORM_COUNT] = {
     {"trainer", "QAMPY_HIP_TRAINER"}, {"pit_form", "QAMPY_HIP_PIT_FORM"}, {"seg_lanes", "QAMPY_HIP_SEG_LANES"}, {"pit_probe", "QAMPY_HIP_PIT_PROBE"},
-    {"bps", "QAMPY_HIP_BPS"}};
+    {"bps", "QAMPY_HIP_BPS"}, {"pit_tail", "QAMPY_HIP_PIT_TAIL"}};
 static int form_parse(int k, const char *v, int *out)
 {
     if (!v || !v[0]) { *out = 0; return 0; }
@@ -139,6 +140,7 @@ static int form_parse(int k, const char *v, int *out)
     case FORM_PIT: *out = v[0] == 's' ? 1 : (v[0] == 'b' ? 2 : (v[0] == 'a' || v[0] == '0' ? 0 : -1)); break;
     case FORM_SEG_LANES: { const int n = atoi(v); *out = (n == 8 || n == 16 || n == 0) ? n : -1; break; }
     case FORM_BPS: *out = v[0] == 't' ? 1 : (v[0] == 'l' ? 2 : (v[0] == 'a' || v[0] == '0' ? 0 : -1)); break;
+    case FORM_PIT_TAIL: *out = v[0] == 's' ? 1 : (v[0] == 'a' || v[0] == '0' ? 0 : -1); break;
     default: *out = atoi(v) != 0 ? 1 : 0; break;
     }
     return *out < 0 ? -1 : 0;

@@ -35,7 +35,7 @@ hipStream_t helper_stream();     // a third stream for small launches beside bot
 // Test / measurement hooks (qh_set_form): every switch that forces a kernel form the automatic choice would not take at that size lives in ONE table of
 // atomics, set through the C ABI; the launch paths read the table, never the environment.  (The environment variables of rounds 1-5 - QAMPY_HIP_TRAINER,
 // QAMPY_HIP_PIT_FORM, ... - are read ONCE, when the library is loaded, as the table's initial values: scripts/ that export them keep working.)
-enum FormKey { FORM_TRAINER = 0, FORM_PIT, FORM_SEG_LANES, FORM_PIT_PROBE, FORM_BPS, FORM_COUNT };
+enum FormKey { FORM_TRAINER = 0, FORM_PIT, FORM_SEG_LANES, FORM_PIT_PROBE, FORM_BPS, FORM_PIT_TAIL, FORM_COUNT };
 int form(FormKey k);
 const char *trainer_force();   // "" (automatic) or "direct" / "lookahead" / "iterative": qh_set_trainer(), else QAMPY_HIP_TRAINER
 double gram_budget_gb();         // scratch the Gram tables of one call may take (qh_set_gram_budget_gb; default: QAMPY_HIP_GRAM_BUDGET_GB read once, else 160)

@@ -1000,6 +1000,9 @@ template <typename R> struct PitFuse {
     // forward product of TWO tap-set arrays in one launch (MODE 0): blocks [0, nb) take T -> Out, blocks [nb, 2 nb) take T2 -> Out2 (nb = ceil(ncol / 16))
     const Cx<R> *T2 = nullptr;
     float2 *Out2 = nullptr;
+    // back product (MODE 1) into X only: the trainer then reads its start taps from X and writes its end taps to Y (SegArgs::wx / wx_out),
+    // so the product of the NEXT pass can share a launch with the decision of this one, which reads Y (pit_tail_kernel)
+    int x_only = 0;
 };
 // A2 = the matrix whose ROWS are read: V for the forward product (op(A) = V^H: op(A)[m][k] = conj(V[k][m])), V^T for the back
 // transform (op(A) = V: op(A)[m][k] = V^T[k][m]) - consecutive threads read consecutive m either way.
@@ -1324,21 +1327,20 @@ typedef float pit_f4 __attribute__((ext_vector_type(4)));
 constexpr int PIT_MC = 16, PIT_MBP = PIT_MC + 1;               // columns per block, row pitch of the B tile in LDS
 inline int pit_mfma_threads(int n) { return 64 * ((n + 15) / 16); }
 inline size_t pit_mfma_lds(int n) { return ((size_t)(n + 4) * PIT_MBP + (size_t)PIT_MC * (PIT_EIGMAX + 1)) * sizeof(Zf); }
+// (the body takes its block index and thread count as arguments: pit_tail_kernel runs it in the blocks behind its estimate blocks)
 template <typename R, int MODE>
-__global__ void __launch_bounds__(64 * (PIT_EIGMAX / 16)) pit_basis_mfma_kernel(const Zf *__restrict__ A2, const Cx<R> *__restrict__ T, const Zf *__restrict__ D, Zf *__restrict__ Out,
-                                                                               int n, int ncol, const PitCtrl *c, PitFuse<R> fz)
+__device__ __forceinline__ void pit_basis_mfma_body(const Zf *__restrict__ A2, const Cx<R> *__restrict__ T, const Zf *__restrict__ D, Zf *__restrict__ Out,
+                                                    int n, int ncol, const PitFuse<R> &fz, const int bid, const int nt)
 {
-    QH_WAVE_FIRST();
-    if (c->done) return;
     extern __shared__ __attribute__((aligned(16))) char pit_smem[];
     const int np = (n + 3) & ~3;                              // contraction length padded to whole MFMA steps (zero rows)
     Zf *Bs = reinterpret_cast<Zf *>(pit_smem);                // [np][PIT_MBP]
     Zf *Ct = Bs + (size_t)(n + 4) * PIT_MBP;                  // [PIT_MC][PIT_EIGMAX + 1] (MODE 1: transposition of the result)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6, nt = blockDim.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
     const int nb1 = (ncol + PIT_MC - 1) / PIT_MC;
-    const bool second = MODE == 0 && (int)blockIdx.x >= nb1;   // (block-uniform: the second array of a two-array forward product)
+    const bool second = MODE == 0 && bid >= nb1;   // (block-uniform: the second array of a two-array forward product)
     if (second) { T = fz.T2; Out = reinterpret_cast<Zf *>(fz.Out2); }
-    const int col0 = ((int)blockIdx.x - (second ? nb1 : 0)) * PIT_MC;
+    const int col0 = (bid - (second ? nb1 : 0)) * PIT_MC;
     const size_t wset = (size_t)fz.nmodes * n;
     // op(A) - 54 KB, the same for every block and launch, L2 resident - goes from global memory straight into the A operand
     // (lane: row 16 wave + (lane & 15), k + (lane >> 4); 8 steps prefetched), the B tile through LDS (shared by the waves)
@@ -1463,13 +1465,21 @@ __global__ void __launch_bounds__(64 * (PIT_EIGMAX / 16)) pit_basis_mfma_kernel(
                             const Zf d = Ct[cc * (PIT_EIGMAX + 1) + m];
                             const Cx<R> w{(R)(qr * x.re - qi * x.im + fz.damp * d.x), (R)(qr * x.im + qi * x.re + fz.damp * d.y)};
                             fz.X[base + m] = w;
-                            fz.Y[base + m] = w;
+                            if (!fz.x_only) fz.Y[base + m] = w;
                         }
                     }
                 }
             }
         }
     }
+}
+template <typename R, int MODE>
+__global__ void __launch_bounds__(64 * (PIT_EIGMAX / 16)) pit_basis_mfma_kernel(const Zf *__restrict__ A2, const Cx<R> *__restrict__ T, const Zf *__restrict__ D, Zf *__restrict__ Out,
+                                                                               int n, int ncol, const PitCtrl *c, PitFuse<R> fz)
+{
+    QH_WAVE_FIRST();
+    if (c->done) return;
+    pit_basis_mfma_body<R, MODE>(A2, T, D, Out, n, ncol, fz, (int)blockIdx.x, (int)blockDim.x);
 }
 
 // Boundary b = 1 .. S-1 of mode j (one wave each; entries (b-1) nsel + j): a = x~[b] against b = y~[b-1], lambda-weighted:
@@ -1960,15 +1970,15 @@ __global__ void __launch_bounds__(PIT_GT_THREADS) pit_gauge_kernel(const double 
 // Output power of the accumulated corrections: dev2[col] = sum_k lambda_k |D~_k[col]|^2 (D~ in the eigenbasis, after the scan), the
 // block's maximum -> devmax[blockIdx.x].  D~[s] is the first-order estimate of how far the start taps of segment s are from the
 // sequential trajectory; lambda-weighted it is the power of the output deviation they cause.
+// (256 threads of block `bid` out of `nblk`: the kernel below, or the first blocks of pit_tail_kernel)
 template <typename R>
-__global__ void __launch_bounds__(256) pit_devest_kernel(const Zf *D, const double *lam, int n, int ncol, const PitCtrl *c, float *devmax, unsigned *ticket, PitDecideArgs<R> da)
+__device__ __forceinline__ void pit_devest_body(const Zf *D, const double *lam, int n, int ncol, float *devmax, unsigned *ticket, const PitDecideArgs<R> &da,
+                                                const int bid, const int nblk)
 {
-    QH_WAVE_FIRST();
-    if (c->done) return;
     // 64 columns per block, 4 threads per column (each a quarter of the k, loads of consecutive columns coalesce and overlap)
     __shared__ float part[2][4][64], red[64], reds[64], redt[64], redm[64];
     const int cl = threadIdx.x & 63, kg = threadIdx.x >> 6;
-    const int col = blockIdx.x * 64 + cl;
+    const int col = bid * 64 + cl;
     float acc = 0.f, tap = 0.f;
     if (col < ncol) {
 #pragma unroll 8
@@ -2000,7 +2010,7 @@ __global__ void __launch_bounds__(256) pit_devest_kernel(const Zf *D, const doub
         __syncthreads();
     }
     if (threadIdx.x == 0) {                                       // worst column / sum over the columns of the output power; sum / worst column of the tap norm
-        devmax[4 * blockIdx.x] = red[0]; devmax[4 * blockIdx.x + 1] = reds[0]; devmax[4 * blockIdx.x + 2] = redt[0]; devmax[4 * blockIdx.x + 3] = redm[0];
+        devmax[4 * bid] = red[0]; devmax[4 * bid + 1] = reds[0]; devmax[4 * bid + 2] = redt[0]; devmax[4 * bid + 3] = redm[0];
     }
     // The block that finishes last takes the decision of the pass (one launch less per pass): results released device-wide, a ticket
     // drawn; whoever draws the last one acquires and goes on.
@@ -2008,12 +2018,48 @@ __global__ void __launch_bounds__(256) pit_devest_kernel(const Zf *D, const doub
     if (threadIdx.x == 0) {
         __threadfence();
         const unsigned t = atomicAdd(ticket, 1u);
-        last = t == gridDim.x - 1;
+        last = t == (unsigned)nblk - 1;
         if (last) { *ticket = 0; __threadfence(); }
     }
     __syncthreads();
     if (!last) return;
     pit_decide_body<R>(da);
+}
+template <typename R>
+__global__ void __launch_bounds__(256) pit_devest_kernel(const Zf *D, const double *lam, int n, int ncol, const PitCtrl *c, float *devmax, unsigned *ticket, PitDecideArgs<R> da)
+{
+    QH_WAVE_FIRST();
+    if (c->done) return;
+    pit_devest_body<R>(D, lam, n, ncol, devmax, ticket, da, (int)blockIdx.x, (int)gridDim.x);
+}
+// The tail of a pass in ONE launch: blocks [0, ndev) are pit_devest_kernel's - estimate, ticket, and in the last of them to finish the
+// decision of this pass -, blocks [ndev, ndev + ceil(ncol / 16)) are pit_basis_mfma_kernel<R, 1>'s - the start taps of the NEXT pass,
+// X[s] = theta_s X[s] + V D~[s], written to X only (PitFuse::x_only; the trainer reads X and writes Y).  The two kinds of block are
+// independent - no block waits for another, in any order of dispatch the result is the same:
+//   estimate / decision  reads  D (= Dz[1]), lam, devmax, dfc, pw, Ye, theta, modes_dev, V, the control block, Ylast (in Y)
+//                        writes devmax, ticket, Yprev, the control block, wx (the caller's taps), the host's flag
+//   product              reads  V^T, D (= Dz[1]), theta, modes_dev, X, and `done` of the control block (once, at entry)
+//                        writes X
+// Nothing one kind writes is read by the other, with one exception: `done`.  An estimate block never sees this launch's own
+// decision (the decision is taken by the block that draws the LAST ticket, and a block draws its ticket after it has read `done`),
+// so the ticket count is always complete.  A product block may see it and leave, or not see it and finish: X is then written in
+// part or in whole for a pass that never runs.  That is harmless - after `done` nothing reads X: the trainer and every analysis
+// kernel return at `done`, the sweep's result was taken from Y into wx by the decision, the exact-form redo starts from its own
+// copies of the caller's taps, and the next sweep's pit_seed_kernel overwrites X and Y from wx.
+// Block size: max(256, the product's 64 ceil(n / 16)); the waves a block's part has no use for leave before its first barrier.
+template <typename R>
+__global__ void __launch_bounds__(64 * (PIT_EIGMAX / 16)) pit_tail_kernel(const Zf *__restrict__ D, const double *lam, int n, int ncol, const PitCtrl *c, float *devmax, unsigned *ticket,
+                                                                         int ndev, PitDecideArgs<R> da, const Zf *__restrict__ VT, PitFuse<R> fz, int nt_prod)
+{
+    QH_WAVE_FIRST();
+    if (c->done) return;
+    if ((int)blockIdx.x < ndev) {
+        if (threadIdx.x >= 256) return;
+        pit_devest_body<R>(D, lam, n, ncol, devmax, ticket, da, (int)blockIdx.x, ndev);
+    } else {
+        if ((int)threadIdx.x >= nt_prod) return;
+        pit_basis_mfma_body<R, 1>(VT, (const Cx<R> *)nullptr, D, (Zf *)nullptr, n, ncol, fz, (int)blockIdx.x - ndev, nt_prod);
+    }
 }
 // last column whose estimated output deviation sum_k lambda_k |D~_k|^2 exceeds thr (way out of a stalled sweep: where does the trouble end?)
 static __global__ void __launch_bounds__(256) pit_front_kernel(const Zf *D, const double *lam, int n, int ncol, double thr, int *front, int *bad)
@@ -2538,6 +2584,10 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
     // keeps the probe-based analysis, whose defect vectors are formed in double precision before they are projected
     // (qh_set_form("pit_probe", "1") forces it for complex64 too: tests compare the two)
     const bool eig = want_corr && sizeof(R) == 4 && form(FORM_PIT_PROBE) == 0;
+    // The tail of a pass - estimate, decision, and the back product for the next pass - in one launch (pit_tail_kernel) where the trainer can
+    // read its start taps from X and write its end taps to Y: the throughput form of a fixed-step sweep of a whole capture under the eigen-space
+    // analysis.  Every other case keeps the two launches (qh_set_form("pit_tail", "split") forces them: tests compare the two).
+    const bool tail_fused = eig && seg_form && !adaptive && !split && form(FORM_PIT_TAIL) == 0;
     // Measured coarse model (pit_model_kernel): gain and the 2 x 2 block of the signal direction from the capture itself.  complex128, cma2 and
     // decision methods whose passes run in neither the segment nor the block-iterative form keep round 3's model (one formula gain per error
     // function, diagonal in the eigenbasis, extra damping beta).
@@ -2573,6 +2623,7 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
         QH_HIP(hipFuncSetAttribute((const void *)pit_cgemm_kernel<R, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
         QH_HIP(hipFuncSetAttribute((const void *)pit_basis_mfma_kernel<R, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
         QH_HIP(hipFuncSetAttribute((const void *)pit_basis_mfma_kernel<R, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+        QH_HIP(hipFuncSetAttribute((const void *)pit_tail_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
         gemm_attr.store(true, std::memory_order_release);
     }
 
@@ -2682,12 +2733,16 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
             return d;
         };
         auto timed = [&](int p) { return timing_mode == 2 || (timing_mode == 1 && p == 1); };
+        int back_done_for = 0;                                    // the pass whose start taps the last tail launch wrote into X (0: none)
         auto enqueue_pass = [&](int p) -> int {
             ((volatile float *)ev.hview)[2 * p] = -1.f;             // "not decided yet": pit_decide_kernel overwrites it (polled below)
             PitFuse<R> fz;
             fz.X = X; fz.Y = Y; fz.theta = theta; fz.modes_dev = (const int64_t *)modes_dev; fz.nmodes = nmodes; fz.nsel = nsel;
             fz.damp = (adaptive && p > 1) ? ad_damp : 1.f;      // (the first correction - from the seeds to the trajectory - in full)
-            if (p > 0 && want_corr) {
+            fz.x_only = tail_fused ? 1 : 0;
+            if (p > 0 && tail_fused && back_done_for == p) {
+                // the tail of pass p - 1 has written this pass's start taps into X already
+            } else if (p > 0 && want_corr) {
                 // start taps = theta X + V D~ with D[s+1] = d[s+1] + J D[s] from the analysis that closed pass p - 1 (below); with the
                 // correction switched off on the device (corr_on = 0) the scan ran with coefficient 0, D = d: plain relaxation
                 if (eig)
@@ -2712,7 +2767,7 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
             if (timed(p)) QH_HIP(hipEventRecord(ev.t0[p], g_stream));
             if (seg_form) {
                 SegArgs<R> sa{};
-                sa.E = (const Cx<R> *)E; sa.wx = Y; sa.symbols = la.symbols; sa.err = (Cx<R> *)err; sa.mu = mu_dev;
+                sa.E = (const Cx<R> *)E; sa.wx = tail_fused ? X : Y; sa.wx_out = tail_fused ? Y : nullptr; sa.symbols = la.symbols; sa.err = (Cx<R> *)err; sa.mu = mu_dev;
                 sa.L = L; sa.TrSyms = TrSyms; sa.nsy = la.nsy; sa.sy_pitch = la.sy_pitch; sa.err_pitch = TrSyms * Niter; sa.err_off = (int64_t)it * TrSyms;
                 sa.nmodes = nmodes; sa.ntaps = ntaps; sa.os = os; sa.nsel = nsel; sa.S = sg.S;
                 sa.seg_len = sg.len; sa.seg_extra = sg.extra; sa.seg_tail = sg.tail; sa.seg_begin = sg.begin;
@@ -2778,6 +2833,16 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
                 hipLaunchKernelGGL((pit_recur_eig_kernel<R>), dim3(ntot, nsel), dim3(PIT_RT), 0, g_stream, Xe, (const Zf *)Ye, Dz[1], (const double *)theta, lam, nsel, sg.S, sg.len,
                                    (const R *)mu_dev, beta, (const PitCtrl *)ctrl, (const float *)ad_M, (adaptive && p >= 1) ? ad_damp : 1.f,
                                    (const float4 *)ualpha, (const float2 *)uqv);
+                if (tail_fused) {
+                    // (whether or not pass p + 1 will be enqueued: the product blocks of a tail behind the last pass write start taps nobody reads)
+                    const int nt_prod = pit_mfma_threads(ntot);
+                    PitFuse<R> fn = fz;
+                    fn.damp = 1.f;                                   // (the next pass's: not adaptive)
+                    hipLaunchKernelGGL((pit_tail_kernel<R>), dim3(ndev + (ncol + PIT_MC - 1) / PIT_MC), dim3(nt_prod > 256 ? nt_prod : 256), pit_mfma_lds(ntot), g_stream,
+                                       (const Zf *)Dz[1], lam, ntot, ncol, (const PitCtrl *)ctrl, devmax, ticket, ndev,
+                                       decide_args(p, (const float *)devmax, (const float2 *)Ye, (float2 *)Yprev, ntot, ncol, 1), Vb + (size_t)ntot * ntot, fn, nt_prod);
+                    back_done_for = p + 1;
+                } else
                 hipLaunchKernelGGL((pit_devest_kernel<R>), dim3(ndev), dim3(256), 0, g_stream, (const Zf *)Dz[1], lam, ntot, ncol, (const PitCtrl *)ctrl, devmax, ticket,
                                    decide_args(p, (const float *)devmax, (const float2 *)Ye, (float2 *)Yprev, ntot, ncol, 1));
             } else {

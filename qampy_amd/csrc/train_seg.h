@@ -25,7 +25,8 @@ constexpr int SG_CH = 64;          // steps per staged chunk
 
 template <typename R> struct SegArgs {
     const Cx<R> *E;
-    Cx<R> *wx;                // (S, nmodes, nmodes*ntaps) tap sets, trained in place
+    Cx<R> *wx;                // (S, nmodes, nmodes*ntaps) tap sets: the start taps of every chain
+    Cx<R> *wx_out;            // the end taps go here, same layout (nullptr: into wx, trained in place)
     const Cx<R> *symbols;
     Cx<R> *err;               // rows of err_pitch, this sweep starts at column err_off
     const R *mu;
@@ -394,7 +395,8 @@ __global__ void __launch_bounds__(64) train_seg_kernel(SegArgs<R> a)
     // ---- taps: lane <-> TPL consecutive taps of input mode kin
     const int kin = l16 / a.lpm, t0 = (l16 - kin * a.lpm) * TPL;
     const bool has = kin < a.nmodes;
-    Cx<R> *wrow = a.wx + ((size_t)seg * a.nmodes + mode) * ntot;
+    const size_t woff = ((size_t)seg * a.nmodes + mode) * ntot;
+    const Cx<R> *wrow = a.wx + woff;
     v2 w[TPL];
 #pragma unroll
     for (int j = 0; j < TPL; j++) {
@@ -711,9 +713,10 @@ __global__ void __launch_bounds__(64) train_seg_kernel(SegArgs<R> a)
         __syncthreads();
     }
     if (alive) {
+        Cx<R> *wend = (a.wx_out ? a.wx_out : a.wx) + woff;
 #pragma unroll
         for (int j = 0; j < TPL; j++)
-            if (has && t0 + j < a.ntaps) stg(wrow + kin * a.ntaps + t0 + j, Cx<R>{w[j].x, w[j].y});
+            if (has && t0 + j < a.ntaps) stg(wend + kin * a.ntaps + t0 + j, Cx<R>{w[j].x, w[j].y});
         if constexpr (ADAPT) if (l16 == 0) { a.r_out[q] = ad_r; a.e_out[q] = ad_ep; a.mu_sum[q] = ad_sum; }
     }
 }
