@@ -700,6 +700,27 @@ int qh_iq_coeffs_dev(const double *mom, int nmodes, int64_t L, int os, int kind,
 int qh_iq_affine_c64_dev(const void *E, int nmodes, int64_t L, const double *coef, void *out);
 int qh_iq_affine_c128_dev(const void *E, int nmodes, int64_t L, const double *coef, void *out);
 
+/* ---- synchronisation of a received row with a transmitted one (csrc/sync.hip; qampy/core/ber_functions.py:33-160).  Device pointers unless
+ * said otherwise, enqueued on the current stream, nothing read back, no atomics: a repeated call is bit-identical.
+ * cc (nx_rows, nx + ny - 1) = fftconvolve(x, conj(y)[::-1], "full") of every row of x (nx_rows, nx) with the one row y (ny,): the peak of |cc|
+ * at index k says y lies k - (ny - 1) samples into x.  Three power-of-two transforms of size P >= max(nx + ny - 1, 2^8); nx < 1, ny < 1 or
+ * nx + ny - 1 > 2^24: QH_ERR_ARG before a launch.  The work buffers are cached: a call at a shape seen before allocates nothing. */
+int qh_xcorr_c64_dev(const void *x, int nx_rows, int64_t nx, const void *y, int64_t ny, void *cc);
+int qh_xcorr_c128_dev(const void *x, int nx_rows, int64_t nx, const void *y, int64_t ny, void *cc);
+/* res (rows, 6) doubles per row of cc (rows, n): the index of the first maximum of |cc| (np.argmax: ties to the lower index, a NaN before any
+ * number), max Re, max Im, max -Re, max -Im (NaN if the row holds one, as np.max) and |cc| at that index, compared in the field's real type.
+ * Two launches: one partial per tile, one workgroup over the partials. */
+int qh_xcorr_peak_c64_dev(const void *cc, int rows, int64_t n, double *res);
+int qh_xcorr_peak_c128_dev(const void *cc, int rows, int64_t n, double *res);
+/* out[i] = 1j^turns src[(i - offset) mod nsrc], i in [0, nout): the roll, roll-and-cut and periodic extension of sync_and_adjust in one
+ * formula; the rotation is exact (a swap and a sign); offset may be negative; out must not be src.  The i32 form moves label rows. */
+int qh_cyclic_gather_c64_dev(const void *src, int64_t nsrc, int64_t offset, int turns, int64_t nout, void *out);
+int qh_cyclic_gather_c128_dev(const void *src, int64_t nsrc, int64_t offset, int turns, int64_t nout, void *out);
+int qh_cyclic_gather_i32_dev(const int32_t *src, int64_t nsrc, int64_t offset, int64_t nout, int32_t *out);
+/* out[i] = alphabet[idx[i]], i in [0, n); a label outside [0, M) gives 0. */
+int qh_labels_to_symbols_c64_dev(const int32_t *idx, int64_t n, const void *alphabet, int M, void *out);
+int qh_labels_to_symbols_c128_dev(const int32_t *idx, int64_t n, const void *alphabet, int M, void *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,6 +157,11 @@ SIGNATURES = {
     "qh_cal_mi_mc_fast_c64": [_vp, _vp, _i64, _vp, _i, C.c_double, _vp], "qh_cal_mi_mc_fast_c128": [_vp, _vp, _i64, _vp, _i, C.c_double, _vp],
     "qh_estimate_snr_c64_dev": _ALIGNED + [_vp], "qh_estimate_snr_c128_dev": _ALIGNED + [_vp],
     "qh_metrics_c64_dev": _ALIGNED + [C.c_double, _i, _vp, _vp], "qh_metrics_c128_dev": _ALIGNED + [C.c_double, _i, _vp, _vp],
+    "qh_xcorr_c64_dev": [_vp, _i, _i64, _vp, _i64, _vp], "qh_xcorr_c128_dev": [_vp, _i, _i64, _vp, _i64, _vp],                  # x, nx_rows, nx, y, ny, cc
+    "qh_xcorr_peak_c64_dev": [_vp, _i, _i64, _vp], "qh_xcorr_peak_c128_dev": [_vp, _i, _i64, _vp],                              # cc, rows, n, res
+    "qh_cyclic_gather_c64_dev": [_vp, _i64, _i64, _i, _i64, _vp], "qh_cyclic_gather_c128_dev": [_vp, _i64, _i64, _i, _i64, _vp],  # src, nsrc, offset, turns, nout, out
+    "qh_cyclic_gather_i32_dev": [_vp, _i64, _i64, _i64, _vp],                                                                   # src, nsrc, offset, nout, out
+    "qh_labels_to_symbols_c64_dev": [_vp, _i64, _vp, _i, _vp], "qh_labels_to_symbols_c128_dev": [_vp, _i64, _vp, _i, _vp],      # idx, n, alphabet, M, out
 }
 
 PIT_MAXPASS, PIT_MAXCHUNK = 24, 32

@@ -42,7 +42,7 @@ double gram_budget_gb();         // scratch the Gram tables of one call may take
 int pit_timing_mode();            // which relaxation passes of a tier-b sweep get HIP events: 0 none, 1 pass 1 (default), 2 all (qh_set_pit_timing)
 int default_tier();               // 0: tier a (exact), 1: tier b - what the drop-in host-array trainers run (qh_set_default_tier)
 double default_tier_tol();        // tolerance of the default tier b (qh_set_default_tier)
-constexpr int SCRATCH_SLOTS = 24;
+constexpr int SCRATCH_SLOTS = 26;
 constexpr int SCRATCH_TWOSTAGE = 16;             // tables of the two-stage phase search (bps.hip)
 constexpr int SCRATCH_FOE = 17;                  // tables, spectrum and intermediates of the frequency-offset estimate (foe.hip)
 constexpr int SCRATCH_IMPAIR = 18;               // tile totals, power partials and sigma of the point-wise impairment pass (impair.hip)
@@ -51,6 +51,8 @@ constexpr int SCRATCH_TXRESP = 20;               // tile extrema and the row ext
 constexpr int SCRATCH_SOS = 21;                  // tile end states / start states of the sections filter (txresp.hip)
 constexpr int SCRATCH_CPR = 22;                  // angles, wrap counts and partial moments of the feed-forward carrier recovery (cpr.hip)
 constexpr int SCRATCH_FFT = 23;                  // tables and work buffers of the whole-row transforms (fft.hip); tile totals of the IQ moments (iq.hip)
+constexpr int SCRATCH_SYNC = 24;                 // reversed conjugate of y and its transform, spectra of the rows of x (sync.hip)
+constexpr int SCRATCH_PEAK = 25;                 // one partial per tile of the correlation's peak search (sync.hip)
 int scratch(int slot, size_t bytes, void **p);   // grow-only device scratch, slots 0..SCRATCH_SLOTS - 1
 unsigned scratch_epoch();        // changes whenever the calling thread's scratch slots are released (contents cached in a slot are gone)
 
@@ -59,6 +61,11 @@ int bps_twostage_recover_f32(const void *E, int nm, int64_t L, const void *angle
                              int32_t *idx2, void *ph, void *Eout);
 int bps_twostage_recover_f64(const void *E, int nm, int64_t L, const void *angles, int A, int B, const void *symbols, int M, int N, int32_t *idx1,
                              int32_t *idx2, void *ph, void *Eout);
+
+// Correlation of `rows` rows of x (nx samples each, dense) with one sequence on power-of-two transforms of size P (fft.hip): yrev (P values, the
+// first ny given: the conjugate of y reversed) is replaced by its transform, spec (rows, P) takes the transforms of the zero-extended rows, and
+// cc (rows, n), n <= P, the first n values of ifft(spec . yrev) of every row.  The caller checks the sizes; P is a power of two, 2^8 .. 2^24.
+template <typename R> int fft_correlate_pow2(const void *x, int rows, int64_t nx, void *yrev, int64_t ny, int64_t P, void *spec, void *cc, int64_t n);
 
 // Staging memory of the host-pointer entry points: power-of-two size classes kept in a small pool (api.hip) instead of a
 // hipMalloc / hipFree pair per call - hipFree synchronises the device, and the pilot receiver makes dozens of small calls.

@@ -22,6 +22,9 @@
 // four-step: step 1 reads the input, step 2 writes the output; Bluestein: the first transform reads the input, the second writes), so
 // `out` may be the very buffer `E`.  Partial overlap is not supported.
 //
+// fft_correlate_pow2 (for sync.hip) is the filter's chain with a caller's geometry: rows of any length zero-extended to a power of two as they
+// are loaded, the table the transform of a second sequence, and only the first n values of the inverse transform stored, densely.
+//
 // Scratch slot SCRATCH_FFT: W_N1 | W_N2 | chirp (L) | transform of the chirp filter (M) | T (rows M, four-step) | W (rows M, Bluestein): the
 // work buffers are 2 nmodes M complex values at most.  No atomics: a repeated call is bit-identical.  Every launch is bounded by the
 // call's arguments alone.
@@ -408,6 +411,30 @@ int spectral_filter_dev(const void *E, int nmodes, int64_t L, int kind, double p
     if ((rc = fft_transform<R>(p, (const Cx<R> *)E, (Cx<R> *)out, nmodes, 0, none))) return rc;
     return fft_transform<R>(p, (const Cx<R> *)out, (Cx<R> *)out, nmodes, 1, h);
 }
+
+// The padding lives in the load functor (zero beyond `valid`) and the cut to n values in the store functor: three transforms, no pass of
+// their own for either.  yrev is transformed in place, the table multiply is the kind-6 load of the inverse transform.
+template <typename R> int fft_correlate_pow2(const void *x, int rows, int64_t nx, void *yrev, int64_t ny, int64_t P, void *spec, void *cc, int64_t n)
+{
+    FftPlan<R> p;
+    int rc = fft_plan<R>(rows, P, p);
+    if (rc) return rc;
+    FftLoad<R> ld{};
+    ld.in = (const Cx<R> *)yrev; ld.stride = P; ld.valid = ny;
+    FftStore<R> st{};
+    st.out = (Cx<R> *)yrev; st.stride = P; st.valid = P; st.scale = (R)1;
+    if ((rc = fft_pow2(p, ld, st, 1))) return rc;
+    ld.in = (const Cx<R> *)x; ld.stride = nx; ld.valid = nx;
+    st.out = (Cx<R> *)spec;
+    if ((rc = fft_pow2(p, ld, st, rows))) return rc;
+    FftLoad<R> li{};
+    li.in = (const Cx<R> *)spec; li.stride = P; li.valid = P; li.conj = 1; li.hkind = FH_COMPLEX; li.H = yrev;
+    FftStore<R> so{};
+    so.out = (Cx<R> *)cc; so.stride = n; so.valid = n; so.conj = 1; so.scale = (R)(1.0 / (double)P);
+    return fft_pow2(p, li, so, rows);
+}
+template int fft_correlate_pow2<float>(const void *, int, int64_t, void *, int64_t, int64_t, void *, void *, int64_t);
+template int fft_correlate_pow2<double>(const void *, int, int64_t, void *, int64_t, int64_t, void *, void *, int64_t);
 
 }  // namespace qh
 

@@ -783,9 +783,10 @@ class ResidentReceiver:
                 res.update(idx2=self.idx2.to_host())
         return res
 
-    def ser(self, symbols_tx, maxlag=256, window=4096, trim=0):
+    def ser(self, symbols_tx, maxlag=256, window=4096, trim=0, sync="window"):
         """Symbol error rate of the recovered (else equalised) rows against the transmitted symbols, computed in HBM
-        (``qampy_amd.core.ber_functions.cal_ser_dev``); needs the alphabet.  Returns one dict per row."""
+        (``qampy_amd.core.ber_functions.cal_ser_dev``); needs the alphabet.  ``sync``: ``"window"`` - bounded search on decisions -
+        or ``"full"`` - the full cross-correlation, any delay, the pattern continued periodically.  Returns one dict per row."""
         from .core import ber_functions as _ber
         if self.alphabet_host is None:
             raise ValueError("ser() needs the alphabet")
@@ -795,16 +796,21 @@ class ResidentReceiver:
         if getattr(self, "_idx_tx", None) is None or self._idx_tx_src is not symbols_tx:
             self._idx_tx = _ber.tx_indices_dev(np.ascontiguousarray(symbols_tx, dtype=self.ct), self.alphabet)
             self._idx_tx_src = symbols_tx
-        return _ber.cal_ser_dev(self.out if self.Mtestangles else self.eq, self._idx_tx, self.alphabet, maxlag, window, trim)
+        return _ber.cal_ser_dev(self.out if self.Mtestangles else self.eq, self._idx_tx, self.alphabet, maxlag, window, trim, sync=sync,
+                                sync_ws=self._sync_workspace())
 
-    def metrics(self, symbols_tx, snr_db=None, maxlag=256, window=4096, trim=0, llr_minmax=False):
+    def metrics(self, symbols_tx, snr_db=None, maxlag=256, window=4096, trim=0, llr_minmax=False, sync="window"):
         """Signal-quality metrics (SER, BER, EVM, SNR estimate, GMI, MI) of the recovered (else equalised) rows against the
         transmitted symbols, computed in HBM (``qampy_amd.core.ber_functions.cal_metrics_dev``); aligned as :meth:`ser`
-        aligns them.  ``snr_db``: the SNR the GMI / MI are evaluated at (None: estimated per row).  One dict per row."""
+        aligns them (``sync`` as there).  ``snr_db``: the SNR the GMI / MI are evaluated at (None: estimated per row).  One dict per row."""
         from .core import ber_functions as _ber
         self._prepare_tx(symbols_tx)
         return _ber.cal_metrics_dev(self.out if self.Mtestangles else self.eq, self._idx_tx, self.alphabet, snr_db, maxlag, window, trim,
-                                    llr_minmax)
+                                    llr_minmax, sync=sync, sync_ws=self._sync_workspace())
+
+    def _sync_workspace(self):
+        """Buffers of ``sync="full"`` (symbols, correlation, peak table, label rows), kept so that a repeated call allocates nothing."""
+        return self.__dict__.setdefault("_sync_ws", {})
 
     def _prepare_tx(self, symbols_tx):
         """Alphabet and transmitted indices in HBM (cached per ``symbols_tx`` object), after the pending post-processing."""
@@ -1080,23 +1086,25 @@ class ChannelBank:
             elif r.Mtestangles:
                 _dsp.bps_recover_dev(self.eq.row(c), r.Mtestangles, r.alphabet, r.Nbps, self.idx.row(c), self.ph.row(c), self.out.row(c), angles=r.angles)
 
-    def ser(self, ch, symbols_tx, maxlag=256, window=4096, trim=0):
+    def ser(self, ch, symbols_tx, maxlag=256, window=4096, trim=0, sync="window"):
         """Per-row symbol errors of channel ``ch`` (device harness, see :meth:`ResidentReceiver.ser`)."""
         from .core import ber_functions as _ber
         r = self.rx
         if getattr(r, "alphabet", None) is None:
             r.alphabet = DeviceArray.from_host(r.alphabet_host)
         idx_tx = _ber.tx_indices_dev(np.ascontiguousarray(symbols_tx, dtype=self.ct), r.alphabet)
-        return _ber.cal_ser_dev((self.out if r.Mtestangles else self.eq).row(ch), idx_tx, r.alphabet, maxlag, window, trim)
+        return _ber.cal_ser_dev((self.out if r.Mtestangles else self.eq).row(ch), idx_tx, r.alphabet, maxlag, window, trim, sync=sync,
+                                sync_ws=r._sync_workspace())
 
-    def metrics(self, ch, symbols_tx, snr_db=None, maxlag=256, window=4096, trim=0, llr_minmax=False):
+    def metrics(self, ch, symbols_tx, snr_db=None, maxlag=256, window=4096, trim=0, llr_minmax=False, sync="window"):
         """Per-row signal-quality metrics of channel ``ch`` (device pass, see :meth:`ResidentReceiver.metrics`)."""
         from .core import ber_functions as _ber
         r = self.rx
         if getattr(r, "alphabet", None) is None:
             r.alphabet = DeviceArray.from_host(r.alphabet_host)
         idx_tx = _ber.tx_indices_dev(np.ascontiguousarray(symbols_tx, dtype=self.ct), r.alphabet)
-        return _ber.cal_metrics_dev((self.out if r.Mtestangles else self.eq).row(ch), idx_tx, r.alphabet, snr_db, maxlag, window, trim, llr_minmax)
+        return _ber.cal_metrics_dev((self.out if r.Mtestangles else self.eq).row(ch), idx_tx, r.alphabet, snr_db, maxlag, window, trim, llr_minmax, sync=sync,
+                                    sync_ws=r._sync_workspace())
 
     def fetch(self, ch):
         _lib.sync()

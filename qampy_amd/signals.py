@@ -102,7 +102,8 @@ class SignalQAM(np.ndarray):
             out._symbols = self._symbols.copy()
         return out
 
-    # ---- signal-quality metrics (qampy/signals.py:245-560); rows of ``signal_rx`` are modes, results are per mode
+    # ---- signal-quality metrics (qampy/signals.py:245-560); rows of ``signal_rx`` are modes, results are per mode.  ``sync_method``: where
+    # the alignment of an unsynchronised capture runs - "pyt": scipy on the host (the reference's), "hip": csrc/sync.hip on the device
     @property
     def Nbits(self):
         """Bits per symbol."""
@@ -111,10 +112,13 @@ class SignalQAM(np.ndarray):
     def _signal_present(self, signal):
         return np.atleast_2d(np.asarray(self if signal is None else signal))
 
-    def _sync_and_adjust(self, tx, rx, synced=False):
+    def _sync_and_adjust(self, tx, rx, synced=False, sync_method="pyt"):
         """Transmitted and received rows brought together (signals.py:245-266): unless ``synced``, every received mode takes
         the still unassigned transmitted mode with the largest correlation peak, rotated and rolled onto it
-        (``ber_functions.sync_and_adjust``); ``synced``: only the lengths are adjusted."""
+        (``ber_functions.sync_and_adjust``, on the host or - ``sync_method="hip"`` - on the device); ``synced``: only the lengths
+        are adjusted."""
+        if sync_method not in ("pyt", "hip"):
+            raise ValueError("sync_method must be 'pyt' (host) or 'hip' (device), not %r" % (sync_method,))
         if tx is None:
             raise ValueError("no transmitted symbols attached")
         tx, rx = np.atleast_2d(tx), np.atleast_2d(rx)
@@ -125,7 +129,7 @@ class SignalQAM(np.ndarray):
         for j in range(rx.shape[0]):
             best, pick = -100., None
             for i in free:
-                pair, peak = ber_functions.sync_and_adjust(tx[i], rx[j])
+                pair, peak = ber_functions.sync_and_adjust(tx[i], rx[j], method=sync_method)
                 if peak > best:
                     best, pick, chosen = peak, i, pair
             free.remove(pick)
@@ -160,36 +164,36 @@ class SignalQAM(np.ndarray):
         shifts = np.arange(self.Nbits - 1, -1, -1)
         return ((idx[..., None].astype(np.int64) >> shifts) & 1).astype(bool).reshape(idx.shape[0], -1)
 
-    def cal_ser(self, signal_rx=None, synced=False, verbose=False):
+    def cal_ser(self, signal_rx=None, synced=False, verbose=False, sync_method="pyt"):
         """Symbol error rate per mode (signals.py:295-333); ``verbose``: also the error vector and the synchronised tx."""
-        tx, rx = self._sync_and_adjust(self.symbols, self._signal_present(signal_rx), synced)
+        tx, rx = self._sync_and_adjust(self.symbols, self._signal_present(signal_rx), synced, sync_method)
         errs = self.make_decision(rx) - tx
         ser = np.count_nonzero(errs, axis=-1) / rx.shape[1]
         return (ser, errs, tx) if verbose else ser
 
-    def cal_ber(self, signal_rx=None, synced=False, verbose=False):
+    def cal_ber(self, signal_rx=None, synced=False, verbose=False, sync_method="pyt"):
         """Bit error rate per mode (signals.py:335-374); ``verbose``: also the bit errors and the synchronised tx bits."""
-        tx, rx = self._sync_and_adjust(self.symbols, self._signal_present(signal_rx), synced)
+        tx, rx = self._sync_and_adjust(self.symbols, self._signal_present(signal_rx), synced, sync_method)
         rx_bits, tx_bits = self.demodulate(rx), self.demodulate(tx)
         errs = tx_bits ^ rx_bits
         ber = np.count_nonzero(errs, axis=-1) / rx_bits.shape[1]
         return (ber, errs, tx_bits) if verbose else ber
 
-    def cal_evm(self, signal_rx=None, synced=False, blind=False):
+    def cal_evm(self, signal_rx=None, synced=False, blind=False, sync_method="pyt"):
         """RMS error vector magnitude per mode against the known symbols, or (``blind``) against the decisions
         (signals.py:376-421)."""
         rx = self._signal_present(signal_rx)
         if blind:
             tx = self.make_decision(rx)
         else:
-            tx, rx = self._sync_and_adjust(self.symbols, rx, synced)
+            tx, rx = self._sync_and_adjust(self.symbols, rx, synced, sync_method)
         d = tx - rx
         return np.asarray(np.sqrt(np.mean(d.real ** 2 + d.imag ** 2, axis=-1)))
 
-    def est_snr(self, signal_rx=None, synced=False, symbols_tx=None, verbose=False):
+    def est_snr(self, signal_rx=None, synced=False, symbols_tx=None, verbose=False, sync_method="pyt"):
         """Linear SNR per mode from the known symbols (signals.py:423-455); ``verbose``: ``(snr, S0, N0)``."""
         from .core import hip_dsp
-        tx, rx = self._sync_and_adjust(self.symbols if symbols_tx is None else symbols_tx, self._signal_present(signal_rx), synced)
+        tx, rx = self._sync_and_adjust(self.symbols if symbols_tx is None else symbols_tx, self._signal_present(signal_rx), synced, sync_method)
         est = np.array([hip_dsp.estimate_snr(np.ascontiguousarray(r), np.ascontiguousarray(t, dtype=r.dtype),
                                              np.ascontiguousarray(self.coded_symbols, dtype=r.dtype)) for r, t in zip(rx, tx)], dtype=np.float64)
         est = est.reshape(-1, 3)
@@ -202,11 +206,11 @@ class SignalQAM(np.ndarray):
         snr = np.atleast_1d(snr)
         return np.ones(rx.shape[0]) * 10 ** (snr / 10) if snr.size != rx.shape[0] else 10 ** (snr / 10)
 
-    def cal_gmi(self, signal_rx=None, synced=False, snr=None, llr_minmax=False):
+    def cal_gmi(self, signal_rx=None, synced=False, snr=None, llr_minmax=False, sync_method="pyt"):
         """``(GMI, GMI_per_bit)`` per mode from soft-decision LLRs (signals.py:457-508); ``snr`` in dB, estimated when None.
         One fused device pass per mode (``qh_metrics_*_dev``): the LLRs are never stored."""
         from . import _lib
-        tx, rx = self._sync_and_adjust(self.symbols, self._signal_present(signal_rx), synced)
+        tx, rx = self._sync_and_adjust(self.symbols, self._signal_present(signal_rx), synced, sync_method)
         snr = self._snr_linear(snr, tx, rx)
         ct = rx.dtype
         alphabet = _lib.DeviceArray.from_host(np.ascontiguousarray(self.coded_symbols, dtype=ct))
@@ -222,10 +226,10 @@ class SignalQAM(np.ndarray):
             per_bit[m] = 1 - sums[2:] / max(int(counts[2]), 1)
         return np.sum(per_bit, axis=-1), per_bit
 
-    def cal_mi(self, signal_rx=None, synced=False, snr=None, fast=True):
+    def cal_mi(self, signal_rx=None, synced=False, snr=None, fast=True, sync_method="pyt"):
         """Mutual information per mode (signals.py:510-548); ``snr`` in dB, estimated when None (then ``N0 = 1 / snr``)."""
         from .core import signal_quality
-        tx, rx = self._sync_and_adjust(self.symbols, self._signal_present(signal_rx), synced)
+        tx, rx = self._sync_and_adjust(self.symbols, self._signal_present(signal_rx), synced, sync_method)
         N0 = 1 / self._snr_linear(snr, tx, rx)
         alphabet = np.ascontiguousarray(self.coded_symbols, dtype=rx.dtype)
         return np.array([signal_quality.cal_mi(np.ascontiguousarray(rx[m]), np.ascontiguousarray(tx[m], dtype=rx.dtype), alphabet, N0[m], fast)
