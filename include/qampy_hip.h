@@ -721,6 +721,29 @@ int qh_cyclic_gather_i32_dev(const int32_t *src, int64_t nsrc, int64_t offset, i
 int qh_labels_to_symbols_c64_dev(const int32_t *idx, int64_t n, const void *alphabet, int M, void *out);
 int qh_labels_to_symbols_c128_dev(const int32_t *idx, int64_t n, const void *alphabet, int M, void *out);
 
+/* ---- bit source and Gray mapper (csrc/source.hip; qampy/core/prbs.py, qampy/signals.py:89-137, :678-731).  Device pointers, enqueued on the
+ * current stream, nothing read back, no atomics and no scratch: a repeated call is bit-identical.  Integer work and table look-ups only: the
+ * results are the reference's bit for bit.  Bits are one byte each, 0 or 1 (numpy's bool layout).
+ * bits[i] = bit start + i of the PRBS of `order` (7, 15, 23 or 31), i in [0, n), complemented if invert != 0.  kind 0: external XOR
+ * (pythran_dsp.prbs_ext with the taps of make_prbs_extXOR); kind 1: internal XOR (pythran_dsp.prbs_int(seed, mask, order, n) with the masks of
+ * make_prbs_intXOR).  seed in [0, 2^order), bit 0 = element 0 of the reference's bool seed; 0 <= start <= 2^62; 1 <= n <= 2^31; anything
+ * else: QH_ERR_ARG before a launch.  The work of a call does not depend on start. */
+int qh_prbs_bits_dev(int order, int kind, int64_t seed, int64_t start, int invert, int64_t n, uint8_t *bits);
+/* labels[s] = the nb bits of symbol s, the first one the most significant (SignalQAMGrayCoded._modulate), s in [0, nsym); a non-zero byte
+ * is a one.  nb in [2, 10], 1 <= nsym <= 2^31.  Rows of whole symbols are one call: nsym counts all of them. */
+int qh_bits_to_labels_dev(const uint8_t *bits, int64_t nsym, int nb, int32_t *labels);
+/* the inverse: the low nb bits of every label, most significant first. */
+int qh_labels_to_bits_dev(const int32_t *labels, int64_t nsym, int nb, uint8_t *bits);
+/* symbols[s] = alphabet[label of symbol s] (0 for a label outside [0, M)); labels: written too unless NULL. */
+int qh_modulate_bits_c64_dev(const uint8_t *bits, int64_t nsym, int nb, const void *alphabet, int M, void *symbols, int32_t *labels);
+int qh_modulate_bits_c128_dev(const uint8_t *bits, int64_t nsym, int nb, const void *alphabet, int M, void *symbols, int32_t *labels);
+/* One launch: PRBS bits start .. start + nsym nb - 1 (arguments as qh_prbs_bits_dev, nsym nb <= 2^31) -> labels -> symbols of one row.
+ * M must be 2^nb.  labels (nsym) and bits (nsym nb) are written only if not NULL. */
+int qh_prbs_symbols_c64_dev(int order, int kind, int64_t seed, int64_t start, int64_t nsym, int nb, const void *alphabet, int M, void *symbols,
+                            int32_t *labels, uint8_t *bits);
+int qh_prbs_symbols_c128_dev(int order, int kind, int64_t seed, int64_t start, int64_t nsym, int nb, const void *alphabet, int M, void *symbols,
+                             int32_t *labels, uint8_t *bits);
+
 #ifdef __cplusplus
 }
 #endif

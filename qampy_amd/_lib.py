@@ -162,6 +162,11 @@ SIGNATURES = {
     "qh_cyclic_gather_c64_dev": [_vp, _i64, _i64, _i, _i64, _vp], "qh_cyclic_gather_c128_dev": [_vp, _i64, _i64, _i, _i64, _vp],  # src, nsrc, offset, turns, nout, out
     "qh_cyclic_gather_i32_dev": [_vp, _i64, _i64, _i64, _vp],                                                                   # src, nsrc, offset, nout, out
     "qh_labels_to_symbols_c64_dev": [_vp, _i64, _vp, _i, _vp], "qh_labels_to_symbols_c128_dev": [_vp, _i64, _vp, _i, _vp],      # idx, n, alphabet, M, out
+    "qh_prbs_bits_dev": [_i, _i, _i64, _i64, _i, _i64, _vp],                                                                   # order, kind, seed, start, invert, n, bits
+    "qh_bits_to_labels_dev": [_vp, _i64, _i, _vp], "qh_labels_to_bits_dev": [_vp, _i64, _i, _vp],                               # bits, nsym, nb, labels / labels, nsym, nb, bits
+    "qh_modulate_bits_c64_dev": [_vp, _i64, _i, _vp, _i, _vp, _vp], "qh_modulate_bits_c128_dev": [_vp, _i64, _i, _vp, _i, _vp, _vp],      # bits, nsym, nb, alphabet, M, symbols, labels
+    "qh_prbs_symbols_c64_dev": [_i, _i, _i64, _i64, _i64, _i, _vp, _i, _vp, _vp, _vp],                                         # order, kind, seed, start, nsym, nb, alphabet, M, symbols, labels, bits
+    "qh_prbs_symbols_c128_dev": [_i, _i, _i64, _i64, _i64, _i, _vp, _i, _vp, _vp, _vp],
 }
 
 PIT_MAXPASS, PIT_MAXCHUNK = 24, 32

@@ -1,13 +1,19 @@
 """
-Minimal signal object for the hot path.
+Signal objects: the part of qampy/signals.py (1952 lines) the hot path and a transmitter need.
 
-QAMpy's signal classes (qampy/signals.py, 1952 lines) are out of scope.  The hot-path wrappers only
-touch ``sig.os, sig.M, sig.fb, sig.fs, sig.coded_symbols, sig.symbols`` and ``sig.recreate_from_np_array(arr, fs=...)``
-(qampy/equalisation.py:246-259, qampy/phaserec.py:92, qampy/signals.py:179-181, :209-220, :872-878), so this module
-provides one duck-typed ndarray subclass carrying exactly these.  Any object exposing the same attributes - including a
-real ``qampy.signals.SignalQAMGrayCoded`` - works with ``qampy_amd.equalisation`` / ``qampy_amd.phaserec``.
-:class:`PilotSignal` does the same for the pilot receiver (the attributes of ``SignalWithPilots`` the receiver reads).
+The hot-path wrappers only touch ``sig.os, sig.M, sig.fb, sig.fs, sig.coded_symbols, sig.symbols`` and
+``sig.recreate_from_np_array(arr, fs=...)`` (qampy/equalisation.py:246-259, qampy/phaserec.py:92, qampy/signals.py:179-181, :209-220,
+:872-878): :class:`SignalQAM` is one duck-typed ndarray subclass carrying exactly these around data somebody else produced.  Any object
+exposing the same attributes - including a real ``qampy.signals.SignalQAMGrayCoded`` - works with ``qampy_amd.equalisation`` /
+``qampy_amd.phaserec``.  :class:`PilotSignal` does the same for the pilot receiver (the attributes of ``SignalWithPilots`` the receiver reads).
+
+The source of a signal is here too, with the reference's call surface (qampy/signals.py:53-137, :611-905): :class:`RandomBits`,
+:class:`PRBSBits` (the generator runs on the device, csrc/source.hip) and :class:`SignalQAMGrayCoded` - bits to Gray-mapped symbols on the
+device, ``from_bit_array``, ``from_symbol_array``, ``modulate``, ``bits``.  ``QPSKfromBERT``, ``SignalWithPilots`` generation, ``TDHQAMSymbols``,
+``SignalPSKGrayCoded`` and ``SymbolOnlySignal`` stay out of scope.
 """
+import warnings
+
 import numpy as np
 
 from . import theory
@@ -234,6 +240,173 @@ class SignalQAM(np.ndarray):
         alphabet = np.ascontiguousarray(self.coded_symbols, dtype=rx.dtype)
         return np.array([signal_quality.cal_mi(np.ascontiguousarray(rx[m]), np.ascontiguousarray(tx[m], dtype=rx.dtype), alphabet, N0[m], fast)
                          for m in range(rx.shape[0])], dtype=np.float64)
+
+
+# ------------------------------------------------------------------------------------------------ bit sources and the Gray-coded signal
+class RandomBits(np.ndarray):
+    """
+    ``RandomBits(N, nmodes=1, seed=None)``: bool array ``(nmodes, N)`` of ``np.random.RandomState(seed).randint(0, 2, (nmodes, N))`` - the
+    reference's values (qampy/signals.py:53-86), drawn on the host (a Mersenne Twister is not worth a kernel).
+    """
+
+    def __new__(cls, N, nmodes=1, seed=None):
+        state = np.random.RandomState(seed)
+        obj = state.randint(0, high=2, size=(nmodes, N)).astype(bool).view(cls)
+        obj._rand_state, obj._seed = state, seed
+        return obj
+
+    def __array_finalize__(self, obj):
+        if obj is None:
+            return
+        self._seed = getattr(obj, "_seed", None)
+        self._rand_state = getattr(obj, "_rand_state", None)
+
+
+class PRBSBits(np.ndarray):
+    """
+    ``PRBSBits(N, nmodes=1, seed=[None, None], order=[15, 23])``: bool array ``(nmodes, N)``, row ``i`` the external-XOR PRBS of ``order[i]``
+    started from ``seed[i]`` (None: all ones) - qampy/signals.py:89-142 - generated on the device (``hip_dsp.prbs_bits_dev``).  When ``order``
+    has fewer entries than ``nmodes`` a warning is given and the modes without an entry take a random order out of 15 and 23 and a random seed.
+    """
+
+    def __new__(cls, N, nmodes=1, seed=[None, None], order=[15, 23]):
+        from . import _lib
+        from .core import hip_dsp
+        order, seed = list(order), list(seed)
+        if len(order) < nmodes:
+            warnings.warn("PRBSorder is not given for all dimensions, picking random orders and seeds")
+            given = min(len(order), len(seed))
+            order, seed = order[:given], seed[:given]
+            for _ in range(given, nmodes):
+                o = int(np.random.choice([15, 23]))
+                order.append(o)
+                seed.append(int(np.random.randint(0, 2 ** o)))
+        N = int(N)
+        d = _lib.DeviceArray((nmodes, N), np.uint8)
+        for i in range(nmodes):
+            hip_dsp.prbs_bits_dev(d.row(i), order[i], seed[i], kind="ext")
+        obj = d.to_host().view(bool).view(cls)
+        obj._order, obj._seed = order, seed
+        return obj
+
+    def __array_finalize__(self, obj):
+        if obj is None:
+            return
+        self._seed = getattr(obj, "_seed", None)
+        self._order = getattr(obj, "_order", None)
+
+
+def _check_dtype(dtype):
+    assert dtype in [np.complex128, np.complex64], "only np.complex128 and np.complex64  or None dtypes are supported"
+
+
+def _gray_alphabet(M, scale, dtype):
+    """The constellation over ``scale`` in Gray-label order (``_generate_mapping``, qampy/signals.py:831-845)."""
+    points = theory.cal_symbols_qam(M).astype(dtype)
+    points /= scale
+    code = theory.gray_code_qam(M)
+    place = np.zeros_like(code)
+    place[code] = np.arange(code.size)
+    return points[place]
+
+
+class SignalQAMGrayCoded(SignalQAM):
+    """
+    ``SignalQAMGrayCoded(M, N, nmodes=1, fb=1, bitclass=RandomBits, dtype=np.complex128, **kwargs)``: ``N`` Gray-coded M-QAM symbols per mode at
+    one sample per symbol, made from the bits of ``bitclass(N * log2(M), nmodes=nmodes, **kwargs)`` (qampy/signals.py:611-675).  The mapping
+    bits -> labels (MSB first) -> ``coded_symbols[label]`` runs on the device (``hip_dsp.modulate_bits_dev``); the values are the reference's.
+    ``bits`` holds the bit array, ``symbols`` a copy of the signal; everything :class:`SignalQAM` offers is inherited.
+    """
+
+    def __new__(cls, M, N, nmodes=1, fb=1, bitclass=RandomBits, dtype=np.complex128, **kwargs):
+        _check_dtype(dtype)
+        coded = _gray_alphabet(M, np.sqrt(theory.cal_scaling_factor_qam(M)), dtype)
+        bits = bitclass(int(N * np.log2(M)), nmodes=nmodes, **kwargs)
+        return cls._wrap(cls._modulate(bits, coded), M, fb, coded, bits)
+
+    @classmethod
+    def _wrap(cls, data, M, fb, coded, bits):
+        obj = SignalQAM.__new__(cls, data, M, fb=fb, coded_symbols=coded)
+        obj._bits = bits
+        obj._symbols = np.array(obj)
+        return obj
+
+    def __array_finalize__(self, obj):
+        super().__array_finalize__(obj)
+        if obj is not None:
+            self._bits = getattr(obj, "_bits", None)
+
+    def recreate_from_np_array(self, arr, **kwargs):
+        out = super().recreate_from_np_array(arr, **kwargs)
+        out._bits = self._bits
+        return out
+
+    @staticmethod
+    def _modulate(data, coded_symbols):
+        """Rows of bits to rows of ``coded_symbols``, on the device; bits beyond the last whole symbol are left out (signals.py:705-731)."""
+        from . import _lib
+        from .core import hip_dsp
+        data = np.atleast_2d(np.asarray(data))
+        nb = int(np.log2(coded_symbols.shape[0]))
+        nsym = data.shape[1] // nb
+        if nsym < 1 or data.shape[0] < 1:
+            return np.empty((data.shape[0], nsym), dtype=coded_symbols.dtype)
+        bits = _lib.DeviceArray.from_host(np.ascontiguousarray(data[:, :nsym * nb] != 0).view(np.uint8))
+        out = _lib.DeviceArray((data.shape[0], nsym), coded_symbols.dtype)
+        hip_dsp.modulate_bits_dev(bits, _lib.DeviceArray.from_host(np.ascontiguousarray(coded_symbols)), out)
+        return out.to_host()
+
+    @property
+    def bits(self):
+        return self._bits
+
+    def modulate(self, data):
+        """Modulate rows of bits into this signal's alphabet (a plain ``(nmodes, len // Nbits)`` array of the signal's dtype)."""
+        return self._modulate(data, np.ascontiguousarray(self.coded_symbols, dtype=self.dtype))
+
+    @classmethod
+    def from_bit_array(cls, bits, M, fb=1, dtype=np.complex128):
+        """A signal from a given 1-d or 2-d bit array (qampy/signals.py:784-829); a length that is no multiple of ``log2(M)`` is cut to one
+        with a warning, and ``bits`` holds the bits that were modulated."""
+        _check_dtype(dtype)
+        arr = np.atleast_2d(bits)
+        nb = int(np.log2(M))
+        if arr.shape[1] % nb > 0:
+            warnings.warn("Length of bits not divisible by log2(M) truncating")
+            arr = arr[:, :arr.shape[1] // nb * nb]
+        coded = _gray_alphabet(M, np.sqrt(theory.cal_scaling_factor_qam(M)), dtype)
+        return cls._wrap(cls._modulate(arr, coded), M, fb, coded, arr)
+
+    @classmethod
+    def from_symbol_array(cls, symbs, M=None, fb=1, dtype=None):
+        """A signal from given symbols (qampy/signals.py:733-782): the alphabet scaled to the power of the distinct values of ``symbs``,
+        decisions on it, then the decisions' bits - both on the device (what ``hip_dsp.demodulate_dev`` does, the decided symbols kept as
+        the signal).  ``bits`` holds every mode's bits,
+        ``(nmodes, N * log2(M))``."""
+        from . import _lib
+        from .core import hip_dsp
+        from .core.equalisation import hip_equalisation as hk
+        if dtype is not None:
+            _check_dtype(dtype)
+        symbs = np.atleast_2d(symbs)
+        if M is None:
+            warnings.warn("no M given, estimating how mnay unique symbols are in array, this can cause errors")
+            M = np.unique(symbs).shape[0]
+        if dtype is None:
+            dtype = symbs.dtype
+        P = (abs(np.unique(symbs)) ** 2).mean()
+        if not np.isclose(P, 1):
+            warnings.warn("Power of symbols is not normalized to 1, this might cause issues later")
+        scale = np.sqrt(theory.cal_scaling_factor_qam(M)) / np.sqrt((abs(np.unique(symbs)) ** 2).mean())
+        coded = _gray_alphabet(M, scale, dtype)
+        nb = int(np.log2(M))
+        E = _lib.DeviceArray.from_host(np.ascontiguousarray(symbs, dtype=dtype))
+        alphabet = _lib.DeviceArray.from_host(np.ascontiguousarray(coded))
+        det, labels = _lib.DeviceArray(E.shape, dtype), _lib.DeviceArray(E.shape, np.int32)
+        bits = _lib.DeviceArray((E.shape[0], E.shape[1] * nb), np.uint8)
+        hk.make_decision_dev(E, alphabet, det, None, labels)
+        hip_dsp.labels_to_bits_dev(labels, nb, bits)
+        return cls._wrap(det.to_host(), M, fb, coded, bits.to_host().view(bool))
 
 
 # ------------------------------------------------------------------------------------------------ pilot frames

@@ -156,6 +156,35 @@ def make_capture_dev(M, nsym, nmodes=2, os=2, snr_db=None, theta=None, dgd=None,
     return dict(E=E, symbols=sy, idx_tx=idx, alphabet=d_al, alphabet_host=alphabet, fb=fb, fs=fs, M=M)
 
 
+def make_symbols_dev(M, nsym, nmodes=2, order=(15, 23), seed=(None, None), kind="ext", dtype=np.complex64, keep_bits=False):
+    """
+    The transmitted symbols of a PRBS payload, made in HBM (``hip_dsp.prbs_symbols_dev``, csrc/source.hip): per mode one launch takes the PRBS
+    of ``order[m]`` from ``seed[m]`` through labels to Gray-mapped unit-power symbols - what ``SignalQAMGrayCoded(M, nsym, nmodes,
+    bitclass=PRBSBits, order=order, seed=seed)`` holds, bit for bit.  Nothing is read back.
+
+    Returns ``dict(symbols=(nmodes, nsym) dtype, idx_tx=(nmodes, nsym) int32, alphabet=(M,))`` of :class:`qampy_amd._lib.DeviceArray` plus
+    ``alphabet_host`` and ``M`` - the keys of :func:`make_capture_dev`, so ``idx_tx`` feeds ``cal_metrics_dev`` / ``ResidentReceiver.metrics``
+    directly - and, with ``keep_bits``, ``bits=(nmodes, nsym * log2(M)) uint8``.
+    """
+    from ._lib import DeviceArray
+    from .core import hip_dsp
+    if len(order) < nmodes or len(seed) < nmodes:
+        raise ValueError("make_symbols_dev: one PRBS order and one seed per mode")
+    if nmodes < 1 or nsym < 1:
+        raise ValueError("make_symbols_dev: at least one mode and one symbol")
+    alphabet = np.ascontiguousarray(theory.coded_symbols_qam(M, dtype=dtype))
+    nb = int(np.log2(M))
+    d_al = DeviceArray.from_host(alphabet)
+    sy, idx = DeviceArray((nmodes, nsym), dtype), DeviceArray((nmodes, nsym), np.int32)
+    bits = DeviceArray((nmodes, nsym * nb), np.uint8) if keep_bits else None
+    for m in range(nmodes):
+        hip_dsp.prbs_symbols_dev(sy.row(m), d_al, order[m], seed[m], kind=kind, labels=idx.row(m), bits=bits.row(m) if keep_bits else None)
+    out = dict(symbols=sy, idx_tx=idx, alphabet=d_al, alphabet_host=alphabet, M=M)
+    if keep_bits:
+        out["bits"] = bits
+    return out
+
+
 # ------------------------------------------------------------------------------------------------- SER harness
 def normalise_and_center(E):
     """Per-mode mean removal and unit-power scaling (behaviour of qampy/helpers.py:46-58)."""
