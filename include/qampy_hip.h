@@ -744,6 +744,51 @@ int qh_prbs_symbols_c64_dev(int order, int kind, int64_t seed, int64_t start, in
 int qh_prbs_symbols_c128_dev(int order, int kind, int64_t seed, int64_t start, int64_t nsym, int nb, const void *alphabet, int M, void *symbols,
                              int32_t *labels, uint8_t *bits);
 
+/* ---- pilot frames (csrc/pilot.hip; qampy/signals.py:1494-1545, :1753-1804, qampy/core/pilotbased_receiver.py:32-73, :258-327,
+ * qampy/phaserec.py:194-218).  Device pointers, enqueued on the current stream, nothing read back.  A frame of F symbols: S pilots (the
+ * sequence), then payload with one phase pilot every R symbols, the first of them at position S; R == 0: the sequence only.  NP = S + (F - S) / R
+ * pilots (R == 0: S) and ND = F - NP payload symbols per frame.  QH_ERR_ARG before a launch for S < 0, S > F, R < 0, R == 1 and (F - S) % R != 0.
+ * Assemble: frame (nmodes, nframes F) from pilots (nmodes, NP), scaled by pilot_scale (product in double, rounded once), and payload
+ * (nmodes, ND), repeated in every frame, or - own_payload != 0 - (nmodes, nframes ND), ND symbols per frame.  idx_frame (nmodes, nframes F),
+ * unless NULL: the payload's labels (same shape as payload) in the frame's layout, -1 at the pilots. */
+int qh_pilot_frame_c64_dev(const void *pilots, const void *payload, const int32_t *labels, int nmodes, int64_t F, int64_t S, int64_t R, int64_t nframes,
+                           int own_payload, double pilot_scale, void *frame, int32_t *idx_frame);
+int qh_pilot_frame_c128_dev(const void *pilots, const void *payload, const int32_t *labels, int nmodes, int64_t F, int64_t S, int64_t R, int64_t nframes,
+                            int own_payload, double pilot_scale, void *frame, int32_t *idx_frame);
+/* Take apart: the frames frames[0 .. nfr - 1] (device table; every one whole inside L - a frame that is not is left out) of the frame-aligned
+ * rows E (nmodes, L) into payload (nmodes, nfr ND) and / or pilots (nmodes, nfr NP), in the order of the table; either may be NULL. */
+int qh_pilot_split_c64_dev(const void *E, int nmodes, int64_t L, int64_t F, int64_t S, int64_t R, const int32_t *frames, int64_t nfr, void *payload,
+                           void *pilots);
+int qh_pilot_split_c128_dev(const void *E, int nmodes, int64_t L, int64_t F, int64_t S, int64_t R, const int32_t *frames, int64_t nfr, void *payload,
+                            void *pilots);
+/* phase (nmodes, n) float64 = unwrap(angle(E[:, pos_j] conj(sent[:, j % nref]))), j in [0, n): pilot j sits at pos_j = where[j % npf] + (j / npf) F,
+ * where (npf, device) strictly increasing inside [0, F); n is the number of j < npf nframes with pos_j < span <= min(L, nframes F) (the caller
+ * counts them; a position outside the span counts as a zero sample).  Angles in double for both precisions, np.unwrap as an exact integer prefix
+ * sum of wrap counts. */
+int qh_pilot_phase_c64_dev(const void *E, int nmodes, int64_t L, const int64_t *where, int64_t npf, int64_t nframes, int64_t F, int64_t span, int64_t n,
+                           const void *sent, int64_t nref, double *phase);
+int qh_pilot_phase_c128_dev(const void *E, int nmodes, int64_t L, const int64_t *where, int64_t npf, int64_t nframes, int64_t F, int64_t span, int64_t n,
+                            const void *sent, int64_t nref, double *phase);
+/* knot_phase (nmodes, n - N + 1): the centred moving average over N phases, every output a direct sum in double; N odd, 3 <= N <= min(n, 1023).
+ * knot_pos (n - N + 1) int64, unless NULL: the position of the pilot in the middle of every window (where == NULL: pilot j sits at j). */
+int qh_pilot_knots_dev(const double *phase, int nmodes, int64_t n, int N, const int64_t *where, int64_t npf, int64_t F, double *knot_phase, int64_t *knot_pos);
+/* The two above, then np.interp of the knots to every symbol of [0, span) (constant outside the knots) and its removal:
+ * trace (nmodes, span) in the signal's real type, Eout (nmodes, span) = E[:, :span] exp(-1j trace). */
+int qh_pilot_cpe_c64_dev(const void *E, int nmodes, int64_t L, const int64_t *where, int64_t npf, int64_t nframes, int64_t F, int64_t span, int64_t n,
+                         const void *sent, int64_t nref, int N, void *Eout, void *trace);
+int qh_pilot_cpe_c128_dev(const void *E, int nmodes, int64_t L, const int64_t *where, int64_t npf, int64_t nframes, int64_t F, int64_t span, int64_t n,
+                          const void *sent, int64_t nref, int N, void *Eout, void *trace);
+/* Least-squares line through the unwrapped phase of rec against ref, both (nmodes, n), n >= 2: fit (nmodes, 2) = [slope / (2 pi), intercept];
+ * fo (nmodes): every mode's own slope / (2 pi), or - average != 0 - their mean in every entry (what qh_comp_freq_offset_*_dev takes). */
+int qh_pilot_foe_c64_dev(const void *rec, const void *ref, int nmodes, int64_t n, int average, double *fit, double *fo);
+int qh_pilot_foe_c128_dev(const void *rec, const void *ref, int nmodes, int64_t n, int average, double *fit, double *fo);
+/* phase (nmodes): the mean of the unwrapped phase of rec against ref, both (nmodes, n). */
+int qh_pilot_const_phase_c64_dev(const void *rec, const void *ref, int nmodes, int64_t n, double *phase);
+int qh_pilot_const_phase_c128_dev(const void *rec, const void *ref, int nmodes, int64_t n, double *phase);
+/* out[m] = E[m] exp(-1j phi[m]), phi (nmodes) float64 in device memory; out may be E. */
+int qh_rotate_rows_c64_dev(const void *E, int nmodes, int64_t L, const double *phi, void *out);
+int qh_rotate_rows_c128_dev(const void *E, int nmodes, int64_t L, const double *phi, void *out);
+
 #ifdef __cplusplus
 }
 #endif

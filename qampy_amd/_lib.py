@@ -39,6 +39,9 @@ _DAC = [_vp, _i, _i64, _vp, _i, C.c_double, _i, C.c_double, C.c_uint64, _vp]    
 _MOD = [_vp, _i, _i64, _vp, _i, C.c_double, _vp, _vp]                            # E, nmodes, L, ext, have_amp, tgt_v, prm (host), out
 _SPECTRAL = [_vp, _i, _i64, _i, C.c_double, C.c_double, C.c_double, _i64, _i64, _vp, _vp]      # E, nmodes, L, kind, p0, p1, p2, i0, i1, H, out
 _ALIGNED = [_vp, _i64, _vp, _i64, _vp, _i, _i, _i64, _i64]          # row, N, idx_tx, ntx, alphabet, M, rot, lag, trim
+_PILOT_FRAME = [_vp, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i, C.c_double, _vp, _vp]      # pilots, payload, labels, nmodes, F, S, R, nframes, own_payload, pilot_scale, frame, idx_frame
+_PILOT_SPLIT = [_vp, _i, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp]                     # E, nmodes, L, F, S, R, frames, nfr, payload, pilots
+_PILOT_PHASE = [_vp, _i, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64]              # E, nmodes, L, where, npf, nframes, F, span, n, sent, nref
 
 
 def _train_sig(mu_ptr, dev=False):
@@ -167,6 +170,14 @@ SIGNATURES = {
     "qh_modulate_bits_c64_dev": [_vp, _i64, _i, _vp, _i, _vp, _vp], "qh_modulate_bits_c128_dev": [_vp, _i64, _i, _vp, _i, _vp, _vp],      # bits, nsym, nb, alphabet, M, symbols, labels
     "qh_prbs_symbols_c64_dev": [_i, _i, _i64, _i64, _i64, _i, _vp, _i, _vp, _vp, _vp],                                         # order, kind, seed, start, nsym, nb, alphabet, M, symbols, labels, bits
     "qh_prbs_symbols_c128_dev": [_i, _i, _i64, _i64, _i64, _i, _vp, _i, _vp, _vp, _vp],
+    "qh_pilot_frame_c64_dev": _PILOT_FRAME, "qh_pilot_frame_c128_dev": _PILOT_FRAME,
+    "qh_pilot_split_c64_dev": _PILOT_SPLIT, "qh_pilot_split_c128_dev": _PILOT_SPLIT,
+    "qh_pilot_phase_c64_dev": _PILOT_PHASE + [_vp], "qh_pilot_phase_c128_dev": _PILOT_PHASE + [_vp],                           # ..., phase
+    "qh_pilot_knots_dev": [_vp, _i, _i64, _i, _vp, _i64, _i64, _vp, _vp],                                                      # phase, nmodes, n, N, where, npf, F, knot_phase, knot_pos
+    "qh_pilot_cpe_c64_dev": _PILOT_PHASE + [_i, _vp, _vp], "qh_pilot_cpe_c128_dev": _PILOT_PHASE + [_i, _vp, _vp],             # ..., N, Eout, trace
+    "qh_pilot_foe_c64_dev": [_vp, _vp, _i, _i64, _i, _vp, _vp], "qh_pilot_foe_c128_dev": [_vp, _vp, _i, _i64, _i, _vp, _vp],   # rec, ref, nmodes, n, average, fit, fo
+    "qh_pilot_const_phase_c64_dev": [_vp, _vp, _i, _i64, _vp], "qh_pilot_const_phase_c128_dev": [_vp, _vp, _i, _i64, _vp],     # rec, ref, nmodes, n, phase
+    "qh_rotate_rows_c64_dev": [_vp, _i, _i64, _vp, _vp], "qh_rotate_rows_c128_dev": [_vp, _i, _i64, _vp, _vp],                 # E, nmodes, L, phi, out
 }
 
 PIT_MAXPASS, PIT_MAXCHUNK = 24, 32

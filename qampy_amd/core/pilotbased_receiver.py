@@ -126,10 +126,21 @@ def shift_signal(sig, shift_factors):
     return sig
 
 
-def pilot_based_foe(rec_symbs, pilot_symbs):
+def _check_method(method):
+    if method not in ("pyt", "hip"):
+        raise ValueError("method must be 'pyt' (host) or 'hip' (device), not %r" % (method,))
+
+
+def pilot_based_foe(rec_symbs, pilot_symbs, method="pyt"):
     """Frequency offset (cycles per symbol) from the slope of the unwrapped phase of received against transmitted pilots:
-    ``(mean over modes, per mode (n, 1), intercepts (n, 1))``."""
+    ``(mean over modes, per mode (n, 1), intercepts (n, 1))``.  ``method="hip"``: phase, unwrap and the line fit on the device
+    (``hip_dsp.pilot_foe``, centred sums instead of ``np.polyfit``)."""
+    _check_method(method)
     rec, ref = np.atleast_2d(rec_symbs), np.atleast_2d(pilot_symbs)
+    if method == "hip":
+        ct = np.result_type(rec.dtype, ref.dtype, np.complex64)
+        fit, _ = phaserecovery._dsp.pilot_foe(np.asarray(rec, dtype=ct), np.asarray(ref, dtype=ct))
+        return np.mean(fit[:, :1]), fit[:, :1].copy(), fit[:, 1:].copy()
     phase = np.unwrap(np.angle(ref.conj() * rec), axis=-1)
     n = np.arange(phase.shape[-1])
     fits = np.array([np.polyfit(n, row, 1) for row in phase])            # (nmodes, [slope, intercept])
@@ -138,12 +149,15 @@ def pilot_based_foe(rec_symbs, pilot_symbs):
 
 
 def pilot_based_cpe_new(signal, pilot_symbs, pilot_idx, frame_len, seq_len=None, num_average=1, use_pilot_ratio=1,
-                        max_num_blocks=None, nframes=1):
+                        max_num_blocks=None, nframes=1, method="pyt"):
     """
     Carrier phase from the pilots spread over the frame(s): phase of every used pilot against its reference, unwrapped,
     smoothed by a moving average of ``num_average`` pilots, interpolated linearly to every symbol and taken out.
-    Returns ``(compensated signal, phase trace)``, both ``nframes * frame_len`` long.
+    Returns ``(compensated signal, phase trace)``, both ``nframes * frame_len`` long.  ``method="pyt"``: angle, unwrap and average on
+    the host, interpolation and removal on the device; ``"hip"``: the whole estimate on the device (``hip_dsp.pilot_cpe``: the
+    signal goes up once, only the selection of the pilots stays here); the moving average is then a direct sum per window.
     """
+    _check_method(method)
     if not num_average > 1:
         raise AssertionError("need to take average over at least 3")
     if num_average % 2 == 0:
@@ -160,6 +174,11 @@ def pilot_based_cpe_new(signal, pilot_symbs, pilot_idx, frame_len, seq_len=None,
         raise AssertionError("Inproper pilot configuration, the number of received pilots differs from reference ones")
     if where.size < num_average:
         raise AssertionError("Inpropper pilot symbol configuration. Larger averaging block size than total number of pilot symbols")
+    if method == "hip":
+        ct = np.result_type(rows.dtype, sent.dtype, np.complex64)
+        corrected, trace = phaserecovery._dsp.pilot_cpe(np.asarray(rows[:, :span], dtype=ct), np.asarray(refs[:, ::use_pilot_ratio], dtype=ct), in_frame,
+                                                        frame_len, nframes, num_average)
+        return corrected[:, :nframes * frame_len], trace.astype(ct)[:, :nframes * frame_len]       # (the trace in the complex dtype the reference returns)
     # phase of every pilot against its reference, unwrapped and averaged over num_average neighbours: the knots of the phase trace
     knot_phase = moving_average(np.unwrap(np.angle(rows[:, where] * sent.conjugate()), axis=-1), num_average)
     half = num_average // 2

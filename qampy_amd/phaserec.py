@@ -47,22 +47,29 @@ def comp_freq_offset(sig, freq_offset):
     return sig.recreate_from_np_array(core.phaserecovery.comp_freq_offset(np.asarray(sig), freq_offset, sig.os))
 
 
-def pilot_cpe(signal, N=3, pilot_rat=1, max_blocks=None, nframes=1, use_seq=False):
+def pilot_cpe(signal, N=3, pilot_rat=1, max_blocks=None, nframes=1, use_seq=False, method="pyt"):
     """Pilot-based carrier-phase estimation on a frame-aligned 1 sample/symbol pilot signal: ``(signal_out, phase_trace)``
-    (qampy/phaserec.py:156-192 -> core.pilotbased_receiver.pilot_based_cpe_new)."""
+    (qampy/phaserec.py:156-192 -> core.pilotbased_receiver.pilot_based_cpe_new).  ``method="hip"``: the whole estimate on the device."""
     positions = np.flatnonzero(signal._idx_pil)
     if use_seq:                                          # sequence + phase pilots, or the phase pilots behind the sequence only
         reference, where, seq = signal.pilots, positions, signal._pilot_seq_len
     else:
         reference, where, seq = signal.ph_pilots, positions[signal._pilot_seq_len:], None
     corrected, trace = core.pilotbased_receiver.pilot_based_cpe_new(np.asarray(signal), np.asarray(reference), where, signal.frame_len, seq_len=seq,
-                                                                    num_average=N, use_pilot_ratio=pilot_rat, max_num_blocks=max_blocks, nframes=nframes)
+                                                                    num_average=N, use_pilot_ratio=pilot_rat, max_num_blocks=max_blocks, nframes=nframes,
+                                                                    method=method)
     return signal.recreate_from_np_array(corrected), trace
 
 
-def find_pilot_const_phase(rec_pilots, ref_pilots):
-    """Constant phase offset per mode between received and transmitted pilots (qampy/phaserec.py:194-218)."""
+def find_pilot_const_phase(rec_pilots, ref_pilots, method="pyt"):
+    """Constant phase offset per mode between received and transmitted pilots (qampy/phaserec.py:194-218).  ``method="hip"``: phase, unwrap
+    and mean on the device (``hip_dsp.pilot_const_phase``)."""
+    if method not in ("pyt", "hip"):
+        raise ValueError("method must be 'pyt' (host) or 'hip' (device), not %r" % (method,))
     rec, ref = np.atleast_2d(rec_pilots), np.atleast_2d(ref_pilots)
+    if method == "hip":
+        ct = np.result_type(rec.dtype, ref.dtype, np.complex64)
+        return core.hip_dsp.pilot_const_phase(np.asarray(rec, dtype=ct), np.asarray(ref, dtype=ct)).reshape(-1, 1)
     return np.array([[np.mean(np.unwrap(np.angle(ref[m].conj() * rec[m])))] for m in range(rec.shape[0])], dtype=np.float64)
 
 

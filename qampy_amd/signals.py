@@ -9,8 +9,9 @@ exposing the same attributes - including a real ``qampy.signals.SignalQAMGrayCod
 
 The source of a signal is here too, with the reference's call surface (qampy/signals.py:53-137, :611-905): :class:`RandomBits`,
 :class:`PRBSBits` (the generator runs on the device, csrc/source.hip) and :class:`SignalQAMGrayCoded` - bits to Gray-mapped symbols on the
-device, ``from_bit_array``, ``from_symbol_array``, ``modulate``, ``bits``.  ``QPSKfromBERT``, ``SignalWithPilots`` generation, ``TDHQAMSymbols``,
-``SignalPSKGrayCoded`` and ``SymbolOnlySignal`` stay out of scope.
+device, ``from_bit_array``, ``from_symbol_array``, ``modulate``, ``bits`` - and :class:`SignalWithPilots` (:1430-1645), which lays pilots and
+payload out as frames on the device (csrc/pilot.hip).  ``QPSKfromBERT``, ``TDHQAMSymbols``, ``SignalPSKGrayCoded`` and ``SymbolOnlySignal`` stay out
+of scope.
 """
 import warnings
 
@@ -419,8 +420,8 @@ class PilotSignal(np.ndarray):
     Pilot-frame capture ``(nmodes, nsamples)``: the attributes of ``qampy.signals.SignalWithPilots`` that the pilot receiver
     reads (qampy/signals.py:1430-1760) - frame geometry, pilot sequence / phase pilots, ``shiftfctrs`` / ``synctaps`` after
     :meth:`sync2frame` - on a plain ndarray subclass.  A frame is ``pilot_seq_len`` pilot symbols followed by payload with
-    one phase pilot every ``pilot_ins_rat`` symbols (:1532-1545).  Generation of such signals is out of scope; build one
-    from arrays (a received capture plus the known pilots).
+    one phase pilot every ``pilot_ins_rat`` symbols (:1532-1545).  Build one from arrays (a received capture plus the known
+    pilots); :class:`SignalWithPilots` generates such a signal.
 
     Parameters
     ----------
@@ -537,13 +538,39 @@ class PilotSignal(np.ndarray):
             idx[i * self.frame_len:(i + 1) * self.frame_len] = per_frame[:max(0, min(self.frame_len, self.shape[-1] - i * self.frame_len))]
         return idx
 
-    def get_data(self, frames=None):
-        """Payload symbols of a frame-aligned, 1 sample/symbol signal (qampy/signals.py:1753-1781)."""
-        return np.asarray(self)[:, self._frame_mask(self._idx_dat, frames)].copy()
+    def _split_dev(self, frames, pilots):
+        """Payload or pilots of whole frames through ``hip_dsp.pilot_split_dev`` - the host mask's result: frames in ascending order, each
+        once.  None when the request is not one of whole frames of a complex64 / complex128 signal (the caller then takes the host path)."""
+        from . import _lib
+        from .core import hip_dsp
+        F, L = self.frame_len, self.shape[-1]
+        fr = np.arange(self.nframes) if frames is None else np.unique(np.atleast_1d(frames))
+        if fr.size == 0 or not np.issubdtype(fr.dtype, np.integer) or fr.min() < 0 or (fr.max() + 1) * F > L:
+            return None
+        if self.dtype not in (np.complex64, np.complex128) or self.ndim != 2:
+            return None
+        count = hip_dsp.pilot_counts(F, self._pilot_seq_len, self._pilot_ins_rat)[0 if pilots else 1]
+        if count < 1:
+            return None
+        E = _lib.DeviceArray.from_host(np.ascontiguousarray(np.asarray(self)))
+        out = _lib.DeviceArray((self.shape[0], fr.size * count), self.dtype)
+        hip_dsp.pilot_split_dev(E, F, self._pilot_seq_len, self._pilot_ins_rat, fr, **{"pilots" if pilots else "payload": out})
+        return out.to_host()
 
-    def extract_pilots(self, frames=None):
-        """Pilot symbols of a frame-aligned, 1 sample/symbol signal (qampy/signals.py:1783-1804)."""
-        return np.asarray(self)[:, self._frame_mask(self._idx_pil, frames)].copy()
+    def _split(self, per_frame, frames, method, pilots):
+        if method not in ("pyt", "hip"):
+            raise ValueError("method must be 'pyt' (host) or 'hip' (device), not %r" % (method,))
+        out = self._split_dev(frames, pilots) if method == "hip" else None
+        return np.asarray(self)[:, self._frame_mask(per_frame, frames)].copy() if out is None else out
+
+    def get_data(self, frames=None, method="pyt"):
+        """Payload symbols of a frame-aligned, 1 sample/symbol signal (qampy/signals.py:1753-1781).  ``method="hip"``: gathered on the
+        device (whole frames; a truncated last frame takes the host path)."""
+        return self._split(self._idx_dat, frames, method, False)
+
+    def extract_pilots(self, frames=None, method="pyt"):
+        """Pilot symbols of a frame-aligned, 1 sample/symbol signal (qampy/signals.py:1783-1804); ``method`` as in :meth:`get_data`."""
+        return self._split(self._idx_pil, frames, method, True)
 
     def cal_ser(self, frames=None):
         """Symbol error rate of the payload against ``symbols`` (aligned by construction once the frame is synced)."""
@@ -594,3 +621,124 @@ class PilotSignal(np.ndarray):
         """Linear SNR per mode from the payload, or (``use_pilots``) from the pilots (signals.py:1927-1950)."""
         sig = self._pilot_signal(frames) if use_pilots else self._payload(frames)
         return sig.est_snr(signal_rx, synced=synced, symbols_tx=symbols_tx)
+
+
+class SignalWithPilots(PilotSignal):
+    """
+    ``SignalWithPilots(M, frame_len, pilot_seq_len, pilot_ins_rat, nframes=1, pilot_scale=1, Mpilots=4, dataclass=SignalQAMGrayCoded, nmodes=1,
+    dtype=np.complex128, repeat_data=True, repeat_pilots=True, **kwargs)``: ``nframes`` pilot frames ``(nmodes, nframes * frame_len)`` at one
+    sample per symbol (qampy/signals.py:1430-1530).  Pilots - ``SignalQAMGrayCoded(Mpilots, NP, ...)`` times ``pilot_scale`` - and payload -
+    ``dataclass(M, ND, ...)``, or ``nframes * ND`` symbols without ``repeat_data`` - are made on the device by :class:`SignalQAMGrayCoded` with
+    ``**kwargs`` handed to both, as in the reference (so two PRBS sources start from the same bits), and laid out as frames in one launch
+    (``hip_dsp.pilot_frame_dev``).  ``pilots`` and ``symbols`` hold what the reference's hold: the scaled pilots and the payload, repeated
+    ``nframes`` times.  ``pilot_ins_rat`` 0 or None: a sequence only; ``pilot_seq_len`` 0: position 0 is a phase pilot.
+    ``repeat_pilots=False`` raises ``ValueError`` (the reference fails on it).  Everything :class:`PilotSignal` offers is inherited.
+    """
+
+    def __new__(cls, M, frame_len, pilot_seq_len, pilot_ins_rat, nframes=1, pilot_scale=1, Mpilots=4, dataclass=SignalQAMGrayCoded, nmodes=1,
+                dtype=np.complex128, repeat_data=True, repeat_pilots=True, **kwargs):
+        from .core import hip_dsp
+        _check_dtype(dtype)
+        if not repeat_pilots:
+            raise ValueError("repeat_pilots=False is not supported (the reference fails on it: its pilots then fill one frame only)")
+        NP, ND = hip_dsp.pilot_counts(frame_len, pilot_seq_len, pilot_ins_rat)
+        if int(nframes) != nframes or nframes < 1:
+            raise ValueError("nframes must be a positive whole number")
+        nframes = int(nframes)
+        if NP < 1 or ND < 1:
+            raise ValueError("a frame needs at least one pilot and one payload symbol")
+        pilots = SignalQAMGrayCoded(Mpilots, NP, nmodes=nmodes, dtype=dtype, **kwargs)
+        symbs = dataclass(M, ND if repeat_data else ND * nframes, nmodes=nmodes, dtype=dtype, **kwargs)
+        frame = cls._assemble(np.asarray(pilots), np.asarray(symbs), frame_len, pilot_seq_len, pilot_ins_rat, nframes, pilot_scale, repeat_data)
+        if repeat_data:
+            symbs = np.tile(symbs, (1, nframes))
+        fb = kwargs["fb"] if "fb" in kwargs else symbs.fb
+        fs = kwargs["fs"] if "fs" in kwargs else symbs.fb
+        pilots = np.tile(pilots * pilot_scale, (1, nframes))
+        obj = PilotSignal.__new__(cls, frame, M, fb, fs, frame_len, pilot_seq_len, pilot_ins_rat, pilots, symbols=symbs, Mpilots=Mpilots,
+                                  coded_symbols=symbs.coded_symbols)
+        obj._symbols, obj._pilots = symbs, pilots        # (the signal objects themselves, as in the reference)
+        obj._pilot_scale = pilot_scale
+        return obj
+
+    def __array_finalize__(self, obj):
+        super().__array_finalize__(obj)
+        if obj is not None:
+            self._pilot_scale = getattr(obj, "_pilot_scale", None)
+
+    def recreate_from_np_array(self, arr, **kwargs):
+        out = super().recreate_from_np_array(arr, **kwargs)
+        out._pilot_scale = self._pilot_scale
+        return out
+
+    pilot_scale = property(lambda self: self._pilot_scale)
+
+    @staticmethod
+    def _assemble(pilots, payload, frame_len, pilot_seq_len, pilot_ins_rat, nframes, pilot_scale, repeat_data):
+        """The frames ``(nmodes, nframes * frame_len)`` of ``payload``'s dtype from host rows of pilots and payload, on the device.  The pilots
+        times ``pilot_scale`` are what numpy's product, stored into an array of that dtype, holds: a scale numpy keeps in the array's
+        precision is rounded to it first; the product is then formed in double and rounded once."""
+        from . import _lib
+        from .core import hip_dsp
+        dtype = payload.dtype
+        if np.iscomplexobj(pilot_scale) or np.ndim(pilot_scale) != 0:
+            raise ValueError("pilot_scale must be one real number")
+        scale = float(pilot_scale)
+        if (np.zeros(1, dtype) * pilot_scale).dtype == dtype:
+            scale = float(np.zeros(1, dtype).real.dtype.type(scale))
+        D = _lib.DeviceArray
+        frame = D((payload.shape[0], nframes * int(frame_len)), dtype)
+        hip_dsp.pilot_frame_dev(D.from_host(np.ascontiguousarray(pilots, dtype=dtype)), D.from_host(np.ascontiguousarray(payload)), frame_len, pilot_seq_len,
+                                pilot_ins_rat, nframes, frame, pilot_scale=scale, repeat_data=repeat_data)
+        return frame.to_host()
+
+    @classmethod
+    def from_symbol_array(cls, payload, frame_len, pilot_seq_len, pilot_ins_rat, pilots=None, pilot_idx=None, nframes=1, pilot_scale=1,
+                          payload_is_frame=False, pilot_class=SignalQAMGrayCoded, pilot_kwargs={"M": 4}, payload_class=SignalQAMGrayCoded,
+                          payload_kwargs={}, **kwargs):
+        """
+        Pilot frames around a given payload (qampy/signals.py:1547-1645): ``payload (nmodes, >= ND)`` - an array or a signal object; with
+        ``payload_is_frame`` a whole frame, whose pilot positions become the pilots -, ``pilots`` an array or signal object of ``nmodes``
+        modes or of one, which is then used for all (None: ``pilot_class(pilot_kwargs["M"], NP, ...) / sqrt(pilot_scale)``, as the reference
+        makes them).  Arrays become signal objects through ``from_symbol_array`` of ``pilot_class`` / ``payload_class`` with ``pilot_kwargs`` /
+        ``payload_kwargs`` and ``**kwargs``.  The frame is repeated ``nframes`` times; ``symbols`` holds the ``ND`` payload symbols of one frame.
+        ``pilot_idx`` (free pilot positions) raises ``NotImplementedError``: only the rule geometry is supported.
+        """
+        from .core import hip_dsp
+        if pilot_idx is not None:
+            raise NotImplementedError("pilot_idx (free pilot positions) is not implemented: frames follow pilot_seq_len and pilot_ins_rat")
+        nmodes, N = payload.shape
+        NP, ND = hip_dsp.pilot_counts(frame_len, pilot_seq_len, pilot_ins_rat)
+        if int(nframes) != nframes or nframes < 1:
+            raise ValueError("nframes must be a positive whole number")
+        if NP < 1 or ND < 1:
+            raise ValueError("a frame needs at least one pilot and one payload symbol")
+        assert ND <= N, "data frame is to short for the given frame length"
+        pilot_kwargs, payload_kwargs = dict(pilot_kwargs), dict(payload_kwargs)
+        if "M" in kwargs:
+            assert "M" not in payload_kwargs, "M can not be provided as a argument for payload and signal"
+            payload_kwargs["M"] = kwargs.pop("M")
+        if payload_is_frame:
+            idx_pil, idx_dat = hip_dsp.pilot_positions(frame_len, pilot_seq_len, pilot_ins_rat)
+            pilots = pilot_class.from_symbol_array(np.asarray(payload)[:, idx_pil], **pilot_kwargs, **kwargs)
+            payload = payload_class.from_symbol_array(np.asarray(payload)[:, idx_dat], **payload_kwargs, **kwargs)
+        if pilots is None:
+            pilots = pilot_class(pilot_kwargs["M"], NP, nmodes=nmodes, dtype=payload.dtype, **kwargs) / np.sqrt(pilot_scale)
+        else:
+            if pilots.shape[0] not in (1, nmodes):
+                raise ValueError("Pilots need to have the same number of modes as data or be one mode")
+            if pilots.shape[0] == 1 and nmodes > 1:
+                pilots = np.array(np.vstack([pilots] * nmodes))
+            if not isinstance(pilots, SignalQAM):
+                pilots = pilot_class.from_symbol_array(pilots, **pilot_kwargs, **kwargs)
+        if not isinstance(payload, SignalQAM):
+            payload = payload_class.from_symbol_array(payload, **payload_kwargs, **kwargs)
+        _check_dtype(payload.dtype)
+        if pilots.shape[1] != NP:
+            raise ValueError("a frame holds %d pilots, got %d" % (NP, pilots.shape[1]))
+        frame = cls._assemble(np.asarray(pilots), np.asarray(payload)[:, :ND], frame_len, pilot_seq_len, pilot_ins_rat, int(nframes), 1, True)
+        obj = PilotSignal.__new__(cls, frame, payload.M, payload.fb, payload.fb, frame_len, pilot_seq_len, pilot_ins_rat, pilots,
+                                  symbols=payload[:, :ND].copy(), Mpilots=pilots.M, coded_symbols=payload.coded_symbols)
+        obj._symbols, obj._pilots = payload[:, :ND].copy(), pilots
+        obj._pilot_scale = pilot_scale
+        return obj

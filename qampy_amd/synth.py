@@ -185,6 +185,38 @@ def make_symbols_dev(M, nsym, nmodes=2, order=(15, 23), seed=(None, None), kind=
     return out
 
 
+def make_pilot_frames_dev(M, frame_len, seq_len, ins_rat, nframes=1, nmodes=2, Mpilots=4, order=(15, 23), seed=(None, None), dtype=np.complex64,
+                          repeat_data=True):
+    """
+    Pilot frames made in HBM: what ``SignalWithPilots(M, frame_len, seq_len, ins_rat, nframes, nmodes=nmodes, Mpilots=Mpilots, dtype=dtype,
+    repeat_data=repeat_data, bitclass=PRBSBits, order=order, seed=seed)`` holds, bit for bit.  Pilots and payload are two PRBS sources
+    (:func:`make_symbols_dev`; both start from the seed, as in the reference), the frame is one launch of ``hip_dsp.pilot_frame_dev``.  Nothing
+    is read back.
+
+    Returns a dict of :class:`qampy_amd._lib.DeviceArray`: ``frame (nmodes, nframes * frame_len)``, ``pilots (nmodes, NP)``, ``payload (nmodes,
+    ND)`` - ``nframes * ND`` without ``repeat_data`` -, ``idx_tx`` (the payload's int32 labels, ready for ``cal_metrics_dev``), ``idx_frame``
+    (the labels in the frame's layout, -1 at the pilots), ``alphabet (M,)`` and ``pilot_alphabet (Mpilots,)``; and the geometry: ``frame_len``,
+    ``seq_len``, ``ins_rat``, ``nframes``, ``NP``, ``ND``, ``M``, ``Mpilots``, ``alphabet_host``, ``pilot_alphabet_host``.
+    """
+    from ._lib import DeviceArray
+    from .core import hip_dsp
+    NP, ND = hip_dsp.pilot_counts(frame_len, seq_len, ins_rat)
+    if NP < 1 or ND < 1:
+        raise ValueError("make_pilot_frames_dev: a frame needs at least one pilot and one payload symbol")
+    if int(nframes) != nframes or nframes < 1:
+        raise ValueError("make_pilot_frames_dev: nframes must be a positive whole number")
+    nframes = int(nframes)
+    pil = make_symbols_dev(Mpilots, NP, nmodes=nmodes, order=order, seed=seed, dtype=dtype)
+    pay = make_symbols_dev(M, ND if repeat_data else nframes * ND, nmodes=nmodes, order=order, seed=seed, dtype=dtype)
+    frame = DeviceArray((nmodes, nframes * int(frame_len)), dtype)
+    idx_frame = DeviceArray((nmodes, nframes * int(frame_len)), np.int32)
+    hip_dsp.pilot_frame_dev(pil["symbols"], pay["symbols"], frame_len, seq_len, ins_rat, nframes, frame, repeat_data=repeat_data, labels=pay["idx_tx"],
+                            idx_frame=idx_frame)
+    return dict(frame=frame, pilots=pil["symbols"], payload=pay["symbols"], idx_tx=pay["idx_tx"], idx_frame=idx_frame, alphabet=pay["alphabet"],
+                pilot_alphabet=pil["alphabet"], alphabet_host=pay["alphabet_host"], pilot_alphabet_host=pil["alphabet_host"], frame_len=int(frame_len),
+                seq_len=int(seq_len), ins_rat=int(ins_rat or 0), nframes=nframes, NP=NP, ND=ND, M=M, Mpilots=Mpilots)
+
+
 # ------------------------------------------------------------------------------------------------- SER harness
 def normalise_and_center(E):
     """Per-mode mean removal and unit-power scaling (behaviour of qampy/helpers.py:46-58)."""
