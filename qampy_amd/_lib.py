@@ -371,6 +371,11 @@ def suffix(dtype):
     raise TypeError("unsupported dtype %s (the hot path is exported for float32/64 and complex64/128 only)" % dtype)
 
 
+def cname(suf):
+    """``"c64"`` / ``"c128"``: how the complex entry points spell the ABI suffix of :func:`suffix`."""
+    return "c64" if suf == "32" else "c128"
+
+
 PINNED_MIN_BYTES = 1 << 20        # results below 1 MiB are not worth a pinned buffer
 
 
@@ -403,6 +408,21 @@ def pinned_empty(shape, dtype):
 
 def stream_sync():
     call("qh_stream_sync")
+
+
+class on_stream:
+    """``with on_stream(idx):`` - what the block enqueues goes onto library stream ``idx``; stream 0 is current again afterwards, also after an
+    exception.  (A plain class: it sits on the host's critical path, where a generator-based context manager costs several times as much.)"""
+    __slots__ = ("idx",)
+
+    def __init__(self, idx):
+        self.idx = idx
+
+    def __enter__(self):
+        call("qh_use_stream", self.idx)
+
+    def __exit__(self, *exc):
+        call("qh_use_stream", 0)
 
 
 class DeviceArray:

@@ -66,7 +66,7 @@ def train_equaliser(E, TrSyms, Niter, os, mu, wx, modes, adaptive, symbols, meth
     modes = _as_modes(modes, nmodes)
     err = np.zeros((nmodes, int(TrSyms) * int(Niter)), dtype=ct)
     mu_c = (C.c_float if rt is np.float32 else C.c_double)(mu)
-    _lib.call("qh_train_equaliser_c" + ("64" if suf == "32" else "128"), _lib.ptr(E), nmodes, L, int(TrSyms), int(Niter),
+    _lib.call("qh_train_equaliser_" + _lib.cname(suf), _lib.ptr(E), nmodes, L, int(TrSyms), int(Niter),
               int(os), C.byref(mu_c), _lib.ptr(wx), ntaps, _lib.ptr(modes), modes.size, _adaptive_flag(adaptive),
               _lib.ptr(symbols), symbols.shape[1], _lib.METHOD_ID[method], _lib.ptr(err))
     return err, wx, rt(mu_c.value)
@@ -93,7 +93,7 @@ def train_equaliser_windows(E, starts, win_len, TrSyms, Niter, os, mu, wx0, mode
     err = np.zeros((nwin, nmodes, int(TrSyms) * int(Niter)), dtype=ct)
     wx = np.zeros((nwin,) + wx0.shape, dtype=ct)
     mu_out = np.zeros(nwin, dtype=rt)
-    _lib.call("qh_train_equaliser_windows_c" + ("64" if suf == "32" else "128"), _lib.ptr(E), nmodes, L, _lib.ptr(starts), nwin,
+    _lib.call("qh_train_equaliser_windows_" + _lib.cname(suf), _lib.ptr(E), nmodes, L, _lib.ptr(starts), nwin,
               int(win_len), int(TrSyms), int(Niter), int(os), rt(mu), _lib.ptr(wx0), ntaps, _lib.ptr(modes), modes.size,
               _adaptive_flag(adaptive, False), _lib.ptr(symbols), symbols.shape[1], _lib.METHOD_ID[method], _lib.ptr(wx), _lib.ptr(err),
               _lib.ptr(mu_out))
@@ -118,7 +118,7 @@ def train_equaliser_windows_search(E, starts, win_len, TrSyms, Niter, os, mu, wx
     var = np.zeros((nmodes, starts.size), dtype=np.float64)
     best = np.zeros(nmodes, dtype=np.int32)
     wx = np.zeros((nmodes,) + wx0.shape, dtype=ct)
-    _lib.call("qh_train_equaliser_windows_search_c" + ("64" if suf == "32" else "128"), _lib.ptr(E), nmodes, L, _lib.ptr(starts), starts.size,
+    _lib.call("qh_train_equaliser_windows_search_" + _lib.cname(suf), _lib.ptr(E), nmodes, L, _lib.ptr(starts), starts.size,
               int(win_len), int(TrSyms), int(Niter), int(os), rt(mu), _lib.ptr(wx0), wx0.shape[-1], _lib.ptr(modes), modes.size,
               _adaptive_flag(adaptive, False), _lib.ptr(symbols), symbols.shape[1], _lib.METHOD_ID[method], _lib.ptr(var), _lib.ptr(best), _lib.ptr(wx))
     return var, best, wx
@@ -191,7 +191,7 @@ def make_decision(E, symbols):
     det = np.zeros(L, dtype=ct)
     dist = np.zeros(L, dtype=rt)
     idx = np.zeros(L, dtype=np.int32)
-    _lib.call("qh_make_decision_c" + ("64" if suf == "32" else "128"), _lib.ptr(E), L, _lib.ptr(symbols), symbols.size,
+    _lib.call("qh_make_decision_" + _lib.cname(suf), _lib.ptr(E), L, _lib.ptr(symbols), symbols.size,
               _lib.ptr(det), _lib.ptr(dist), _lib.ptr(idx))
     return det, dist, idx
 
@@ -260,12 +260,9 @@ class ResidentField:
             return darr.to_host()
         ev = _lib.Event()
         ev.record()
-        _lib.call("qh_use_stream", 2)
-        try:
+        with _lib.on_stream(2):
             _lib.call("qh_stream_wait_event", ev.ptr)
             out = darr.to_host(pinned=True, wait=not self.defer)
-        finally:
-            _lib.call("qh_use_stream", 0)
         if self.defer:
             self._pending.append((darr, ev))           # the device array stays alive until the copy has run
         return out
@@ -422,7 +419,7 @@ def gram_build_dev(E, os, ntaps, TrSyms):
     suf, rt, ct = _lib.suffix(E.dtype)
     nmodes, L = E.shape
     g = C.c_void_p()
-    _lib.call("qh_gram_build_c" + ("64" if suf == "32" else "128") + "_dev", E.ptr, nmodes, L, int(os), int(ntaps), int(TrSyms),
+    _lib.call("qh_gram_build_" + _lib.cname(suf) + "_dev", E.ptr, nmodes, L, int(os), int(ntaps), int(TrSyms),
               C.byref(g))
     return g.value
 
@@ -451,7 +448,7 @@ def train_equaliser_dev(E, TrSyms, Niter, os, mu, wx, modes, adaptive, symbols, 
     modes = _as_modes(modes, nmodes)
     args = (E.ptr, nmodes, L, int(TrSyms), int(Niter), int(os), mu.ptr, wx.ptr, ntaps, _lib.ptr(modes), modes.size,
             _adaptive_flag(adaptive), symbols.ptr, symbols.shape[1], _lib.METHOD_ID[method], err.ptr, int(bool(zero_err)))
-    name = "qh_train_equaliser_c" + ("64" if suf == "32" else "128")
+    name = "qh_train_equaliser_" + _lib.cname(suf)
     if pit is not None:
         o = _lib.PitOpts()
         o.phase_seed = -1
@@ -530,7 +527,7 @@ def pit_basis_dev(E, os, ntaps, TrSyms, basis=None, overlap=False):
         n = C.c_size_t(0)
         _lib.call("qh_pit_basis_bytes", nmodes * int(ntaps), C.byref(n))
         basis = DeviceArray((n.value,), np.uint8)
-    _lib.call("qh_pit_basis_c" + ("64" if suf == "32" else "128") + "_dev", E.ptr, nmodes, L, int(os), int(ntaps), int(TrSyms), basis.ptr, int(bool(overlap)))
+    _lib.call("qh_pit_basis_" + _lib.cname(suf) + "_dev", E.ptr, nmodes, L, int(os), int(ntaps), int(TrSyms), basis.ptr, int(bool(overlap)))
     return basis
 
 
@@ -611,7 +608,7 @@ def gram_build_batch_dev(E, os, ntaps, TrSyms):
     suf, rt, ct = _lib.suffix(E.dtype)
     nch, nmodes, L = E.shape
     g = C.c_void_p()
-    _lib.call("qh_gram_build_c" + ("64" if suf == "32" else "128") + "_batch_dev", E.ptr, nch, nmodes, L, int(os), int(ntaps), int(TrSyms),
+    _lib.call("qh_gram_build_" + _lib.cname(suf) + "_batch_dev", E.ptr, nch, nmodes, L, int(os), int(ntaps), int(TrSyms),
               C.byref(g))
     return g.value
 
@@ -629,7 +626,7 @@ def train_equaliser_batch_dev(E, TrSyms, Niter, os, mu, wx, modes, adaptive, sym
     nch, nmodes, L = E.shape
     ntaps = wx.shape[-1]
     modes = _as_modes(modes, nmodes)
-    _lib.call("qh_train_equaliser_c" + ("64" if suf == "32" else "128") + "_batch_dev", E.ptr, nch, nmodes, L, int(TrSyms), int(Niter), int(os),
+    _lib.call("qh_train_equaliser_" + _lib.cname(suf) + "_batch_dev", E.ptr, nch, nmodes, L, int(TrSyms), int(Niter), int(os),
               mu.ptr, wx.ptr, ntaps, _lib.ptr(modes), modes.size, _adaptive_flag(adaptive), symbols.ptr, symbols.shape[1],
               _lib.METHOD_ID[method], err.ptr, int(bool(zero_err)), gram)
 
@@ -638,12 +635,12 @@ def apply_filter_to_signal_dev(E, os, wx, modes, out):
     suf, rt, ct = _lib.suffix(E.dtype)
     nmodes, L = E.shape
     modes = _as_modes(modes, wx.shape[0])
-    _lib.call("qh_apply_filter_c" + ("64" if suf == "32" else "128") + "_dev", E.ptr, nmodes, L, int(os), wx.ptr, wx.shape[-1],
+    _lib.call("qh_apply_filter_" + _lib.cname(suf) + "_dev", E.ptr, nmodes, L, int(os), wx.ptr, wx.shape[-1],
               _lib.ptr(modes), modes.size, out.ptr)
 
 
 def make_decision_dev(E, symbols, det, dist, idx):
     suf, rt, ct = _lib.suffix(E.dtype)
     L = int(np.prod(E.shape))
-    _lib.call("qh_make_decision_c" + ("64" if suf == "32" else "128") + "_dev", E.ptr, L, symbols.ptr, int(np.prod(symbols.shape)),
+    _lib.call("qh_make_decision_" + _lib.cname(suf) + "_dev", E.ptr, L, symbols.ptr, int(np.prod(symbols.shape)),
               det.ptr if det is not None else None, dist.ptr if dist is not None else None, idx.ptr)

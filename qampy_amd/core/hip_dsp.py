@@ -31,7 +31,7 @@ def bps(E, testangles, symbols, N):
     if not (p == 1 or p == L):
         raise ValueError("p must be either 1 or the length of the input signal")
     idx = np.zeros(L, dtype=np.int32)
-    _lib.call("qh_bps_c" + ("64" if suf == "32" else "128"), _lib.ptr(E), L, _lib.ptr(testangles), p, A, _lib.ptr(symbols),
+    _lib.call("qh_bps_" + _lib.cname(suf), _lib.ptr(E), L, _lib.ptr(testangles), p, A, _lib.ptr(symbols),
               symbols.size, int(N), _lib.ptr(idx))
     return idx
 
@@ -73,10 +73,10 @@ def bps_recover_dev(E, Mtestangles, symbols, N, idx, ph, Eout, angles=None, part
     suf, rt, ct = _lib.suffix(E.dtype)
     nm, L = E.shape
     if nparts == 1:
-        _lib.call("qh_bps_recover_c" + ("64" if suf == "32" else "128") + "_dev", E.ptr, nm, L, angles.ptr if angles is not None else None,
+        _lib.call("qh_bps_recover_" + _lib.cname(suf) + "_dev", E.ptr, nm, L, angles.ptr if angles is not None else None,
                   int(Mtestangles), symbols.ptr, int(np.prod(symbols.shape)), int(N), idx.ptr, ph.ptr, Eout.ptr)
     else:
-        _lib.call("qh_bps_recover_part_c" + ("64" if suf == "32" else "128") + "_dev", E.ptr, nm, L, angles.ptr if angles is not None else None,
+        _lib.call("qh_bps_recover_part_" + _lib.cname(suf) + "_dev", E.ptr, nm, L, angles.ptr if angles is not None else None,
                   int(Mtestangles), symbols.ptr, int(np.prod(symbols.shape)), int(N), idx.ptr, ph.ptr, Eout.ptr, int(part), int(nparts))
 
 
@@ -102,27 +102,8 @@ def bps_recover(E, Mtestangles, symbols, N):
         dE.set(E)
         bps_recover_dev(dE, Mtestangles, dsy, N, idx, ph, out, angles=dang)
         return out.to_host(), ph.to_host()
-    # Rows (modes) are independent: row r + 1 goes up (stream 1) while row r is searched (stream 0) and row r - 1 comes back (stream 2, into
-    # pooled pinned memory) - PCIe carries both directions at once; all searches on ONE stream (they share the library's scratch buffers).
-    h_out, h_ph = _lib.pinned_empty((nm, L), ct), _lib.pinned_empty((nm, L), rt)
-    ev_up, ev_done = [_lib.Event() for _ in range(nm)], [_lib.Event() for _ in range(nm)]
-    try:
-        for r in range(nm):
-            _lib.call("qh_use_stream", 1)
-            _lib.call("qh_memcpy_h2d_async", dE.row(r).ptr, E[r].ctypes.data, E[r].nbytes)
-            ev_up[r].record()
-            _lib.call("qh_use_stream", 0)
-            _lib.call("qh_stream_wait_event", ev_up[r].ptr)
-            bps_recover_dev(_row2d(dE, r), Mtestangles, dsy, N, _row2d(idx, r), _row2d(ph, r), _row2d(out, r), angles=dang)
-            ev_done[r].record()
-            _lib.call("qh_use_stream", 2)
-            _lib.call("qh_stream_wait_event", ev_done[r].ptr)
-            _lib.call("qh_memcpy_d2h_async", h_out[r].ctypes.data, out.row(r).ptr, h_out[r].nbytes)
-            _lib.call("qh_memcpy_d2h_async", h_ph[r].ctypes.data, ph.row(r).ptr, h_ph[r].nbytes)
-    finally:
-        _lib.call("qh_use_stream", 0)
-    _lib.sync()
-    return h_out, h_ph
+    return _row_pipeline(E, dE, (out, ph), lambda r: bps_recover_dev(_row2d(dE, r), Mtestangles, dsy, N, _row2d(idx, r), _row2d(ph, r), _row2d(out, r),
+                                                                    angles=dang))
 
 
 def twostage_offsets(Mtestangles, B):
@@ -143,7 +124,7 @@ def bps_twostage_recover_dev(E, Mtestangles, B, symbols, N, idx1, idx2, ph, Eout
     """
     suf, rt, ct = _lib.suffix(E.dtype)
     nm, L = E.shape
-    _lib.call("qh_bps_twostage_recover_c" + ("64" if suf == "32" else "128") + "_dev", E.ptr, nm, L, angles.ptr if angles is not None else None,
+    _lib.call("qh_bps_twostage_recover_" + _lib.cname(suf) + "_dev", E.ptr, nm, L, angles.ptr if angles is not None else None,
               int(Mtestangles), int(B), symbols.ptr, int(np.prod(symbols.shape)), int(N), idx1.ptr, idx2.ptr, ph.ptr, Eout.ptr)
 
 
@@ -170,26 +151,30 @@ def bps_twostage_recover(E, Mtestangles, symbols, N, B=4):
         dE.set(E)
         bps_twostage_recover_dev(dE, Mtestangles, B, dsy, N, idx1, idx2, ph, out, angles=dang)
         return out.to_host(), ph.to_host()
-    # row-pipelined like bps_recover: row r + 1 goes up while row r is searched and row r - 1 comes back into pooled pinned memory
-    h_out, h_ph = _lib.pinned_empty((nm, L), ct), _lib.pinned_empty((nm, L), rt)
+    return _row_pipeline(E, dE, (out, ph), lambda r: bps_twostage_recover_dev(_row2d(dE, r), Mtestangles, B, dsy, N, _row2d(idx1, r), _row2d(idx2, r),
+                                                                             _row2d(ph, r), _row2d(out, r), angles=dang))
+
+
+def _row_pipeline(E, dE, results, search):
+    """Rows (modes) are independent: row r + 1 of the host array ``E`` goes up into ``dE`` (stream 1) while ``search(r)`` enqueues the search of
+    row r (stream 0) and row r - 1 of every DeviceArray in ``results`` comes back (stream 2, into pooled pinned memory) - PCIe carries both
+    directions at once; all searches on ONE stream (they share the library's scratch buffers).  Returns the host arrays, complete."""
+    nm = E.shape[0]
+    back = [_lib.pinned_empty(d.shape, d.dtype) for d in results]
     ev_up, ev_done = [_lib.Event() for _ in range(nm)], [_lib.Event() for _ in range(nm)]
-    try:
-        for r in range(nm):
-            _lib.call("qh_use_stream", 1)
+    for r in range(nm):
+        with _lib.on_stream(1):
             _lib.call("qh_memcpy_h2d_async", dE.row(r).ptr, E[r].ctypes.data, E[r].nbytes)
             ev_up[r].record()
-            _lib.call("qh_use_stream", 0)
-            _lib.call("qh_stream_wait_event", ev_up[r].ptr)
-            bps_twostage_recover_dev(_row2d(dE, r), Mtestangles, B, dsy, N, _row2d(idx1, r), _row2d(idx2, r), _row2d(ph, r), _row2d(out, r), angles=dang)
-            ev_done[r].record()
-            _lib.call("qh_use_stream", 2)
+        _lib.call("qh_stream_wait_event", ev_up[r].ptr)
+        search(r)
+        ev_done[r].record()
+        with _lib.on_stream(2):
             _lib.call("qh_stream_wait_event", ev_done[r].ptr)
-            _lib.call("qh_memcpy_d2h_async", h_out[r].ctypes.data, out.row(r).ptr, h_out[r].nbytes)
-            _lib.call("qh_memcpy_d2h_async", h_ph[r].ctypes.data, ph.row(r).ptr, h_ph[r].nbytes)
-    finally:
-        _lib.call("qh_use_stream", 0)
+            for h, d in zip(back, results):
+                _lib.call("qh_memcpy_d2h_async", h[r].ctypes.data, d.row(r).ptr, h[r].nbytes)
     _lib.sync()
-    return h_out, h_ph
+    return tuple(back)
 
 
 def _row2d(a, r):
@@ -210,7 +195,7 @@ def comp_freq_offset(E, freq_offset, os=1):
     if fo.size != E.shape[0]:
         raise ValueError("one frequency offset per mode (or one for all)")
     out = np.empty_like(E)
-    _lib.call("qh_comp_freq_offset_c" + ("64" if suf == "32" else "128"), _lib.ptr(E), E.shape[0], E.shape[1], _lib.ptr(fo), int(os), _lib.ptr(out))
+    _lib.call("qh_comp_freq_offset_" + _lib.cname(suf), _lib.ptr(E), E.shape[0], E.shape[1], _lib.ptr(fo), int(os), _lib.ptr(out))
     return out
 
 
@@ -224,7 +209,7 @@ def comp_freq_offset_dev(E, fo, os, out):
         raise ValueError("out must have E's shape and dtype")
     if np.dtype(fo.dtype) != np.float64 or int(np.prod(fo.shape)) != E.shape[0]:
         raise ValueError("fo: one float64 offset per mode")
-    _lib.call("qh_comp_freq_offset_c" + ("64" if suf == "32" else "128") + "_dev", E.ptr, E.shape[0], E.shape[1], fo.ptr, int(os), out.ptr)
+    _lib.call("qh_comp_freq_offset_" + _lib.cname(suf) + "_dev", E.ptr, E.shape[0], E.shape[1], fo.ptr, int(os), out.ptr)
 
 
 # ------------------------------------------------------------------------------------------------ blind frequency-offset estimate
@@ -281,7 +266,7 @@ def find_freq_offset_dev(E, os, fft_size, blocks, average_over_modes, fo, stats=
         raise ValueError("stats must be (nmodes, 3) float64")
     if spectrum is not None and (np.dtype(spectrum.dtype) != rt or tuple(spectrum.shape) != (nm, N)):
         raise ValueError("spectrum must be (nmodes, %d) %s" % (N, np.dtype(rt).name))
-    _lib.call("qh_find_freq_offset_c" + ("64" if suf == "32" else "128") + "_dev", E.ptr, nm, L, os, N, B, int(bool(average_over_modes)), fo.ptr,
+    _lib.call("qh_find_freq_offset_" + _lib.cname(suf) + "_dev", E.ptr, nm, L, os, N, B, int(bool(average_over_modes)), fo.ptr,
               stats.ptr if stats is not None else None, spectrum.ptr if spectrum is not None else None)
 
 
@@ -295,7 +280,7 @@ def find_freq_offset(E, os=1, fft_size=2 ** 16, blocks=1, average_over_modes=Tru
     os = _foe_os(os)
     E = np.ascontiguousarray(E)
     fo = np.zeros(E.shape[0], dtype=np.float64)
-    _lib.call("qh_find_freq_offset_c" + ("64" if suf == "32" else "128"), _lib.ptr(E), E.shape[0], E.shape[1], os, N, B, int(bool(average_over_modes)),
+    _lib.call("qh_find_freq_offset_" + _lib.cname(suf), _lib.ptr(E), E.shape[0], E.shape[1], os, N, B, int(bool(average_over_modes)),
               _lib.ptr(fo), None, None)
     return fo
 
@@ -312,7 +297,7 @@ def _cpr_check(name, E, trace, Eout, trace_len):
         raise ValueError("Eout must have E's shape and dtype")
     if tuple(trace.shape) != (E.shape[0], trace_len) or np.dtype(trace.dtype) != rt:
         raise ValueError("trace must be (%d, %d) %s" % (E.shape[0], trace_len, np.dtype(rt).name))
-    return "64" if suf == "32" else "128"
+    return _lib.cname(suf)
 
 
 def vv_recover_dev(E, N, M, trace, Eout):
@@ -334,7 +319,7 @@ def vv_recover_dev(E, N, M, trace, Eout):
     if not 2 <= M <= VV_MMAX:
         raise ValueError("M must be between 2 and %d" % VV_MMAX)
     c = _cpr_check("vv_recover_dev", E, trace, Eout, L - N + 1)
-    _lib.call("qh_vv_recover_c%s_dev" % c, E.ptr, E.shape[0], L, N, M, trace.ptr, Eout.ptr)
+    _lib.call("qh_vv_recover_%s_dev" % c, E.ptr, E.shape[0], L, N, M, trace.ptr, Eout.ptr)
 
 
 def partition16_recover_dev(E, Nblock, trace, Eout):
@@ -351,7 +336,7 @@ def partition16_recover_dev(E, Nblock, trace, Eout):
     if len(E.shape) != 2 or E.shape[1] < 1:
         raise ValueError("partition16_recover_dev works on a 2-d complex array")
     c = _cpr_check("partition16_recover_dev", E, trace, Eout, E.shape[1])
-    _lib.call("qh_partition16_recover_c%s_dev" % c, E.ptr, E.shape[0], E.shape[1], Nblock, trace.ptr, Eout.ptr)
+    _lib.call("qh_partition16_recover_%s_dev" % c, E.ptr, E.shape[0], E.shape[1], Nblock, trace.ptr, Eout.ptr)
 
 
 def _cpr_host(E, run, trace_len):
@@ -408,7 +393,7 @@ def pilot_phase_trace(E, knots, knot_phase):
     big = E.nbytes >= _lib.PINNED_MIN_BYTES                       # results through the pinned pool: one DMA at the link rate each
     out = _lib.pinned_empty(E.shape, E.dtype) if big else np.empty_like(E)
     trace = _lib.pinned_empty(E.shape, E.dtype) if big else np.empty_like(E)
-    _lib.call("qh_pilot_phase_trace_c" + ("64" if suf == "32" else "128"), _lib.ptr(E), E.shape[0], E.shape[1], _lib.ptr(knots), _lib.ptr(kph), knots.size,
+    _lib.call("qh_pilot_phase_trace_" + _lib.cname(suf), _lib.ptr(E), E.shape[0], E.shape[1], _lib.ptr(knots), _lib.ptr(kph), knots.size,
               _lib.ptr(out), _lib.ptr(trace))
     return out, trace
 
@@ -446,10 +431,6 @@ def bits_map_labels(bits_map):
     return alphabet
 
 
-def _c(suf):
-    return "c64" if suf == "32" else "c128"
-
-
 def _demapper(rx_symbs, num_bits, snr, bits_map, minmax):
     rx = np.ascontiguousarray(rx_symbs)
     if rx.ndim != 1 or not np.iscomplexobj(rx):
@@ -460,7 +441,7 @@ def _demapper(rx_symbs, num_bits, snr, bits_map, minmax):
     if not 1 <= int(num_bits) <= nbits:
         raise ValueError("num_bits must be 1 .. bits_map.shape[0]")
     L = np.zeros((rx.size, nbits), dtype=np.float64)
-    name = "qh_soft_l_value_demapper_" + ("minmax_" if minmax else "") + _c(suf)
+    name = "qh_soft_l_value_demapper_" + ("minmax_" if minmax else "") + _lib.cname(suf)
     _lib.call(name, _lib.ptr(rx), rx.size, nbits, float(snr), _lib.ptr(alphabet), alphabet.size, _lib.ptr(L))
     return L if int(num_bits) == nbits else np.ascontiguousarray(L[:, :int(num_bits)])
 
@@ -485,7 +466,7 @@ def estimate_snr(signal_rx, symbols_tx, gray_symbols):
     if rx.ndim != 1 or tx.shape != rx.shape:
         raise ValueError("signal_rx and symbols_tx must be 1-d arrays of the same length")
     res = np.zeros(3, np.float64)
-    _lib.call("qh_estimate_snr_" + _c(suf), _lib.ptr(rx), rx.size, _lib.ptr(tx), tx.size, _lib.ptr(al), al.size, _lib.ptr(res))
+    _lib.call("qh_estimate_snr_" + _lib.cname(suf), _lib.ptr(rx), rx.size, _lib.ptr(tx), tx.size, _lib.ptr(al), al.size, _lib.ptr(res))
     return float(res[0]), float(res[1]), float(res[2])
 
 
@@ -495,7 +476,7 @@ def cal_mi_mc(noise, symbols, N0):
     suf, rt, ct = _lib.suffix(n.dtype)
     al = np.ascontiguousarray(symbols, dtype=ct)
     mi = np.zeros(1, np.float64)
-    _lib.call("qh_cal_mi_mc_" + _c(suf), _lib.ptr(n), n.size, _lib.ptr(al), al.size, float(N0), _lib.ptr(mi))
+    _lib.call("qh_cal_mi_mc_" + _lib.cname(suf), _lib.ptr(n), n.size, _lib.ptr(al), al.size, float(N0), _lib.ptr(mi))
     return float(mi[0])
 
 
@@ -508,7 +489,7 @@ def cal_mi_mc_fast(sig, sig_tx, symbols, N0):
     if tx.shape != x.shape or x.ndim != 1:
         raise ValueError("sig and sig_tx must be 1-d arrays of the same length")
     mi = np.zeros(1, np.float64)
-    _lib.call("qh_cal_mi_mc_fast_" + _c(suf), _lib.ptr(x), _lib.ptr(tx), x.size, _lib.ptr(al), al.size, float(N0), _lib.ptr(mi))
+    _lib.call("qh_cal_mi_mc_fast_" + _lib.cname(suf), _lib.ptr(x), _lib.ptr(tx), x.size, _lib.ptr(al), al.size, float(N0), _lib.ptr(mi))
     return float(mi[0])
 
 

@@ -92,6 +92,8 @@ class ResidentReceiver:
             if o.get("acq_chunk"):
                 o["_acq_chunk_user"] = True        # the caller fixed the chunk length: load() leaves it alone
         self._owner_thread = None                  # set by ReceiverGroup: the stages of this receiver are enqueued by that thread only
+        self.fs = None                             # the receiver's sampling rate (load_resampled)
+        self.filter_aside = True                   # run(overlap=True), tier b: the capture's filter on stream 2 (False: on stream 0, for measurements)
         # Tolerance per stage (round 5).  `tol` bounds what the CALL returns: equaliser output <= tol, taps <= 3 tol, error traces <= 3 tol.
         # The device's stop rule holds the estimated output deviation of a sweep to its `tol` - which is what the LAST stage's filter output needs; an
         # earlier stage returns an error trace and hands on taps, both held to 3 tol, so it is certified at NONFINAL_TOL_FACTOR x tol (2: the error
@@ -117,6 +119,7 @@ class ResidentReceiver:
             self.symbols.append(DeviceArray.from_host(sy))
         self.err = [DeviceArray((nmodes, self.TrSyms[s] * self.Niter[s]), self.ct, zero=True) for s in range(self.nstage)]
         self.eq = DeviceArray((self.modes.size, self.N), self.ct)
+        self.alphabet = self.angles = self.idx = self.idx2 = self.ph = self.out = None
         if Mtestangles and self.carrier != "bps":
             lim = min(self.N, _dsp.VV_NMAX) if self.carrier == "vv" else _dsp.P16_NBLOCK_MAX
             if not 1 <= int(Nbps) <= lim:
@@ -142,6 +145,37 @@ class ResidentReceiver:
                     o.setdefault("segments", 0)
                 else:
                     o.setdefault("segments", _k.pit_auto_segments(self.TrSyms[s_], float(self.mu0[s_]), self.modes.size, cold=bool(o["acquire"])))
+        # ---- what the stages allocate on first use (None until then: nothing is allocated here)
+        self.E_next, self._next_loaded = None, False       # the second input buffer (load_next) and whether it holds the capture that follows
+        self._cd_buf = self._fe_buf = self._fe_mom = self._fe_coef = self._foe_fo = self._foe_stats = self._tx_mom = self._raw_buf = self._raw_mom = None
+        self._idx_tx = self._idx_tx_src = None             # ser() / metrics(): the transmitted indices, cached per symbols_tx object
+        self._sync_ws = {}                                 # buffers of sync="full" (symbols, correlation, peak table, label rows), kept from call to call
+        self._load_power = None                            # tier b: the clean power the last load() read (impair(snr=...) scales it)
+        self._acq_asked = [False] * self.nstage            # tier b: the stage's acquisition chunk is known, or the device has been asked for it once
+        self._gram = self._basis = None                    # what build_gram() made for this capture
+        self._hook_keepalive = self._pass_hook_keepalive = None    # the ctypes callbacks of the training call under way
+        # prepared ahead (run(prefetch=True), _prepare_next): two slots, the acquisition and the eigenbasis of the capture that follows; _ev_main is
+        # recorded by run() on stream 0 (the capture is in place) and awaited by stream 1, _ev_prep[slot] by stream 1 behind the preparation and
+        # awaited by stream 0 when the next run adopts it
+        self._prep, self._prep_ready, self._prep_cur = None, [False, False], 0
+        self._basis_alt = self._ev_main = self._ev_prep = self._use_prep = None
+        # ---- run(overlap=True): the schedule over stream 0 (training), stream 1 (preparation ahead) and stream 2 (filter aside, phase search).
+        # The events (created on first use), who records each and who waits for it:
+        #   _ev_ready    behind the capture's filter: on stream 2 where the filter went aside, else on stream 0.  Stream 2 waits for it in front of the
+        #                pending search, which reads the filter output; stream 0 waits for it (input_free) before an input buffer or the taps copy is
+        #                written, which the filter aside reads.  _filter_pending: a filter went aside and stream 0 has not waited since.
+        #   _ev_trained  on stream 0 behind the copy of the trained taps into _wxy_f; stream 2 waits for it in front of the filter aside.
+        #   _ev_pass     on stream 0 in front of a pass's trainer launch; stream 2 waits for it in front of the part of the search that goes beside it.
+        #   _ev_post     on stream 2 behind the last launch of a search.  Stream 0 waits for it in wait_post() and in front of a filter on stream 0, which
+        #                overwrites what the search read; stream 1 in front of the next preparation.  A filter aside is behind it by stream 2's order.
+        # The pending search: nothing pending -> run(overlap=True): pending (_post_pending, _post_n = 0) -> the next run, tier b, post_parts != 1:
+        # in parts (_post_next of _post_n enqueued, one per on_pass, the rest after the training; _post_mark marks the first and the last) -> the last
+        # launch enqueued: running (_post_running) -> consumed (stream 0 has waited for _ev_post, or the next filter went aside behind it).
+        # _hook_calls: on_pass calls of the run under way; _hook_calls_prev: those of the last run that had any (0: none yet) - the next search's parts.
+        self._ev_ready = self._ev_post = self._ev_trained = self._ev_pass = self._wxy_f = None
+        self._filter_pending = self._post_pending = self._post_running = False
+        self._post_n = self._post_next = self._hook_calls = self._hook_calls_prev = 0
+        self._post_mark = None
         _lib.sync()
 
     # ------------------------------------------------------------------------------------------ data movement
@@ -152,15 +186,27 @@ class ResidentReceiver:
         no call has to wait for the device to say it."""
         E = np.ascontiguousarray(np.asarray(E), dtype=self.ct)
         assert E.shape == (self.nmodes, self.L)
-        self._filter_done()
-        self.E.set(E)
-        if getattr(self, "_prep", None) is not None:
-            self.invalidate()
+        self._capture_to_write().set(E)
         self._acq_asked = [False] * self.nstage
         if self.tier == "b":
-            npow = min(self.L, 4096)
-            power = float(np.mean(np.abs(E[:, :npow].astype(np.complex128)) ** 2))
-            self._load_power = power                   # (impair(snr=...) scales it)
+            self._load_power = float(np.mean(np.abs(E[:, :min(self.L, 4096)].astype(np.complex128)) ** 2))
+        self._capture_written(power=self._load_power)
+
+    def _capture_to_write(self, next_capture=False):
+        """Start of a stage that writes an input buffer: ``self.E``, or ``self.E_next`` with ``next_capture``, with stream 0 behind a filter that
+        may still be reading it on stream 2."""
+        buf = self.E_next if next_capture else self.E
+        if buf is None:
+            raise ValueError("no capture loaded for next_capture=True (load_next first)")
+        self.input_free()
+        return buf
+
+    def _capture_written(self, next_capture=False, power=None):
+        """End of such a stage: what was prepared ahead is dropped.  ``power``, from a stage that changes or first learns the power of the capture
+        in ``self.E``: tier b re-derives the acquisition chunk of every cold fixed-step stage from it by the library's own rule (``load``)."""
+        if self._prep is not None:
+            self.invalidate()
+        if self.tier == "b" and power is not None and not next_capture:
             for s_, o in enumerate(self.pit):
                 if o.get("acquire") and not self.adaptive[s_] and not o.get("_acq_chunk_user"):
                     o["acq_chunk"] = self._acq_chunk_rule(power, float(self.mu0[s_]), o)
@@ -172,16 +218,12 @@ class ResidentReceiver:
         ``load()`` / ``load_next()`` and ``run()``.  ``L`` is the fibre length the capture went through, as ``add_dispersion`` takes it.
         The filter is all-pass, so the power ``load()`` read for tier b's acquisition rule is still the capture's power."""
         from .core.filter import cd_filter_dev
-        buf = getattr(self, "E_next", None) if next_capture else self.E
-        if buf is None:
-            raise ValueError("no capture loaded for next_capture=True (load_next first)")
-        self._filter_done()                        # (a filter on stream 2 may still be reading the buffer)
-        if getattr(self, "_cd_buf", None) is None:
+        buf = self._capture_to_write(next_capture)
+        if self._cd_buf is None:
             self._cd_buf = DeviceArray((self.nmodes, self.L), self.ct)
         cd_filter_dev(buf, self._cd_buf, fs, D, -L, wl0=wl0, N=N)
         buf.copy_from(self._cd_buf)
-        if getattr(self, "_prep", None) is not None:
-            self.invalidate()
+        self._capture_written(next_capture)
 
     def frontend(self, orthonormalize=True, skew=None, sampling_rate=None, pre_filter_bw=None, next_capture=False):
         """Condition the loaded capture in HBM (``self.E``, or ``self.E_next`` with ``next_capture``) as the analog front end does, between
@@ -193,9 +235,7 @@ class ResidentReceiver:
         This stage changes the power.  Tier b: ``_load_power`` and the acquisition chunk of every cold stage are re-derived by the rule of
         ``load()`` from a read-back of the first ``min(L, 4096)`` conditioned samples of every mode, which waits for the stage (not with
         ``next_capture``, as in ``impair``)."""
-        buf = getattr(self, "E_next", None) if next_capture else self.E
-        if buf is None:
-            raise ValueError("no capture loaded for next_capture=True (load_next first)")
+        buf = self._capture_to_write(next_capture)
         if skew is not None:
             skew = tuple(float(v) for v in np.atleast_1d(skew))
             if len(skew) != 2 or not all(np.isfinite(skew)):
@@ -207,8 +247,7 @@ class ResidentReceiver:
             _dsp.pre_filter_bins(self.L, float(pre_filter_bw))
         if skew is not None or pre_filter_bw is not None:
             _dsp.fft_plan(self.L)
-        self._filter_done()                        # (a filter on stream 2 may still be reading the buffer)
-        if (skew is not None or pre_filter_bw is not None) and getattr(self, "_fe_buf", None) is None:
+        if (skew is not None or pre_filter_bw is not None) and self._fe_buf is None:
             self._fe_buf = DeviceArray((self.nmodes, self.L), self.ct)
         cur = buf
         if skew is not None:
@@ -216,25 +255,21 @@ class ResidentReceiver:
         if pre_filter_bw is not None:
             cur = _dsp.pre_filter_dev(cur, buf if cur is not buf else self._fe_buf, pre_filter_bw)
         if orthonormalize:
-            if getattr(self, "_fe_mom", None) is None:
+            if self._fe_mom is None:
                 self._fe_mom = DeviceArray((self.nmodes, 10), np.float64)
                 self._fe_coef = DeviceArray((self.nmodes, 6), np.float64)
             _dsp.orthonormalize_dev(cur, buf, self.os, mom=self._fe_mom, coef=self._fe_coef)
         elif cur is not buf:
             buf.copy_from(cur)
-        if getattr(self, "_prep", None) is not None:
-            self.invalidate()
         if self.tier == "b" and not next_capture:
             npow = min(self.L, 4096)
             head = np.empty((self.nmodes, npow), self.ct)
             for m in range(self.nmodes):
                 _lib.call("qh_memcpy_d2h", head[m].ctypes.data, buf.ptr + m * self.L * head.itemsize, npow * head.itemsize)
-            power = float(np.mean(np.abs(head.astype(np.complex128)) ** 2))
-            self._load_power = power
-            for s_, o in enumerate(self.pit):
-                if o.get("acquire") and not self.adaptive[s_] and not o.get("_acq_chunk_user"):
-                    o["acq_chunk"] = self._acq_chunk_rule(power, float(self.mu0[s_]), o)
-                    self._acq_asked[s_] = True
+            self._load_power = float(np.mean(np.abs(head.astype(np.complex128)) ** 2))
+            self._capture_written(power=self._load_power)
+        else:
+            self._capture_written(next_capture)
 
     def compensate_foe(self, fft_size=2 ** 16, blocks="all", average_over_modes=True, next_capture=False):
         """Estimate the frequency offset of the loaded capture in HBM (``self.E``, or ``self.E_next`` with ``next_capture``) at the receiver's
@@ -242,18 +277,14 @@ class ResidentReceiver:
         ``load()`` / ``load_next()`` (or ``compensate_cd``) and ``run()``, with no read-back between them.  ``fft_size`` and ``blocks`` as in
         ``hip_dsp.foe_plan`` (``"all"``: the spectrum averaged over every whole block of the capture).  The rotation leaves the power as it
         is, so tier b's acquisition rule still holds.  The offsets and the peak statistics stay on the device: :attr:`foe` reads them."""
-        buf = getattr(self, "E_next", None) if next_capture else self.E
-        if buf is None:
-            raise ValueError("no capture loaded for next_capture=True (load_next first)")
+        buf = self._capture_to_write(next_capture)
         N, B = _dsp.foe_plan(self.L, fft_size, blocks)
-        self._filter_done()                        # (a filter on stream 2 may still be reading the buffer)
-        if getattr(self, "_foe_fo", None) is None:
+        if self._foe_fo is None:
             self._foe_fo = DeviceArray((self.nmodes,), np.float64, zero=True)
             self._foe_stats = DeviceArray((self.nmodes, 3), np.float64, zero=True)
         _dsp.find_freq_offset_dev(buf, self.os, N, B, average_over_modes, self._foe_fo, stats=self._foe_stats)
         _dsp.comp_freq_offset_dev(buf, self._foe_fo, self.os, buf)
-        if getattr(self, "_prep", None) is not None:
-            self.invalidate()
+        self._capture_written(next_capture)
 
     def impair(self, fs, snr=None, freq_off=None, lwdth=None, dgd=None, theta=np.pi / 3.731, modal_delay=None, seed=0, source=None,
                next_capture=False, power=None, tx=None):
@@ -275,9 +306,7 @@ class ResidentReceiver:
         applied first, to the source or in place, and every mode is then centred and scaled to unit mean power (``row_moments_dev`` /
         ``center_scale_dev``): the modulator's output carries about a tenth of unit power, and the trainers' radii assume unit power.  The
         channel impairments follow on that field; tier b's clean power is then 1."""
-        buf = getattr(self, "E_next", None) if next_capture else self.E
-        if buf is None:
-            raise ValueError("no capture loaded for next_capture=True (load_next first)")
+        buf = self._capture_to_write(next_capture)
         src = buf if source is None else source
         if tuple(src.shape) != (self.nmodes, self.L) or np.dtype(src.dtype) != np.dtype(self.ct):
             raise ValueError("source must be a (%d, %d) %s DeviceArray" % (self.nmodes, self.L, np.dtype(self.ct).name))
@@ -291,35 +320,28 @@ class ResidentReceiver:
         if tx is not None:
             clean = 1.0
         elif self.tier == "b" and snr is not None and not next_capture:
-            clean = getattr(self, "_load_power", None) if power is None else float(power)
+            clean = self._load_power if power is None else float(power)
             if clean is None:
                 raise ValueError("tier b needs the clean capture's power for its acquisition rule: power=..., or load() first")
-        self._filter_done()                        # (a filter on stream 2 may still be reading the buffer)
-        if (modal_delay is not None or dgd is not None) and getattr(self, "_cd_buf", None) is None:
+        if (modal_delay is not None or dgd is not None) and self._cd_buf is None:
             self._cd_buf = DeviceArray((self.nmodes, self.L), self.ct)
         if tx is not None:
             from .core import resample as _rs
-            if getattr(self, "_tx_mom", None) is None:
+            if self._tx_mom is None:
                 self._tx_mom = DeviceArray((self.nmodes, 3), np.float64)
             _dsp.sim_tx_response_dev(src, buf, fs, **tx)
             _rs.center_scale_dev(buf, _rs.row_moments_dev(buf, self._tx_mom), power=1.0)
             src = buf
         _dsp.simulate_transmission_dev(src, buf, fs / self.os, fs, snr=snr, freq_off=freq_off, lwdth=lwdth, dgd=dgd, theta=theta, modal_delay=modal_delay,
-                                       seed=seed, tmp=getattr(self, "_cd_buf", None))
-        if getattr(self, "_prep", None) is not None:
-            self.invalidate()
-        if self.tier == "b" and snr is not None and not next_capture:
-            noisy = clean * _dsp.snr_power_factor(snr, self.os)
-            for s_, o in enumerate(self.pit):
-                if o.get("acquire") and not self.adaptive[s_] and not o.get("_acq_chunk_user"):
-                    o["acq_chunk"] = self._acq_chunk_rule(noisy, float(self.mu0[s_]), o)
-                    self._acq_asked[s_] = True
+                                       seed=seed, tmp=self._cd_buf)
+        noisy = clean * _dsp.snr_power_factor(snr, self.os) if (self.tier == "b" and snr is not None and not next_capture) else None
+        self._capture_written(next_capture, power=noisy)
 
     @property
     def foe(self):
         """``(offset[nmodes], stats[nmodes, 3])`` of the last :meth:`compensate_foe`, read back after a sync: the offset taken out of every
         mode in units of the symbol rate, and per mode the peak's bin, its power and the total power of the fourth-power spectrum."""
-        if getattr(self, "_foe_fo", None) is None:
+        if self._foe_fo is None:
             raise ValueError("compensate_foe has not run")
         _lib.sync()
         return self._foe_fo.to_host(), self._foe_stats.to_host()
@@ -335,7 +357,7 @@ class ResidentReceiver:
         Tier b: the loaded capture has unit power by construction, so the acquisition rule of ``load()`` is given the power 1.0 - it stays a
         function of values the host knows."""
         from .core import resample as _rs
-        fs = getattr(self, "fs", None) if fs is None else fs
+        fs = self.fs if fs is None else fs
         if fs is None:
             raise ValueError("load_resampled needs the receiver's sampling rate: fs=..., or set rx.fs")
         E_raw = np.ascontiguousarray(np.asarray(E_raw), dtype=self.ct)
@@ -351,27 +373,20 @@ class ResidentReceiver:
             if not 0 < beta <= 1:
                 raise ValueError("beta needs to be in interval (0,1]")
             h, gain = _rs.rrcos_taps(taps, up * fs_in, self.os / fs, beta), (1 if fftconv else up)
-        if next_capture and getattr(self, "E_next", None) is None:
+        if next_capture and self.E_next is None:
             self.E_next = DeviceArray((self.nmodes, self.L), self.ct)
-        buf = self.E_next if next_capture else self.E
-        if getattr(self, "_raw_buf", None) is None or self._raw_buf.shape != E_raw.shape:
+        if self._raw_buf is None or self._raw_buf.shape != E_raw.shape:
             self._raw_buf = DeviceArray(E_raw.shape, self.ct)
             self._raw_mom = DeviceArray((self.nmodes, 3), np.float64)
-        self._filter_done()                        # (a filter on stream 2 may still be reading the buffer)
+        buf = self._capture_to_write(next_capture)
         self._raw_buf.set(E_raw)
         _rs.resample_dev(self._raw_buf, buf, h, up, down, gain)
         _rs.center_scale_dev(buf, _rs.row_moments_dev(buf, self._raw_mom), power=1.0)
-        if getattr(self, "_prep", None) is not None:
-            self.invalidate()
         if next_capture:
             self._next_loaded = True
-            return
-        self._acq_asked = [False] * self.nstage
-        if self.tier == "b":
-            for s_, o in enumerate(self.pit):
-                if o.get("acquire") and not self.adaptive[s_] and not o.get("_acq_chunk_user"):
-                    o["acq_chunk"] = self._acq_chunk_rule(1.0, float(self.mu0[s_]), o)
-                    self._acq_asked[s_] = True
+        else:
+            self._acq_asked = [False] * self.nstage
+        self._capture_written(next_capture, power=1.0)
 
     def _acq_chunk_rule(self, power, mu, o):
         return _k.pit_acq_chunk(power, mu, self.nmodes * self.Ntaps, self.rt, o.get("gear"), o.get("acq_bound"))
@@ -399,7 +414,6 @@ class ResidentReceiver:
         if self.tier == "a":
             # shared table only when a block form will read it (>= 128 steps) and it fits the library's scratch budget - otherwise
             # the trainers chunk the sweep themselves (csrc/train_impl.h: gram_budget), which a caller's table would switch off
-            import os as _os
             budget = _lib.gram_budget_gb() * 2 ** 30
             fits = self.TrSyms[0] * 1024 * (np.dtype(self.ct).itemsize // 8) <= budget
             if len(set(self.TrSyms)) == 1 and self.TrSyms[0] >= 128 and fits and _lib.get_form("trainer") != 1:
@@ -407,7 +421,7 @@ class ResidentReceiver:
         elif len(set(self.TrSyms)) == 1 and self.nmodes * self.Ntaps <= 128:
             # tier b builds what its passes need itself (no Gram table in the throughput form, csrc/train_seg.h); what the stages
             # share is the eigenbasis of the capture's input covariance for the coarse correction
-            self._basis = _k.pit_basis_dev(self.E, self.os, self.Ntaps, self.TrSyms[0], getattr(self, "_basis", None), overlap=True)
+            self._basis = _k.pit_basis_dev(self.E, self.os, self.Ntaps, self.TrSyms[0], self._basis, overlap=True)
             for o in self.pit:
                 o["basis"] = self._basis.ptr
 
@@ -421,7 +435,7 @@ class ResidentReceiver:
         tb = self.tier == "b"
         self._bound()
         opts = {k: v for k, v in self.pit[stage].items() if not k.startswith("_")} if tb else None
-        if tb and stage == 0 and getattr(self, "_use_prep", None) is not None:
+        if tb and stage == 0 and self._use_prep is not None:
             opts["prepared"] = self._use_prep.ptr
             self._use_prep = None
         fired, failed = [False], []
@@ -453,7 +467,7 @@ class ResidentReceiver:
             opts["on_pass0"] = _C.cast(self._hook_keepalive, _C.c_void_p).value
         _k.train_equaliser_dev(self.E, self.TrSyms[stage], self.Niter[stage], self.os, self.mu[stage], self.wxy, self.modes,
                                self.adaptive[stage], self.symbols[stage], self.methods[stage], self.err[stage],
-                               gram=getattr(self, "_gram", None), pit=opts, report=self.pit_report[stage] if tb else None)
+                               gram=self._gram, pit=opts, report=self.pit_report[stage] if tb else None)
         if hook is not None and not fired[0]:
             fired[0] = True
             hook()
@@ -462,13 +476,11 @@ class ResidentReceiver:
         if tb:
             self.pit_timing[stage] = _k.pit_last_timing()      # host-side copy of the HIP-event times: no synchronisation
             o = self.pit[stage]
-            asked = getattr(self, "_acq_asked", None) or [False] * self.nstage
-            if o.get("acquire") and not o.get("acq_chunk") and not self.adaptive[stage] and not asked[stage]:
+            if o.get("acquire") and not o.get("acq_chunk") and not self.adaptive[stage] and not self._acq_asked[stage]:
                 # a capture that was put into self.E directly (device-side synthesis, tests): the chunk length the device derived for it is
                 # read back ONCE (this synchronises: the one read of the receiver's life, whatever the report says - a sweep the library
                 # sent to the exact form has no acquisition to report and is not asked again); load() derives it on the host instead
-                asked[stage] = True
-                self._acq_asked = asked
+                self._acq_asked[stage] = True
                 a = self.pit_report[stage].read()["acquisition"]
                 if a["chunks"] > 0 and a["steps"] > 0:
                     o["acq_chunk"] = int(a["steps"] // a["chunks"])
@@ -517,17 +529,25 @@ class ResidentReceiver:
         ``load_next(c1)``, ``run()``, ``load_next(c2)``, ``run()``, ..."""
         E = np.ascontiguousarray(np.asarray(E), dtype=self.ct)
         assert E.shape == (self.nmodes, self.L)
-        if getattr(self, "E_next", None) is None:
+        if self.E_next is None:
             self.E_next = DeviceArray((self.nmodes, self.L), self.ct)
-        self._filter_done()                        # (the buffer may be the capture a filter on stream 2 is still reading)
-        self.E_next.set(E)
+        self._capture_to_write(next_capture=True).set(E)        # (the buffer may be the capture a filter on stream 2 is still reading)
         self._next_loaded = True
 
-    def _filter_done(self):
-        """run(overlap=True) leaves the filter of the last capture on stream 2: stream 0 waits for it before an input buffer is written."""
-        if getattr(self, "_filter_pending", False):
+    def input_free(self):
+        """run(overlap=True) leaves the filter of the last capture on stream 2: stream 0 waits for it before an input buffer is written.  The
+        receiver's own loading and conditioning methods do that themselves; a caller needs it after ``run(overlap=True)`` before writing
+        ``rx.E`` or ``rx.E_next`` any other way (``rx.E.copy_from(...)``, a kernel of its own on stream 0)."""
+        if self._filter_pending:
             _lib.call("qh_stream_wait_event", self._ev_ready.ptr)
             self._filter_pending = False
+
+    def release_thread_state(self):
+        """The receiver's worker thread is gone (ReceiverGroup.close) and with it that thread's library streams and scratch buffers: give up what
+        pointed into them - the Gram table, the overlap events and flags - and the binding to the thread."""
+        self._gram = self._ev_ready = self._ev_post = self._ev_trained = None
+        self._filter_pending = self._post_pending = self._post_running = False
+        self._owner_thread = None
 
     def invalidate(self):
         """Forget what was prepared ahead (after the capture in ``self.E`` / ``self.E_next`` was changed by hand)."""
@@ -539,7 +559,7 @@ class ResidentReceiver:
         32 compute units free for exactly that, csrc/train_pit.h) instead of in front of the next capture's passes (qh_pit_prepare_*_dev).  The next
         capture is ``E_next`` (``load_next``), or - a receiver fed the same resident capture again and again, as bench.py does - ``E`` itself."""
         o = self.pit[0]
-        if self.tier != "b" or not o.get("acquire") or self.adaptive[0] or self.ct != np.complex64 or not getattr(self, "_basis", None):
+        if self.tier != "b" or not o.get("acquire") or self.adaptive[0] or self.ct != np.complex64 or not self._basis:
             return
         if not (o.get("acq_chunk") and o.get("mu_hint") and o.get("segments", 0) > 1):
             return
@@ -549,11 +569,10 @@ class ResidentReceiver:
         need = _k.pit_prepare_bytes(self.nmodes, self.Ntaps, amax, self.ct)
         if self._prep[slot] is None or self._prep[slot].nbytes < need:
             self._prep[slot] = DeviceArray((need,), np.uint8)
-        nxt = self.E_next if getattr(self, "_next_loaded", False) else self.E
-        _lib.call("qh_use_stream", 1)             # (_ev_main: recorded by run() on stream 0 when the next capture was in place)
-        try:
+        nxt = self.E_next if self._next_loaded else self.E
+        with _lib.on_stream(1):                   # (_ev_main: recorded by run() on stream 0 when the next capture was in place)
             _lib.call("qh_stream_wait_event", self._ev_main.ptr)
-            if getattr(self, "_post_running", False):
+            if self._post_running:
                 _lib.call("qh_stream_wait_event", self._ev_post.ptr)        # (the previous capture's phase search: see run)
             # (NOT behind the first trainer launch like the parts of the phase search: its chip-wide kernels - setup, Gram terms, covariance - then share
             # the ~70 us of analysis behind passes 0 and 1 with the control path, which is the critical path: gaps of 130 / 123 instead of 90 us,
@@ -563,19 +582,17 @@ class ResidentReceiver:
             if ok:
                 self._basis_alt = _k.pit_basis_dev(nxt, self.os, self.Ntaps, self.TrSyms[0], self._basis_alt, overlap=False)
                 self._ev_prep[slot].record()
-        finally:
-            _lib.call("qh_use_stream", 0)
         self._prep_ready[slot] = bool(ok)
 
     def _prep_init(self):
-        if getattr(self, "_prep", None) is None:
+        if self._prep is None:
             self._prep, self._prep_ready, self._prep_cur = [None, None], [False, False], 0
             self._basis_alt, self._ev_main, self._ev_prep = None, _lib.Event(), [_lib.Event(), _lib.Event()]
 
     def _adopt_prepared(self):
         """Start of a run: if the previous run prepared this capture, its eigenbasis and its acquisition are there already."""
         self._use_prep = None
-        if getattr(self, "_prep", None) is None:
+        if self._prep is None:
             return False
         slot = 1 - self._prep_cur
         if not self._prep_ready[slot]:
@@ -601,7 +618,9 @@ class ResidentReceiver:
         a pass are complete after ``wait_post()`` (enqueues what is pending; stream 0 waits for it) or ``fetch()`` (the host waits
         too).  Bit-identical to ``overlap=False``: the same kernels on the same data, in another order.  The two-stage search (``Bbps``) has
         no part-wise form: where the pending search would go beside the passes in parts (tier b, ``post_parts``), it goes as one launch
-        (``nparts = 1``) with the last of them.
+        (``nparts = 1``) with the last of them.  Tier b leaves the capture's filter on stream 2 too, still reading the input buffer when this
+        call returns: before writing ``rx.E`` or ``rx.E_next`` other than through the receiver's own loading and conditioning methods, call
+        ``input_free()``.
 
         ``prefetch=True`` (tier b, consecutive captures): the acquisition and the eigenbasis of the NEXT capture are enqueued on stream 1 at the
         start of this run and adopted by the next one (``_prepare_next``); results bit-identical to ``prefetch=False``.
@@ -625,21 +644,19 @@ class ResidentReceiver:
         # trainer launches of the previous capture less two (one may have been enqueued in vain ahead of the decision that ended a sweep; the last part
         # also unwraps and de-rotates and should not hold up this capture's filter, which overwrites what it reads); what is left when the training is
         # over is enqueued then.  Bit-identical to one launch.
-        parts_mode = self.tier == "b" and int(getattr(self, "post_parts", 0)) != 1
+        parts_mode = self.tier == "b" and int(self.post_parts) != 1
         self._hook_calls = 0
-        if parts_mode and getattr(self, "_post_pending", False):
-            fixed = int(getattr(self, "post_parts", 0))
-            self._post_n = fixed if fixed > 1 else max(1, min(16, int(getattr(self, "_hook_calls_prev", 10)) - 2))
+        if parts_mode and self._post_pending:
+            fixed = int(self.post_parts)
+            self._post_n = fixed if fixed > 1 else max(1, min(16, (self._hook_calls_prev or 10) - 2))
             self._post_next, self._post_mark = 0, m
-        if getattr(self, "_ev_pass", None) is None:
+        if self._ev_pass is None:
             self._ev_pass = _lib.Event()
 
         def on_pass(sweep, p):
             self._hook_calls += 1
-            pend = parts_mode and getattr(self, "_post_pending", False)
-            if pend:                              # (nothing to gate: no packet on stream 0 either)
-                self._ev_pass.record()            # stream 0: in front of the trainer launch of this pass
-            if pend:
+            if parts_mode and self._post_pending:     # (else nothing to gate: no packet on stream 0 either)
+                self._ev_pass.record()                # stream 0: in front of the trainer launch of this pass
                 self._post_part(gated=True)
 
         def side_work():
@@ -663,40 +680,38 @@ class ResidentReceiver:
             self.train(s, hook=side_work if (defer and s == 0) else None, pass_hook=on_pass if parts_mode else None)
             m("train%d" % s)
         if parts_mode:
-            self._hook_calls_prev = self._hook_calls if self._hook_calls > 0 else getattr(self, "_hook_calls_prev", 9)
+            self._hook_calls_prev = self._hook_calls or self._hook_calls_prev or 9
             self._enqueue_post(m)                 # parts the passes did not take
         # The filter of this capture.  One capture at a time it follows the training on stream 0.  Consecutive captures (tier b, overlap): it goes onto
         # stream 2 - IN FRONT of this capture's phase search, which reads its output, and behind the previous capture's search, which read the buffer it
         # overwrites: the stream's own order is all the ordering those need - with a private copy of the taps (the next run's reset() restores the start
         # taps), so that stream 0 goes straight on to the next capture: the filter (87 us chip-wide at C3) and its launch gaps were ~0.1 ms of the ~0.2 ms
         # between the last pass of a capture and the first pass of the next one (round 6; profiles/r06_c3_timeline.txt).  Bit-identical.
-        aside = bool(overlap and self.Mtestangles and self.tier == "b" and getattr(self, "filter_aside", True))
+        aside = bool(overlap and self.Mtestangles and self.tier == "b" and self.filter_aside)
         if aside:
-            if getattr(self, "_wxy_f", None) is None:
+            if self._wxy_f is None:
                 self._wxy_f = DeviceArray(self.wxy.shape, self.ct)
-            if getattr(self, "_ev_trained", None) is None:
+            if self._ev_trained is None:
                 self._ev_trained = _lib.Event()
-            if getattr(self, "_ev_post", None) is None:
+            if self._ev_post is None:
                 self._ev_ready, self._ev_post = _lib.Event(), _lib.Event()
+            self.input_free()                      # the previous capture's filter, a whole training ago, read the taps copy
             self._wxy_f.copy_from(self.wxy)
             self._ev_trained.record()
-            _lib.call("qh_use_stream", 2)
-            try:
+            with _lib.on_stream(2):
                 _lib.call("qh_stream_wait_event", self._ev_trained.ptr)
                 _k.apply_filter_to_signal_dev(self.E, self.os, self._wxy_f, self.modes, self.eq)
                 m("apply")
-                self._ev_ready.record()            # stream 2: the filter has read the capture and written its output (load_next / load wait for it)
-            finally:
-                _lib.call("qh_use_stream", 0)
+                self._ev_ready.record()            # stream 2: the filter has read the capture and written its output (input_free waits for it)
             self._post_running = False             # (the previous search is in front of this filter on stream 2; wait_post() waits for the NEW search's event)
             self._filter_pending = True
         else:
-            if getattr(self, "_post_running", False):
+            if self._post_running:
                 _lib.call("qh_stream_wait_event", self._ev_post.ptr)        # the filter output of the previous pass has been consumed
                 self._post_running = False
             self._apply()
             m("apply")
-        if prefetch and getattr(self, "_next_loaded", False):
+        if prefetch and self._next_loaded:
             # the capture load_next() brought - prepared above, where that was possible - is the next one to be processed; the old one's buffer takes
             # the next load_next()
             self.E, self.E_next = self.E_next, self.E
@@ -707,7 +722,7 @@ class ResidentReceiver:
             self._recover()
             m("bps")
             return
-        if getattr(self, "_ev_post", None) is None:
+        if self._ev_post is None:
             self._ev_ready, self._ev_post = _lib.Event(), _lib.Event()
         if not aside:
             self._ev_ready.record()               # stream 0 up to here: the filter output the pending phase search reads
@@ -717,10 +732,8 @@ class ResidentReceiver:
     def _post_part(self, gated):
         """The next part of the pending phase search onto stream 2; ``gated``: behind ``_ev_pass`` (recorded in front of the trainer launch that is
         about to go onto stream 0)."""
-        i, n = self._post_next, self._post_n
-        mark = getattr(self, "_post_mark", None)
-        _lib.call("qh_use_stream", 2)
-        try:
+        i, n, mark = self._post_next, self._post_n, self._post_mark
+        with _lib.on_stream(2):
             if gated:
                 _lib.call("qh_stream_wait_event", self._ev_pass.ptr)
             if i == 0:
@@ -732,23 +745,20 @@ class ResidentReceiver:
                 if mark:
                     mark("post_end")
                 self._ev_post.record()
-        finally:
-            _lib.call("qh_use_stream", 0)
         self._post_next = i + 1
         if i == n - 1:
             self._post_pending, self._post_running = False, True
 
     def _enqueue_post(self, mark=None):
-        if not getattr(self, "_post_pending", False):
+        if not self._post_pending:
             return
-        if getattr(self, "_post_n", 0) and getattr(self, "_post_next", 0) > 0:      # a search already under way in parts: the rest of them, now
-            while getattr(self, "_post_pending", False):
+        if self._post_n and self._post_next > 0:      # a search already under way in parts: the rest of them, now
+            while self._post_pending:
                 self._post_part(gated=False)
             self._post_n = 0
             return
         self._post_n = 0
-        _lib.call("qh_use_stream", 2)             # (_ev_ready: recorded behind the filter of the pass whose phase search is pending)
-        try:
+        with _lib.on_stream(2):                   # (_ev_ready: recorded behind the filter of the pass whose phase search is pending)
             _lib.call("qh_stream_wait_event", self._ev_ready.ptr)
             if mark:
                 mark("post_begin")
@@ -756,15 +766,13 @@ class ResidentReceiver:
             if mark:
                 mark("post_end")
             self._ev_post.record()
-        finally:
-            _lib.call("qh_use_stream", 0)
         self._post_pending, self._post_running = False, True
 
     def wait_post(self, mark=None):
         """After ``run(overlap=True)``: enqueue the pending phase search; work enqueued from here on (stream 0) sees its results (and the filter's)."""
         self._enqueue_post(mark)
-        self._filter_done()
-        if getattr(self, "_post_running", False):
+        self.input_free()
+        if self._post_running:
             _lib.call("qh_stream_wait_event", self._ev_post.ptr)
             self._post_running = False
 
@@ -788,16 +796,9 @@ class ResidentReceiver:
         (``qampy_amd.core.ber_functions.cal_ser_dev``); needs the alphabet.  ``sync``: ``"window"`` - bounded search on decisions -
         or ``"full"`` - the full cross-correlation, any delay, the pattern continued periodically.  Returns one dict per row."""
         from .core import ber_functions as _ber
-        if self.alphabet_host is None:
-            raise ValueError("ser() needs the alphabet")
-        if getattr(self, "alphabet", None) is None:
-            self.alphabet = DeviceArray.from_host(self.alphabet_host)
-        self.wait_post()
-        if getattr(self, "_idx_tx", None) is None or self._idx_tx_src is not symbols_tx:
-            self._idx_tx = _ber.tx_indices_dev(np.ascontiguousarray(symbols_tx, dtype=self.ct), self.alphabet)
-            self._idx_tx_src = symbols_tx
+        self._prepare_tx(symbols_tx)
         return _ber.cal_ser_dev(self.out if self.Mtestangles else self.eq, self._idx_tx, self.alphabet, maxlag, window, trim, sync=sync,
-                                sync_ws=self._sync_workspace())
+                                sync_ws=self._sync_ws)
 
     def metrics(self, symbols_tx, snr_db=None, maxlag=256, window=4096, trim=0, llr_minmax=False, sync="window"):
         """Signal-quality metrics (SER, BER, EVM, SNR estimate, GMI, MI) of the recovered (else equalised) rows against the
@@ -806,21 +807,20 @@ class ResidentReceiver:
         from .core import ber_functions as _ber
         self._prepare_tx(symbols_tx)
         return _ber.cal_metrics_dev(self.out if self.Mtestangles else self.eq, self._idx_tx, self.alphabet, snr_db, maxlag, window, trim,
-                                    llr_minmax, sync=sync, sync_ws=self._sync_workspace())
+                                    llr_minmax, sync=sync, sync_ws=self._sync_ws)
 
     def _sync_workspace(self):
-        """Buffers of ``sync="full"`` (symbols, correlation, peak table, label rows), kept so that a repeated call allocates nothing."""
-        return self.__dict__.setdefault("_sync_ws", {})
+        return self._sync_ws
 
     def _prepare_tx(self, symbols_tx):
         """Alphabet and transmitted indices in HBM (cached per ``symbols_tx`` object), after the pending post-processing."""
         from .core import ber_functions as _ber
         if self.alphabet_host is None:
-            raise ValueError("the metrics need the alphabet")
-        if getattr(self, "alphabet", None) is None:
+            raise ValueError("ser() and the metrics need the alphabet")
+        if self.alphabet is None:
             self.alphabet = DeviceArray.from_host(self.alphabet_host)
         self.wait_post()
-        if getattr(self, "_idx_tx", None) is None or self._idx_tx_src is not symbols_tx:
+        if self._idx_tx is None or self._idx_tx_src is not symbols_tx:
             self._idx_tx = _ber.tx_indices_dev(np.ascontiguousarray(symbols_tx, dtype=self.ct), self.alphabet)
             self._idx_tx_src = symbols_tx
 
@@ -944,15 +944,9 @@ class ReceiverGroup:
         for t in self._threads:
             t.join(timeout=10.)
         self._threads = []
-        for r in self.rx:                          # what pointed into the worker threads' (now released) scratch buffers and streams
-            for name in ("_gram", "_ev_post", "_ev_ready", "_ev_trained"):
-                if hasattr(r, name):
-                    setattr(r, name, None)
-            for name in ("_post_pending", "_post_running", "_filter_pending"):
-                if hasattr(r, name):
-                    setattr(r, name, False)
-            if hasattr(r, "_owner_thread"):
-                r._owner_thread = None
+        for r in self.rx:
+            if hasattr(r, "release_thread_state"):
+                r.release_thread_state()
 
     def __del__(self):
         try:
@@ -1006,6 +1000,7 @@ class ChannelBank:
             self.ph = DeviceArray((self.nch, nsel, self.N), self.rt)
             self.out = DeviceArray((self.nch, nsel, self.N), self.ct)
         self._gram = None
+        self._taps_b = self._ev_trained = self._ev_post = None      # run_pipelined: two copies of the taps and their events, made on first use
         _lib.sync()
 
     def load(self, ch, E):
@@ -1035,15 +1030,13 @@ class ChannelBank:
         built in, whose workgroups claim every vector register of a SIMD.  Same results as :meth:`run`; enqueue only
         (``_lib.sync()`` to wait).
         """
-        from ._lib import Event
         r = self.rx
-        if getattr(self, "_taps_b", None) is None:
+        if self._taps_b is None:
             self._taps_b = [DeviceArray(self.wxy.shape, self.ct) for _ in range(2)]
-            self._ev_trained, self._ev_post = [Event(), Event()], [Event(), Event()]
+            self._ev_trained, self._ev_post = [_lib.Event(), _lib.Event()], [_lib.Event(), _lib.Event()]
         try:
             for k in range(steps):
                 p = k & 1
-                _lib.call("qh_use_stream", 0)
                 if k >= 2:
                     _lib.call("qh_stream_wait_event", self._ev_post[p].ptr)        # the taps copy of pass k-2 has been consumed
                 self.wxy.copy_from(self.wxy0)
@@ -1054,13 +1047,12 @@ class ChannelBank:
                 _lib.call("qh_set_trainer", 0)
                 self._taps_b[p].copy_from(self.wxy)
                 self._ev_trained[p].record()
-                _lib.call("qh_use_stream", 1)
-                _lib.call("qh_stream_wait_event", self._ev_trained[p].ptr)
-                self._post_stages(r, self._taps_b[p])
-                self._ev_post[p].record()
+                with _lib.on_stream(1):
+                    _lib.call("qh_stream_wait_event", self._ev_trained[p].ptr)
+                    self._post_stages(r, self._taps_b[p])
+                    self._ev_post[p].record()
         finally:
             _lib.call("qh_set_trainer", 0)
-            _lib.call("qh_use_stream", 0)
 
     def _run_stages(self, r):
         self._train_stages(r)
@@ -1090,21 +1082,21 @@ class ChannelBank:
         """Per-row symbol errors of channel ``ch`` (device harness, see :meth:`ResidentReceiver.ser`)."""
         from .core import ber_functions as _ber
         r = self.rx
-        if getattr(r, "alphabet", None) is None:
+        if r.alphabet is None:
             r.alphabet = DeviceArray.from_host(r.alphabet_host)
         idx_tx = _ber.tx_indices_dev(np.ascontiguousarray(symbols_tx, dtype=self.ct), r.alphabet)
         return _ber.cal_ser_dev((self.out if r.Mtestangles else self.eq).row(ch), idx_tx, r.alphabet, maxlag, window, trim, sync=sync,
-                                sync_ws=r._sync_workspace())
+                                sync_ws=r._sync_ws)
 
     def metrics(self, ch, symbols_tx, snr_db=None, maxlag=256, window=4096, trim=0, llr_minmax=False, sync="window"):
         """Per-row signal-quality metrics of channel ``ch`` (device pass, see :meth:`ResidentReceiver.metrics`)."""
         from .core import ber_functions as _ber
         r = self.rx
-        if getattr(r, "alphabet", None) is None:
+        if r.alphabet is None:
             r.alphabet = DeviceArray.from_host(r.alphabet_host)
         idx_tx = _ber.tx_indices_dev(np.ascontiguousarray(symbols_tx, dtype=self.ct), r.alphabet)
         return _ber.cal_metrics_dev((self.out if r.Mtestangles else self.eq).row(ch), idx_tx, r.alphabet, snr_db, maxlag, window, trim, llr_minmax, sync=sync,
-                                    sync_ws=r._sync_workspace())
+                                    sync_ws=r._sync_ws)
 
     def fetch(self, ch):
         _lib.sync()

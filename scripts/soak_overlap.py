@@ -28,6 +28,7 @@ for tier in ("b", "a"):
     prev = None
     for k in range(n):
         i = (k * 7 + k // 5) % len(caps)
+        rx.input_free()                       # the filter of the previous capture may still be reading rx.E on stream 2
         rx.E.copy_from(caps[i]["E"])
         rx.run(overlap=True)
         if prev is not None:                  # the search of the previous capture ran beside this training
@@ -45,6 +46,7 @@ for tier in ("b", "a"):
         try:
             for rnd in range(max(2, npass // 30)):
                 for j, r in enumerate(g.rx):
+                    r.input_free()
                     r.E.copy_from(caps[(j + rnd) % len(caps)]["E"])
                 _lib.sync()
                 g.run(3 * 5)

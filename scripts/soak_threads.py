@@ -17,6 +17,7 @@ for c in caps:
 g = ReceiverGroup(2, 2, 2 * nsym, 2, M, ntaps, mu, **kw)
 for rnd in range(4):
     for j, r in enumerate(g.rx):
+        r.input_free()
         r.E.copy_from(caps[(j + rnd) % 2]["E"])
     _lib.sync(); g.run(6)
     for j, r in enumerate(g.rx):

@@ -283,3 +283,25 @@ def test_real_input_is_a_type_error():
         hip_dsp.bps_twostage_recover(np.zeros((1, 64), np.float32), 8, np.ones(4, np.complex64), 4)
     with pytest.raises(TypeError):
         core_ph.bps_twostage(np.zeros(64, np.float64), 8, np.ones(4, np.complex128), 4, method="fused")
+
+
+def test_row_pipeline_returns_what_the_one_stream_path_returns(monkeypatch):
+    """``hip_dsp.bps_recover`` / ``bps_twostage_recover`` on a (3, 2**16) complex64 field: 1.5 MiB, just above ``_lib.PINNED_MIN_BYTES``, so the rows go
+    through the three-stream pipeline - a first, a middle and a last row, every one different; bit for bit what the same calls return on the
+    one-stream path (the threshold moved out of reach)."""
+    rng = np.random.default_rng(7)
+    M, nm, L = 16, 3, 2 ** 16
+    sy = theory.cal_symbols_qam(M).astype(np.complex64)
+    sy /= np.sqrt(np.mean(np.abs(sy) ** 2))
+    ph = np.cumsum(rng.normal(0, 2e-2, (nm, L)), axis=1)
+    E = (sy[rng.integers(0, M, (nm, L))] * np.exp(1j * ph) + 0.05 * (rng.normal(size=(nm, L)) + 1j * rng.normal(size=(nm, L)))).astype(np.complex64)
+    assert E.nbytes >= _lib.PINNED_MIN_BYTES
+
+    def both():
+        return [np.array(a) for a in hip_dsp.bps_recover(E, 32, sy, 12) + hip_dsp.bps_twostage_recover(E, 16, sy, 12, B=4)]
+    piped = both()
+    monkeypatch.setattr(_lib, "PINNED_MIN_BYTES", 1 << 40)
+    plain = both()
+    assert all(a.shape == (nm, L) and np.any(a) for a in piped)
+    for name, a, b in zip(("bps out", "bps ph", "two-stage out", "two-stage ph"), piped, plain):
+        assert a.dtype == b.dtype and np.array_equal(a, b), name

@@ -533,6 +533,7 @@ def test_overlapped_passes_give_the_results_of_one_capture_at_a_time(tier):
     # overlapped: capture 0, then capture 1 while the search of capture 0 is pending; the recovered signal of capture 0 is read in between
     rx.E.copy_from(caps[0]["E"])
     rx.run(overlap=True)
+    rx.input_free()                             # (tier b: the filter of capture 0 reads rx.E on stream 2)
     rx.E.copy_from(caps[1]["E"])
     rx.run(overlap=True)                        # enqueues the search of capture 0 beside this training
     _lib.sync()
@@ -567,6 +568,7 @@ def test_phase_search_in_parts_between_the_passes_is_bit_identical(parts):
     rx.post_parts = parts
     got = []
     for i, c in enumerate(caps):
+        rx.input_free()                         # (the filter of capture i - 1 reads rx.E on stream 2)
         rx.E.copy_from(c["E"])
         rx.run(overlap=True)                    # the search of capture i - 1 in parts between this capture's passes
         if i > 0:

@@ -150,7 +150,7 @@ def test_receiver_and_bank_pass_sync_through(monkeypatch):
     monkeypatch.setattr(ber_functions, "tx_indices_dev", lambda *a, **k: "idx")
     rx = object.__new__(pipeline.ResidentReceiver)
     rx.alphabet_host, rx.alphabet, rx.Mtestangles, rx.out, rx.eq, rx.ct = np.ones(4), "alphabet", 0, None, _Stub((2, 8), np.complex64), np.complex64
-    rx.wait_post = lambda *a: None
+    rx.wait_post, rx._sync_ws, rx._idx_tx = lambda *a: None, {}, None
     rx._prepare_tx = lambda s: setattr(rx, "_idx_tx", "idx")
     tx = np.ones((2, 8), np.complex64)
     rx.ser(tx, sync="full"); rx.metrics(tx, sync="full"); rx.ser(tx); rx.metrics(tx)
