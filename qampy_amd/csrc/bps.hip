@@ -28,10 +28,6 @@ namespace qh {
 constexpr int BPS_THREADS = 1024;
 constexpr size_t BPS_LDS_BUDGET = 120 * 1024;
 
-template <typename R> __device__ __forceinline__ void sincos_(R x, R *s, R *c);
-template <> __device__ __forceinline__ void sincos_<float>(float x, float *s, float *c) { sincosf(x, s, c); }
-template <> __device__ __forceinline__ void sincos_<double>(double x, double *s, double *c) { sincos(x, s, c); }
-
 // Alphabet descriptor built on the device by analyse_alphabet_kernel (no host round trip).  A square-QAM alphabet is
 // a cartesian product {re levels} x {im levels}; then  min_k |t - s_k|^2 = fma(dr*, dr*, di* * di*)  with dr* / di* the
 // per-axis minima of |t_re - a_r| / |t_im - b_i| - bit-identical to the brute-force scan (rounding is monotone and

@@ -126,13 +126,12 @@ template <typename R> static int cd_table(int N, double c2, double c1, double c0
     if ((rc = scratch(15, bytes, &p))) return rc;
     g_cd.host.resize(bytes);
     Cx<R> *h = reinterpret_cast<Cx<R> *>(g_cd.host.data());
-    const double two_pi = 6.283185307179586476925;
     for (int m = 0; m < N; m++) {
-        const double a = -two_pi * (double)m / (double)N;
+        const double a = -QH_TWO_PI * (double)m / (double)N;
         h[m] = Cx<R>{(R)cos(a), (R)sin(a)};
         const int k = m < N / 2 ? m : m - N;                              // fftfreq order
-        const double w = two_pi * (double)k / (double)N;
-        const double ph = remainder(c2 * w * w + c1 * w + c0, two_pi);
+        const double w = QH_TWO_PI * (double)k / (double)N;
+        const double ph = remainder(c2 * w * w + c1 * w + c0, QH_TWO_PI);
         h[N + m] = Cx<R>{(R)(cos(ph) / N), (R)(sin(ph) / N)};
     }
     QH_HIP(hipMemcpyAsync(p, h, bytes, hipMemcpyHostToDevice, g_stream));
@@ -145,7 +144,8 @@ template <typename R, int N>
 static int cd_launch(const Cx<R> *E, Cx<R> *out, int nmodes, int64_t L, int64_t Lout, const Cx<R> *tab, int mode)
 {
     const size_t lds = (size_t)N * sizeof(Cx<R>);
-    if (lds > 64 * 1024) QH_HIP(hipFuncSetAttribute((const void *)cd_filter_kernel<R, N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int rc = dyn_lds(cd_filter_kernel<R, N>, lds);
+    if (rc) return rc;
     constexpr int64_t n = N / 2;
     if (mode == 0) {
         const int whole = L == N;

@@ -57,6 +57,21 @@ constexpr int SCRATCH_PILOT = 26;                // pilot phases, knots and wrap
 int scratch(int slot, size_t bytes, void **p);   // grow-only device scratch, slots 0..SCRATCH_SLOTS - 1
 unsigned scratch_epoch();        // changes whenever the calling thread's scratch slots are released (contents cached in a slot are gone)
 
+constexpr double QH_PI = 3.14159265358979323846, QH_TWO_PI = 2 * QH_PI;      // (the doubling is exact: QH_TWO_PI is the double nearest 2 pi)
+
+inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
+// Layout of one scratch slot as regions aligned to 256 bytes: take() every region in order, pass `total` to scratch(), add the offsets to its base.
+struct ScratchLayout {
+    size_t total = 0;
+    size_t take(size_t bytes) { const size_t o = total; total += up256(bytes); return o; }
+};
+// a kernel that asks for more than 64 KiB of dynamic LDS has to be opted in before its launch
+template <typename K> int dyn_lds(K kernel, size_t bytes)
+{
+    if (bytes > 64 * 1024) QH_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return QH_OK;
+}
+
 // two-stage phase search on device pointers (bps.hip); the C entry points in api.hip check the arguments
 int bps_twostage_recover_f32(const void *E, int nm, int64_t L, const void *angles, int A, int B, const void *symbols, int M, int N, int32_t *idx1,
                              int32_t *idx2, void *ph, void *Eout);
@@ -121,6 +136,19 @@ __device__ __forceinline__ float abs_(float a) { return __builtin_fabsf(a); }
 __device__ __forceinline__ double abs_(double a) { return __builtin_fabs(a); }
 __device__ __forceinline__ float min_(float a, float b) { return __builtin_fminf(a, b); }
 __device__ __forceinline__ double min_(double a, double b) { return __builtin_fmin(a, b); }
+template <typename R> __device__ __forceinline__ void sincos_(R x, R *s, R *c);
+template <> __device__ __forceinline__ void sincos_<float>(float x, float *s, float *c) { sincosf(x, s, c); }
+template <> __device__ __forceinline__ void sincos_<double>(double x, double *s, double *c) { sincos(x, s, c); }
+
+template <typename R> __device__ __forceinline__ Cx<R> cadd(Cx<R> a, Cx<R> b) { return Cx<R>{a.re + b.re, a.im + b.im}; }
+template <typename R> __device__ __forceinline__ Cx<R> csub(Cx<R> a, Cx<R> b) { return Cx<R>{a.re - b.re, a.im - b.im}; }
+template <typename R> __device__ __forceinline__ Cx<R> cmul(Cx<R> a, Cx<R> b) { return Cx<R>{a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
+template <typename R> __device__ __forceinline__ Cx<R> cconj(Cx<R> a) { return Cx<R>{a.re, -a.im}; }
+template <typename R> __device__ __forceinline__ Cx<R> pow4(Cx<R> x)
+{
+    const Cx<R> s = cmul(x, x);
+    return cmul(s, s);
+}
 
 // ---------------------------------------------------------------------------------------------- wave64 cross-lane
 // DPP controls (gfx9 encoding)
@@ -179,6 +207,28 @@ template <typename R> __device__ __forceinline__ void wave_sum2(R &a, R &b)
     a += dpp_mov<DPP_ROW_BCAST31, 0xC>(a);     b += dpp_mov<DPP_ROW_BCAST31, 0xC>(b);
     a = readlane(a, 63);
     b = readlane(b, 63);
+}
+// Sum of a double over a workgroup of T threads in a fixed order - wave_sum, then waves 0, 1, 2, ... - to every thread: the same bits in
+// every workgroup and every run.  red: T / 64 entries of LDS.  Ends in a barrier: red may be used again.
+template <int T> __device__ __forceinline__ double block_sum(double s, double *red)
+{
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    double t = 0.;
+    for (int w = 0; w < T / 64; w++) t += red[w];
+    __syncthreads();
+    return t;
+}
+// two sums at once, the wave sums interleaved
+template <int T> __device__ __forceinline__ void block_sum2(double &a, double &b, double (*red)[2])
+{
+    wave_sum2(a, b);
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = a; red[threadIdx.x >> 6][1] = b; }
+    __syncthreads();
+    a = b = 0.;
+    for (int w = 0; w < T / 64; w++) { a += red[w][0]; b += red[w][1]; }
+    __syncthreads();
 }
 // min over the 64 lanes, returned wave-uniformly
 template <typename R> __device__ __forceinline__ R wave_min(R v)

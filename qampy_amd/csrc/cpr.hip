@@ -46,25 +46,6 @@ constexpr int P16_WAVES = UW_THREADS / 64;
 static_assert(VV_NMAX <= UW_CHUNK, "the halo of a V&V tile must fit the second half of the tile");
 static_assert(P16_PARTS <= UW_THREADS, "one partial sum per thread");
 
-constexpr double CPR_PI = 3.14159265358979323846;
-
-template <typename R> __device__ __forceinline__ void sincos_(R x, R *s, R *c);
-template <> __device__ __forceinline__ void sincos_<float>(float x, float *s, float *c) { sincosf(x, s, c); }
-template <> __device__ __forceinline__ void sincos_<double>(double x, double *s, double *c) { sincos(x, s, c); }
-template <typename R> __device__ __forceinline__ Cx<R> cmul(Cx<R> a, Cx<R> b) { return Cx<R>{a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-template <typename R> __device__ __forceinline__ Cx<R> pow4(Cx<R> x)
-{
-    const Cx<R> s = cmul(x, x);
-    return cmul(s, s);
-}
-
-// np.unwrap's correction for the step prev -> cur of a sequence of angles, in units of 2 pi
-__device__ __forceinline__ int wrap_count(double prev, double cur)
-{
-    const double d = cur - prev;
-    return d > CPR_PI ? -1 : (d < -CPR_PI ? 1 : 0);
-}
-
 // (x / |x|)^M in the precision of x; zero -> 1 (np.angle(0) = 0)
 template <typename R> __device__ __forceinline__ Cx<R> unit_pow(Cx<R> x, int M)
 {
@@ -86,37 +67,6 @@ template <typename R> __device__ __forceinline__ Cx<R> derotate(Cx<R> x, R p)
     R sn, cs;
     sincos_<R>(p, &sn, &cs);
     return Cx<R>{fma_(x.re, cs, x.im * sn), fma_(x.im, cs, -(x.re * sn))};
-}
-
-// Inclusive prefix of the wrap counts over one chunk, plus the chunk's offset.  Thread t owns the UW_PER_THREAD consecutive elements from
-// t * UW_PER_THREAD on and brings their inclusive sums inside the thread; corr[e] receives K of element e of the chunk.  Ends in a barrier.
-__device__ __forceinline__ void chunk_prefix(const int (&jmp)[UW_PER_THREAD], int chunk_off, int *corr, int *wsum)
-{
-    const int local = jmp[UW_PER_THREAD - 1];
-    int incl = local;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o);
-        if ((int)(threadIdx.x & 63) >= o) incl += t;
-    }
-    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    int off = chunk_off + incl - local;
-    for (int w = 0; w < (int)(threadIdx.x >> 6); w++) off += wsum[w];
-#pragma unroll
-    for (int r = 0; r < UW_PER_THREAD; r++) corr[threadIdx.x * UW_PER_THREAD + r] = off + jmp[r];
-    __syncthreads();
-}
-
-// sum of an int over the workgroup, to thread 0
-__device__ __forceinline__ int block_sum_int(int s, int *red)
-{
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    int t = 0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < UW_THREADS / 64; w++) t += red[w];
-    return t;
 }
 
 // ------------------------------------------------------------------------------------------------ Viterbi-Viterbi
@@ -182,17 +132,7 @@ __global__ void __launch_bounds__(UW_THREADS) vv_theta_kernel(const Cx<R> *__res
         th[li] = t;
     }
     __syncthreads();
-    int s = 0;
-#pragma unroll
-    for (int r = 0; r < UW_PER_THREAD; r++) {
-        const int li = 1 + r * UW_THREADS + tid;
-        const int64_t k = j0 + li;
-        int j = 0;
-        if (k >= 1 && k < nout) j = wrap_count(th[li - 1], th[li]);
-        if (li == 1) first_jump[mode * nchunk + blockIdx.x] = j;
-        s += j;
-    }
-    s = block_sum_int(s, red);
+    const int s = block_sum_int(strided_wrap_counts(th, base, nout, first_jump + mode * nchunk + blockIdx.x), red);
     if (tid == 0) chunk_sum[mode * nchunk + blockIdx.x] = s;
 }
 
@@ -216,16 +156,7 @@ __global__ void __launch_bounds__(UW_THREADS) vv_apply_kernel(const Cx<R> *__res
     }
     __syncthreads();
     int jmp[UW_PER_THREAD];
-    int local = 0;
-#pragma unroll
-    for (int r = 0; r < UW_PER_THREAD; r++) {
-        const int el = tid * UW_PER_THREAD + r;
-        const int64_t k = base + el;
-        int j = 0;
-        if (k >= 1 && k < nout) j = el == 0 ? first_jump[mode * nchunk + blockIdx.x] : wrap_count(th[el - 1], th[el]);
-        local += j;
-        jmp[r] = local;
-    }
+    owned_wrap_counts(th, base, nout, first_jump + mode * nchunk + blockIdx.x, jmp);
     chunk_prefix(jmp, chunk_off[mode * nchunk + blockIdx.x], corr, wsum);
     const Cx<R> *e = E + mode * L;
     Cx<R> *out = Eout + mode * L;
@@ -235,10 +166,10 @@ __global__ void __launch_bounds__(UW_THREADS) vv_apply_kernel(const Cx<R> *__res
         const int64_t k = base + el;
         if (k < nout) {
             const int K = corr[el];
-            trace[mode * nout + k] = (R)((th[el] + 2 * CPR_PI * (double)K - CPR_PI) / (double)M);
+            trace[mode * nout + k] = (R)((th[el] + 2 * QH_PI * (double)K - QH_PI) / (double)M);
             // exp(-j trace) does not change when K changes by M: the argument stays within (-2 pi, 2 pi) and keeps its digits
             const int Km = ((K % M) + M) % M;
-            const R p = (R)((th[el] + 2 * CPR_PI * (double)Km - CPR_PI) / (double)M);
+            const R p = (R)((th[el] + 2 * QH_PI * (double)Km - QH_PI) / (double)M);
             stg(out + o + k, derotate<R>(ldg(e + o + k), p));
         }
     }
@@ -261,12 +192,10 @@ int vv_recover_dev(const void *E, int nmodes, int64_t L, int N, int M, void *tra
     const int64_t nout = L - N + 1, nchunk = (nout + UW_CHUNK - 1) / UW_CHUNK;
     QH_REQUIRE(nchunk <= 0x7fffffff, "vv_recover: row too long");
     // scratch: theta | chunk sums | wrap count of every chunk's first output
-    const size_t o_sum = ((size_t)nmodes * nout * sizeof(double) + 255) & ~(size_t)255, o_first = o_sum + (((size_t)nmodes * nchunk * sizeof(int) + 255) & ~(size_t)255),
-                 total = o_first + (size_t)nmodes * nchunk * sizeof(int);
-    void *sb = nullptr;
-    if ((rc = scratch(SCRATCH_CPR, total, &sb))) return rc;
-    double *theta = (double *)sb;
-    int *csum = (int *)((char *)sb + o_sum), *first = (int *)((char *)sb + o_first);
+    UnwrapScratch us;
+    if ((rc = unwrap_scratch(SCRATCH_CPR, nmodes, nchunk, (size_t)nmodes * nout * sizeof(double), &us))) return rc;
+    double *theta = (double *)us.base;
+    int *csum = us.csum, *first = us.first;
     const dim3 grid((unsigned)nchunk, nmodes);
     const size_t lds = ((size_t)(UW_CHUNK + N + UW_THREADS - 1) / UW_THREADS * UW_THREADS + 1) * sizeof(double2);      // <= 32 KiB + 16
     hipLaunchKernelGGL((vv_theta_kernel<R>), grid, dim3(UW_THREADS), lds, g_stream, (const Cx<R> *)E, L, N, M, nout, nchunk, theta, csum, first);
@@ -278,17 +207,6 @@ int vv_recover_dev(const void *E, int nmodes, int64_t L, int N, int M, void *tra
 }
 
 // ------------------------------------------------------------------------------------------------ 16-QAM by QPSK partitioning
-// sums of two doubles over the workgroup in a fixed order (wave sums, then the waves in turn): the same bits in every workgroup
-__device__ __forceinline__ void block_sum2(double &a, double &b, double (*red)[2])
-{
-    wave_sum2(a, b);
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = a; red[threadIdx.x >> 6][1] = b; }
-    __syncthreads();
-    a = b = 0.;
-    for (int w = 0; w < P16_WAVES; w++) { a += red[w][0]; b += red[w][1]; }
-    __syncthreads();
-}
-
 template <typename R>
 __global__ void __launch_bounds__(UW_THREADS) p16_moments_kernel(const Cx<R> *__restrict__ E, int64_t L, int64_t span, int nparts, double *__restrict__ part)
 {
@@ -310,7 +228,7 @@ __global__ void __launch_bounds__(UW_THREADS) p16_moments_kernel(const Cx<R> *__
             s4 += p * p;
         }
     }
-    block_sum2(s2, s4, red);
+    block_sum2<UW_THREADS>(s2, s4, red);
     if (threadIdx.x == 0) {
         double *o = part + ((int64_t)blockIdx.y * nparts + blockIdx.x) * 2;
         o[0] = s2; o[1] = s4;
@@ -340,7 +258,7 @@ __global__ void __launch_bounds__(UW_THREADS) p16_theta_kernel(P16Args<R> a)
             const double *p = a.part + (mode * a.nparts + tid) * 2;
             s2 = p[0]; s4 = p[1];
         }
-        block_sum2(s2, s4, red);
+        block_sum2<UW_THREADS>(s2, s4, red);
         if (tid == 0) {
             const double gamma = 25. / 33., r2 = s2 / (double)a.L, r4 = s4 / (double)a.L, q = r2 * r2 / r4;
             const double S1 = 1 - 2 * q - sqrt((2 - gamma) * (2 * q * q - q));
@@ -440,8 +358,8 @@ __global__ void __launch_bounds__(UW_THREADS) p16_apply_kernel(const Cx<R> *__re
             const int64_t b = n / Nblock;
             const double t = theta[mode * nb + b];
             const int K = Kb[mode * nb + b];
-            trace[mode * L + n] = (R)(t / 4 + (CPR_PI / 2) * (double)K - CPR_PI / 4);
-            const R p = (R)(t / 4 + (CPR_PI / 2) * (double)(K & 3) - CPR_PI / 4);      // the same rotation: K changes by a multiple of 4
+            trace[mode * L + n] = (R)(t / 4 + (QH_PI / 2) * (double)K - QH_PI / 4);
+            const R p = (R)(t / 4 + (QH_PI / 2) * (double)(K & 3) - QH_PI / 4);      // the same rotation: K changes by a multiple of 4
             stg(Eout + mode * L + n, derotate<R>(ldg(E + mode * L + n), p));
         }
     }
@@ -464,14 +382,14 @@ int partition16_recover_dev(const void *E, int nmodes, int64_t L, int Nblock, vo
     const int64_t ngroups = (nb + (int64_t)P16_WAVES * G - 1) / ((int64_t)P16_WAVES * G);
     QH_REQUIRE(ngroups <= 0x7fffffff && nsamp <= 0x7fffffff, "partition16_recover: row too long");
     // scratch: partial moments | theta_b | K_b | chunk sums
-    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
-    const size_t o_theta = up((size_t)nmodes * nparts * 2 * sizeof(double)), o_K = o_theta + up((size_t)nmodes * nb * sizeof(double)),
-                 o_sum = o_K + up((size_t)nmodes * nb * sizeof(int)), total = o_sum + (size_t)nmodes * nchunk * sizeof(int);
+    ScratchLayout lay;
+    const size_t o_part = lay.take((size_t)nmodes * nparts * 2 * sizeof(double)), o_theta = lay.take((size_t)nmodes * nb * sizeof(double)),
+                 o_K = lay.take((size_t)nmodes * nb * sizeof(int)), o_sum = lay.take((size_t)nmodes * nchunk * sizeof(int));
     void *sb = nullptr;
-    if ((rc = scratch(SCRATCH_CPR, total, &sb))) return rc;
-    double *part = (double *)sb, *theta = (double *)((char *)sb + o_theta);
+    if ((rc = scratch(SCRATCH_CPR, lay.total, &sb))) return rc;
+    double *part = (double *)((char *)sb + o_part), *theta = (double *)((char *)sb + o_theta);
     int *Kb = (int *)((char *)sb + o_K), *csum = (int *)((char *)sb + o_sum);
-    const double phi = CPR_PI / 4 + atan(1. / 3.);
+    const double phi = QH_PI / 4 + atan(1. / 3.);
     P16Args<R> a;
     a.E = (const Cx<R> *)E; a.part = part; a.theta = theta; a.L = L; a.nb = nb; a.Nblock = Nblock; a.nparts = nparts; a.G = G;
     a.cphi = (R)cos(phi); a.sphi = (R)sin(phi);

@@ -65,8 +65,6 @@ template <typename R> struct FftStore {
     R scale;
 };
 
-template <typename R> __device__ __forceinline__ Cx<R> cconj(Cx<R> a) { return Cx<R>{a.re, -a.im}; }
-
 // exp(-2 pi i t) in double, the turn reduced first
 __device__ __forceinline__ void fft_ramp(double t, double &cs, double &sn)
 {
@@ -141,16 +139,6 @@ template <typename R> __device__ __forceinline__ void fft_store(const FftStore<R
     }
     if (st.conj) v = cconj(v);
     stg(st.out + (size_t)row * st.stride + k, Cx<R>{v.re * st.scale, v.im * st.scale});
-}
-
-// tab[m] = exp(-2 pi i m / n), m = 0 .. n - 1 (n a power of two: m / n is exact)
-template <typename R> __global__ void __launch_bounds__(256) fft_twiddle_kernel(Cx<R> *tab, int n)
-{
-    const int m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= n) return;
-    double sn, cs;
-    sincospi(-2.0 * ((double)m / (double)n), &sn, &cs);
-    stg(tab + m, Cx<R>{(R)cs, (R)sn});
 }
 
 // chirp[n] = exp(-i pi n^2 / L), n = 0 .. L - 1: n^2 mod 2 L in integers, the turn (n^2 mod 2 L) / (2 L) below one
@@ -233,8 +221,6 @@ template <typename R> struct FftPlan {
     Cx<R> *tw1 = nullptr, *tw2 = nullptr, *chirp = nullptr, *Bhat = nullptr, *T = nullptr, *W = nullptr;
 };
 
-static size_t fft_up256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 static bool fft_length_ok(int64_t L)
 {
     if (L < 2) return false;
@@ -242,16 +228,10 @@ static bool fft_length_ok(int64_t L)
     return L <= FFT_BLUE_MAX;
 }
 
-template <typename K> static int fft_lds(K kernel, size_t lds)
-{
-    if (lds > 64 * 1024) QH_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return QH_OK;
-}
-
 template <typename R, int N> static int fft_row_launch(const FftLoad<R> &ld, const FftStore<R> &st, int rows, const Cx<R> *tw)
 {
     const size_t lds = (size_t)N * sizeof(Cx<R>);
-    int rc = fft_lds(fft_row_kernel<R, N>, lds);
+    int rc = dyn_lds(fft_row_kernel<R, N>, lds);
     if (rc) return rc;
     hipLaunchKernelGGL((fft_row_kernel<R, N>), dim3(rows), dim3(CD_T), lds, g_stream, ld, st, tw);
     QH_HIP(hipGetLastError());
@@ -262,7 +242,7 @@ template <typename R, int N1> static int fft_step1_launch(const FftLoad<R> &ld, 
 {
     constexpr int C = fft_cols<R, N1>();
     const size_t lds = (size_t)C * (N1 + 1) * sizeof(Cx<R>);
-    int rc = fft_lds(fft_step1_kernel<R, N1>, lds);
+    int rc = dyn_lds(fft_step1_kernel<R, N1>, lds);
     if (rc) return rc;
     hipLaunchKernelGGL((fft_step1_kernel<R, N1>), dim3(N2 / C, rows), dim3(CD_T), lds, g_stream, ld, N2, tw1, T);
     QH_HIP(hipGetLastError());
@@ -273,7 +253,7 @@ template <typename R, int N2> static int fft_step2_launch(const Cx<R> *T, int ro
 {
     constexpr int C = fft_cols<R, N2>();
     const size_t lds = (size_t)C * (N2 + 1) * sizeof(Cx<R>);
-    int rc = fft_lds(fft_step2_kernel<R, N2>, lds);
+    int rc = dyn_lds(fft_step2_kernel<R, N2>, lds);
     if (rc) return rc;
     hipLaunchKernelGGL((fft_step2_kernel<R, N2>), dim3(N1 / C, rows), dim3(CD_T), lds, g_stream, T, N1, tw2, st);
     QH_HIP(hipGetLastError());
@@ -326,17 +306,18 @@ template <typename R> static int fft_plan(int nmodes, int64_t L, FftPlan<R> &p)
     p.N1 = 1 << lgN1;
     p.N2 = 1 << (lg - lgN1);
     const size_t cx = sizeof(Cx<R>);
-    const size_t o_tw1 = 0, o_tw2 = o_tw1 + fft_up256((size_t)p.N1 * cx), o_chirp = o_tw2 + fft_up256((size_t)p.N2 * cx),
-                 o_B = o_chirp + (p.blue ? fft_up256((size_t)L * cx) : 0), o_T = o_B + (p.blue ? fft_up256((size_t)p.M * cx) : 0),
-                 o_W = o_T + (p.N1 > 1 ? fft_up256((size_t)nmodes * p.M * cx) : 0), total = o_W + (p.blue ? fft_up256((size_t)nmodes * p.M * cx) : 0);
+    ScratchLayout lay;
+    const size_t o_tw1 = lay.take((size_t)p.N1 * cx), o_tw2 = lay.take((size_t)p.N2 * cx), o_chirp = lay.take(p.blue ? (size_t)L * cx : 0),
+                 o_B = lay.take(p.blue ? (size_t)p.M * cx : 0), o_T = lay.take(p.N1 > 1 ? (size_t)nmodes * p.M * cx : 0),
+                 o_W = lay.take(p.blue ? (size_t)nmodes * p.M * cx : 0);
     void *base = nullptr;
-    int rc = scratch(SCRATCH_FFT, total, &base);
+    int rc = scratch(SCRATCH_FFT, lay.total, &base);
     if (rc) return rc;
     char *sb = (char *)base;
     p.tw1 = (Cx<R> *)(sb + o_tw1); p.tw2 = (Cx<R> *)(sb + o_tw2); p.chirp = (Cx<R> *)(sb + o_chirp); p.Bhat = (Cx<R> *)(sb + o_B);
     p.T = (Cx<R> *)(sb + o_T); p.W = (Cx<R> *)(sb + o_W);
-    if (p.N1 > 1) hipLaunchKernelGGL((fft_twiddle_kernel<R>), dim3((p.N1 + 255) / 256), dim3(256), 0, g_stream, p.tw1, p.N1);
-    hipLaunchKernelGGL((fft_twiddle_kernel<R>), dim3((p.N2 + 255) / 256), dim3(256), 0, g_stream, p.tw2, p.N2);
+    if (p.N1 > 1) hipLaunchKernelGGL((twiddle_kernel<R>), dim3((p.N1 + 255) / 256), dim3(256), 0, g_stream, p.tw1, p.N1);
+    hipLaunchKernelGGL((twiddle_kernel<R>), dim3((p.N2 + 255) / 256), dim3(256), 0, g_stream, p.tw2, p.N2);
     QH_HIP(hipGetLastError());
     if (p.blue) {
         hipLaunchKernelGGL((fft_chirp_kernel<R>), dim3((unsigned)((L + 255) / 256)), dim3(256), 0, g_stream, p.chirp, L);

@@ -1,4 +1,4 @@
-// Stockham autosort FFT in LDS, shared by the kernels that transform one block per workgroup (cd.hip, foe.hip): every pass reads
+// Stockham autosort FFT in LDS, shared by the kernels that transform one block per workgroup (cd.hip, foe.hip, fft.hip, impair.hip): every pass reads
 // its butterflies' inputs from LDS into registers, runs radix-8/4/2 butterflies there and writes the results back in place (a barrier
 // between the reads and the writes, so one N-point buffer suffices).  `tw` is the table W_N^m = exp(-2 pi i m / N), m = 0 .. N - 1, of
 // the transform's own size, in the signal's precision.
@@ -9,10 +9,18 @@ namespace qh {
 
 constexpr int CD_T = 256;                 // threads per workgroup
 
-template <typename R> __device__ __forceinline__ Cx<R> cadd(Cx<R> a, Cx<R> b) { return Cx<R>{a.re + b.re, a.im + b.im}; }
-template <typename R> __device__ __forceinline__ Cx<R> csub(Cx<R> a, Cx<R> b) { return Cx<R>{a.re - b.re, a.im - b.im}; }
-template <typename R> __device__ __forceinline__ Cx<R> cmul(Cx<R> a, Cx<R> b) { return Cx<R>{a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
 template <typename R> __device__ __forceinline__ Cx<R> mul_mi(Cx<R> a) { return Cx<R>{a.im, -a.re}; }     // a * (-i)
+
+// The table of the units that form it on the device (foe.hip, fft.hip): tab[m] = exp(-2 pi i m / n), m = 0 .. n - 1 (n a power of two: m / n
+// is exact).  grid (n / 256 rounded up).  (`static`: two translation units instantiate it.)
+template <typename R> static __global__ void __launch_bounds__(256) twiddle_kernel(Cx<R> *tab, int n)
+{
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n) return;
+    double sn, cs;
+    sincospi(-2.0 * ((double)m / (double)n), &sn, &cs);
+    stg(tab + m, Cx<R>{(R)cs, (R)sn});
+}
 
 // forward DFTs in registers: y[s] = sum_r v[r] exp(-2 pi i r s / RAD)
 template <typename R> __device__ __forceinline__ void dft2(Cx<R> &a, Cx<R> &b)

@@ -32,22 +32,6 @@ constexpr int FOE_C = 8;                                               // column
 constexpr int64_t FOE_CHUNK = (int64_t)1 << 22;                        // elements of intermediate per chunk of blocks
 constexpr int FOE_PARTS = 256;                                         // partial results per row in the peak search, at most
 
-template <typename R> __device__ __forceinline__ Cx<R> pow4(Cx<R> x)
-{
-    const Cx<R> s = cmul(x, x);
-    return cmul(s, s);
-}
-
-// tab[m] = exp(-2 pi i m / n), m = 0 .. n - 1 (n a power of two: m / n is exact)
-template <typename R> __global__ void __launch_bounds__(256) foe_twiddle_kernel(Cx<R> *tab, int n)
-{
-    const int m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= n) return;
-    double sn, cs;
-    sincospi(-2.0 * ((double)m / (double)n), &sn, &cs);
-    stg(tab + m, Cx<R>{(R)cs, (R)sn});
-}
-
 // grid (transforms per row, nmodes).  FOURTH: transform blockIdx.x is block b0 + blockIdx.x of row blockIdx.y of E, raised to the fourth power,
 // zero beyond the row's end.  Otherwise it is the blockIdx.x-th run of N values of the row's intermediate.  Pb: |X|^2, same layout as the grid.
 template <typename R, int N, bool FOURTH>
@@ -207,17 +191,11 @@ __global__ void __launch_bounds__(256) foe_spectrum_kernel(const R *__restrict__
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-template <typename K> static int foe_lds(K kernel, size_t lds)
-{
-    if (lds > 64 * 1024) QH_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return QH_OK;
-}
-
 template <typename R, int N, bool FOURTH>
 static int foe_fft_launch(const Cx<R> *in, int64_t L, int64_t b0, int64_t count, int nmodes, const Cx<R> *tw, R *Pb)
 {
     const size_t lds = (size_t)N * sizeof(Cx<R>);
-    int rc = foe_lds(foe_fft_kernel<R, N, FOURTH>, lds);
+    int rc = dyn_lds(foe_fft_kernel<R, N, FOURTH>, lds);
     if (rc) return rc;
     hipLaunchKernelGGL((foe_fft_kernel<R, N, FOURTH>), dim3((unsigned)count, nmodes), dim3(CD_T), lds, g_stream, in, L, b0, tw, Pb);
     QH_HIP(hipGetLastError());
@@ -228,14 +206,12 @@ template <typename R, int N1>
 static int foe_step1_launch(const Cx<R> *E, int64_t L, int64_t b0, int nb, int nmodes, int N2, const Cx<R> *tw1, Cx<R> *T)
 {
     const size_t lds = (size_t)FOE_C * (N1 + 1) * sizeof(Cx<R>);
-    int rc = foe_lds(foe_step1_kernel<R, N1>, lds);
+    int rc = dyn_lds(foe_step1_kernel<R, N1>, lds);
     if (rc) return rc;
     hipLaunchKernelGGL((foe_step1_kernel<R, N1>), dim3(N2 / FOE_C, nb, nmodes), dim3(CD_T), lds, g_stream, E, L, b0, N2, tw1, T);
     QH_HIP(hipGetLastError());
     return QH_OK;
 }
-
-static size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 template <typename R>
 int find_freq_offset_dev(const void *E, int nmodes, int64_t L, int os, int fft_size, int blocks, int average, double *fo, double *stats, void *spectrum)
@@ -256,20 +232,20 @@ int find_freq_offset_dev(const void *E, int nmodes, int64_t L, int os, int fft_s
     if (chunk < 1) chunk = 1;
     const int per = N / FOE_PARTS >= 256 ? N / FOE_PARTS : 256, nparts = N / per;
     // scratch: W_N1 | W_N2 | P | partial results | stats | per-block powers | four-step intermediate
-    const size_t o_tw1 = 0, o_tw2 = o_tw1 + up256((size_t)N1 * sizeof(Cx<R>)), o_P = o_tw2 + up256((size_t)N2 * sizeof(Cx<R>)),
-                 o_part = o_P + up256((size_t)nmodes * N * sizeof(R)), o_stats = o_part + up256((size_t)nmodes * nparts * 3 * sizeof(double)),
-                 o_Pb = o_stats + up256((size_t)nmodes * 3 * sizeof(double)), o_T = o_Pb + up256((size_t)nmodes * chunk * N * sizeof(R)),
-                 total = o_T + (N1 > 1 ? up256((size_t)nmodes * chunk * N * sizeof(Cx<R>)) : 0);
+    ScratchLayout lay;
+    const size_t o_tw1 = lay.take((size_t)N1 * sizeof(Cx<R>)), o_tw2 = lay.take((size_t)N2 * sizeof(Cx<R>)), o_P = lay.take((size_t)nmodes * N * sizeof(R)),
+                 o_part = lay.take((size_t)nmodes * nparts * 3 * sizeof(double)), o_stats = lay.take((size_t)nmodes * 3 * sizeof(double)),
+                 o_Pb = lay.take((size_t)nmodes * chunk * N * sizeof(R)), o_T = lay.take(N1 > 1 ? (size_t)nmodes * chunk * N * sizeof(Cx<R>) : 0);
     void *base = nullptr;
-    if ((rc = scratch(SCRATCH_FOE, total, &base))) return rc;
+    if ((rc = scratch(SCRATCH_FOE, lay.total, &base))) return rc;
     char *sb = (char *)base;
     Cx<R> *tw1 = (Cx<R> *)(sb + o_tw1), *tw2 = (Cx<R> *)(sb + o_tw2), *T = (Cx<R> *)(sb + o_T);
     R *P = (R *)(sb + o_P), *Pb = (R *)(sb + o_Pb);
     double *part = (double *)(sb + o_part);
     if (!stats) stats = (double *)(sb + o_stats);
     const Cx<R> *e = (const Cx<R> *)E;
-    if (N1 > 1) hipLaunchKernelGGL((foe_twiddle_kernel<R>), dim3((N1 + 255) / 256), dim3(256), 0, g_stream, tw1, N1);
-    hipLaunchKernelGGL((foe_twiddle_kernel<R>), dim3((N2 + 255) / 256), dim3(256), 0, g_stream, tw2, N2);
+    if (N1 > 1) hipLaunchKernelGGL((twiddle_kernel<R>), dim3((N1 + 255) / 256), dim3(256), 0, g_stream, tw1, N1);
+    hipLaunchKernelGGL((twiddle_kernel<R>), dim3((N2 + 255) / 256), dim3(256), 0, g_stream, tw2, N2);
     QH_HIP(hipGetLastError());
     for (int64_t b0 = 0; b0 < blocks; b0 += chunk) {
         const int nb = (int)(blocks - b0 < chunk ? blocks - b0 : chunk);

@@ -42,19 +42,6 @@ template <typename R> __device__ __forceinline__ double imp_increment(int64_t n,
     return sphase * (double)g0;
 }
 
-// sum over the workgroup, valid in thread 0
-__device__ __forceinline__ double imp_block_sum(double v, double *red)
-{
-    v = wave_sum(v);
-    if (threadIdx.x % 64 == 0) red[threadIdx.x / 64] = v;
-    __syncthreads();
-    double s = 0;
-    if (threadIdx.x == 0)
-        for (int q = 0; q < IMP_T / 64; q++) s += red[q];
-    __syncthreads();
-    return s;
-}
-
 // launch 1, grid (ntiles, nmodes): tot[mode][tile] = sum of the tile's phase increments, pw[mode][tile] = sum of the tile's |x|^2
 template <typename R>
 __global__ void __launch_bounds__(IMP_T) impair_part_kernel(const Cx<R> *__restrict__ E, int64_t L, int do_phase, int do_power, double sphase, unsigned k0,
@@ -73,8 +60,8 @@ __global__ void __launch_bounds__(IMP_T) impair_part_kernel(const Cx<R> *__restr
             q = fma_((double)v.re, (double)v.re, fma_((double)v.im, (double)v.im, q));
         }
     }
-    if (do_phase) { s = imp_block_sum(s, red); if (threadIdx.x == 0) tot[slot] = s; }
-    if (do_power) { q = imp_block_sum(q, red); if (threadIdx.x == 0) pw[slot] = q; }
+    if (do_phase) { s = block_sum<IMP_T>(s, red); if (threadIdx.x == 0) tot[slot] = s; }
+    if (do_power) { q = block_sum<IMP_T>(q, red); if (threadIdx.x == 0) pw[slot] = q; }
 }
 
 // launch 2, grid (nmodes): the mode's tile totals become their exclusive prefix sums; workgroup 0 also forms sig[0] = factor sqrt(mean |x|^2)
@@ -242,8 +229,6 @@ __global__ void __launch_bounds__(CD_T) pmd_filter_kernel(const Cx<R> *__restric
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static size_t imp_up256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 // E == nullptr: phase only (trace must be given).  noise_mode 0: none; 1: sigma = noise; 2: sigma = noise sqrt(mean |E|^2 over all modes)
 template <typename R>
 int impair_pointwise_dev(const void *E, int nmodes, int64_t L, int noise_mode, double noise, int have_phase, double phase_var, int cumulative, int have_freq,
@@ -261,9 +246,10 @@ int impair_pointwise_dev(const void *E, int nmodes, int64_t L, int noise_mode, d
     if (L == 0) return QH_OK;
     const int64_t ntiles = (L + IMP_TILE - 1) / IMP_TILE;
     const int scan = have_phase && cumulative, power = E && noise_mode == 2;
-    const size_t o_tot = 0, o_pw = o_tot + imp_up256((size_t)nmodes * ntiles * sizeof(double)), o_sig = o_pw + imp_up256((size_t)nmodes * ntiles * sizeof(double));
+    ScratchLayout lay;
+    const size_t o_tot = lay.take((size_t)nmodes * ntiles * sizeof(double)), o_pw = lay.take((size_t)nmodes * ntiles * sizeof(double)), o_sig = lay.take(sizeof(double));
     void *base = nullptr;
-    if ((rc = scratch(SCRATCH_IMPAIR, o_sig + 256, &base))) return rc;
+    if ((rc = scratch(SCRATCH_IMPAIR, lay.total, &base))) return rc;
     double *tot = (double *)((char *)base + o_tot), *pw = (double *)((char *)base + o_pw), *sig = (double *)((char *)base + o_sig);
     const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
     const double sphase = have_phase ? sqrt(phase_var) : 0.0;
@@ -338,12 +324,11 @@ template <typename R> static int pmd_table(int N, double dgd, const Cx<R> **tab)
     if ((rc = scratch(SCRATCH_PMD, bytes, &p))) return rc;
     g_pmd.host.resize(bytes);
     Cx<R> *h = reinterpret_cast<Cx<R> *>(g_pmd.host.data());
-    const double pi = 3.14159265358979323846;
     for (int m = 0; m < N; m++) {
-        const double a = -2.0 * pi * (double)m / (double)N;
+        const double a = -QH_TWO_PI * (double)m / (double)N;
         h[m] = Cx<R>{(R)cos(a), (R)sin(a)};
         const int k = m < N / 2 ? m : m - N;                              // fftfreq order
-        const double ph = remainder(-pi * dgd * (double)k / (double)N, 2.0 * pi);
+        const double ph = remainder(-QH_PI * dgd * (double)k / (double)N, QH_TWO_PI);
         h[N + m] = Cx<R>{(R)(cos(ph) / N), (R)(sin(ph) / N)};
     }
     QH_HIP(hipMemcpyAsync(p, h, bytes, hipMemcpyHostToDevice, g_stream));
@@ -355,7 +340,8 @@ template <typename R> static int pmd_table(int N, double dgd, const Cx<R> **tab)
 template <typename R, int N> static int pmd_launch(const Cx<R> *E, Cx<R> *out, int64_t L, const Cx<R> *tab, R c, R s)
 {
     const size_t lds = (size_t)N * sizeof(Cx<R>);
-    if (lds > 64 * 1024) QH_HIP(hipFuncSetAttribute((const void *)pmd_filter_kernel<R, N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int rc = dyn_lds(pmd_filter_kernel<R, N>, lds);
+    if (rc) return rc;
     const int whole = L == N;
     const int64_t nblk = whole ? 1 : (L + N / 2 - 1) / (N / 2);
     hipLaunchKernelGGL((pmd_filter_kernel<R, N>), dim3((unsigned)nblk, 2), dim3(CD_T), lds, g_stream, E, out, L, tab, c, s, whole);

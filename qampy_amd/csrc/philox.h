@@ -31,7 +31,7 @@ __device__ __forceinline__ void gauss2(unsigned a, unsigned b, float &g0, float 
 
 // The impairments' draws (impair.hip, txresp.hip): counter (sample index low word, high word, mode, stream), key = the seed.
 constexpr unsigned IMP_STREAM_PHASE = 1u, IMP_STREAM_NOISE = 2u;
-constexpr double IMP_TWO_PI = 6.283185307179586476925;
+constexpr double IMP_TWO_PI = QH_TWO_PI;
 
 // two independent standard normals of sample n of a mode, in the precision of the signal
 __device__ __forceinline__ void imp_gauss(int64_t n, int mode, unsigned stream, unsigned k0, unsigned k1, float &g0, float &g1)

@@ -32,7 +32,6 @@ namespace {
 
 constexpr int PILOT_NMAX = 1023;                       // longest moving average (odd)
 constexpr int PL_THREADS = 256;
-constexpr double PL_PI = 3.14159265358979323846;
 
 struct PilotGeom { int64_t F, S, R, NP, ND; };
 
@@ -46,36 +45,6 @@ __device__ __forceinline__ bool pilot_at(const PilotGeom &g, int64_t i, int64_t 
     if (r == 0) { *ord = g.S + q; return true; }
     *ord = q * (g.R - 1) + r - 1;
     return false;
-}
-
-// np.unwrap's correction for the step prev -> cur, in units of 2 pi (+-pi itself: 0, as numpy)
-__device__ __forceinline__ int wrap_count(double prev, double cur)
-{
-    const double d = cur - prev;
-    return d > PL_PI ? -1 : (d < -PL_PI ? 1 : 0);
-}
-
-__device__ __forceinline__ int block_sum_int(int s, int *red)
-{
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    int t = 0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < UW_THREADS / 64; w++) t += red[w];
-    return t;
-}
-
-// sum of a double over the workgroup, in a fixed order, to every thread.  Ends in a barrier: red may be used again.
-__device__ __forceinline__ double block_sum(double s, double *red)
-{
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    double t = 0.;
-    for (int w = 0; w < PL_THREADS / 64; w++) t += red[w];
-    __syncthreads();
-    return t;
 }
 
 // ------------------------------------------------------------------------------------------------ assemble / split
@@ -166,17 +135,7 @@ __global__ void __launch_bounds__(UW_THREADS) pilot_theta_kernel(PhaseArgs<R> a,
     }
     if (tid == 0) th[0] = base >= 1 ? pilot_angle<R>(a, mode, base - 1) : 0.;
     __syncthreads();
-    int s = 0;
-#pragma unroll
-    for (int r = 0; r < UW_PER_THREAD; r++) {
-        const int el = r * UW_THREADS + tid;
-        const int64_t k = base + el;
-        int j = 0;
-        if (k >= 1 && k < a.n) j = wrap_count(th[el], th[el + 1]);
-        if (el == 0) first_jump[mode * a.nchunk + blockIdx.x] = j;
-        s += j;
-    }
-    s = block_sum_int(s, red);
+    const int s = block_sum_int(strided_wrap_counts(th, base, a.n, first_jump + mode * a.nchunk + blockIdx.x), red);
     if (tid == 0) chunk_sum[mode * a.nchunk + blockIdx.x] = s;
 }
 
@@ -187,7 +146,7 @@ __global__ void __launch_bounds__(UW_THREADS) pilot_unwrap_kernel(double *__rest
     __shared__ double th[UW_CHUNK];
     __shared__ int corr[UW_CHUNK];
     __shared__ int wsum[UW_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int64_t mode = blockIdx.y;
     const int64_t base = (int64_t)blockIdx.x * UW_CHUNK;
 #pragma unroll
@@ -197,53 +156,18 @@ __global__ void __launch_bounds__(UW_THREADS) pilot_unwrap_kernel(double *__rest
         th[el] = k < n ? phase[mode * n + k] : 0.;
     }
     __syncthreads();
-    // thread t owns the UW_PER_THREAD consecutive elements from t * UW_PER_THREAD on
     int jmp[UW_PER_THREAD];
-    int local = 0;
-#pragma unroll
-    for (int r = 0; r < UW_PER_THREAD; r++) {
-        const int el = tid * UW_PER_THREAD + r;
-        const int64_t k = base + el;
-        int j = 0;
-        if (k >= 1 && k < n) j = el == 0 ? first_jump[mode * nchunk + blockIdx.x] : wrap_count(th[el - 1], th[el]);
-        local += j;
-        jmp[r] = local;
-    }
-    int incl = local;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int off = chunk_off[mode * nchunk + blockIdx.x] + incl - local;
-    for (int w = 0; w < wave; w++) off += wsum[w];
-#pragma unroll
-    for (int r = 0; r < UW_PER_THREAD; r++) corr[tid * UW_PER_THREAD + r] = off + jmp[r];
-    __syncthreads();
+    owned_wrap_counts(th, base, n, first_jump + mode * nchunk + blockIdx.x, jmp);
+    chunk_prefix(jmp, chunk_off[mode * nchunk + blockIdx.x], corr, wsum);
 #pragma unroll
     for (int r = 0; r < UW_PER_THREAD; r++) {
         const int el = r * UW_THREADS + tid;
         const int64_t k = base + el;
-        if (k < n) phase[mode * n + k] = th[el] + 2 * PL_PI * (double)corr[el];
+        if (k < n) phase[mode * n + k] = th[el] + 2 * QH_PI * (double)corr[el];
     }
 }
 
-// scratch of the phase: chunk sums | wrap count of every chunk's first pilot, behind `head` bytes the caller keeps for itself
-struct PhaseScratch { char *base; int *csum, *first; };
-int phase_scratch(int nmodes, int64_t nchunk, size_t head, PhaseScratch *s)
-{
-    const size_t o_sum = (head + 255) & ~(size_t)255, o_first = o_sum + (((size_t)nmodes * nchunk * sizeof(int) + 255) & ~(size_t)255);
-    void *sb = nullptr;
-    int rc = scratch(SCRATCH_PILOT, o_first + (size_t)nmodes * nchunk * sizeof(int), &sb);
-    if (rc) return rc;
-    s->base = (char *)sb;
-    s->csum = (int *)((char *)sb + o_sum);
-    s->first = (int *)((char *)sb + o_first);
-    return QH_OK;
-}
-
-template <typename R> void launch_phase(PhaseArgs<R> a, int nmodes, double *phase, const PhaseScratch &s)
+template <typename R> void launch_phase(PhaseArgs<R> a, int nmodes, double *phase, const UnwrapScratch &s)
 {
     const dim3 grid((unsigned)a.nchunk, nmodes);
     hipLaunchKernelGGL((pilot_theta_kernel<R>), grid, dim3(UW_THREADS), 0, g_stream, a, phase, s.csum, s.first);
@@ -285,7 +209,7 @@ __global__ void __launch_bounds__(PL_THREADS) pilot_interp_kernel(const Cx<R> *_
         ph = slope * (double)(i - knots[lo]) + p[lo];
     }
     trace[mode * span + i] = (R)ph;
-    const R t = (R)(ph - 2 * PL_PI * rint(ph / (2 * PL_PI)));
+    const R t = (R)(ph - 2 * QH_PI * rint(ph / (2 * QH_PI)));
     R sn, cs;
     if constexpr (sizeof(R) == 4) sincosf(t, &sn, &cs); else sincos(t, &sn, &cs);
     const Cx<R> x = ldg(E + mode * L + i);
@@ -300,7 +224,7 @@ __global__ void __launch_bounds__(PL_THREADS) pilot_fit_kernel(const double *__r
     const double *y = phase + (int64_t)blockIdx.x * n;
     double s = 0.;
     for (int64_t k = threadIdx.x; k < n; k += PL_THREADS) s += y[k];
-    const double ybar = block_sum(s, red) / (double)n;
+    const double ybar = block_sum<PL_THREADS>(s, red) / (double)n;
     if (mean && threadIdx.x == 0) mean[blockIdx.x] = ybar;
     if (!fit) return;                                  // (uniform)
     const double kbar = 0.5 * (double)(n - 1);
@@ -310,11 +234,11 @@ __global__ void __launch_bounds__(PL_THREADS) pilot_fit_kernel(const double *__r
         sxy += dk * (y[k] - ybar);
         sxx += dk * dk;
     }
-    sxy = block_sum(sxy, red);
-    sxx = block_sum(sxx, red);
+    sxy = block_sum<PL_THREADS>(sxy, red);
+    sxx = block_sum<PL_THREADS>(sxx, red);
     if (threadIdx.x == 0) {
         const double slope = sxy / sxx;
-        fit[2 * blockIdx.x] = slope / (2 * PL_PI);
+        fit[2 * blockIdx.x] = slope / (2 * QH_PI);
         fit[2 * blockIdx.x + 1] = ybar - slope * kbar;
     }
 }
@@ -415,8 +339,8 @@ int pilot_phase_dev(const void *E, int nmodes, int64_t L, const int64_t *where, 
     PhaseArgs<R> a;
     if ((rc = phase_args<R>(&a, "pilot_phase", E, nmodes, L, where, npf, nframes, F, span, n, sent, nref))) return rc;
     QH_REQUIRE(phase, "pilot_phase: phase must be given");
-    PhaseScratch s;
-    if ((rc = phase_scratch(nmodes, a.nchunk, 0, &s))) return rc;
+    UnwrapScratch s;
+    if ((rc = unwrap_scratch(SCRATCH_PILOT, nmodes, a.nchunk, 0, &s))) return rc;
     launch_phase<R>(a, nmodes, phase, s);
     QH_HIP(hipGetLastError());
     return QH_OK;
@@ -449,11 +373,11 @@ int pilot_cpe_dev(const void *E, int nmodes, int64_t L, const int64_t *where, in
     QH_REQUIRE(Eout && trace && grid_ok(span, PL_THREADS), "pilot_cpe: Eout and trace must be given");
     const int64_t nk = n - N + 1;
     // scratch: phase | knot phases | knot positions | (chunk sums | first counts)
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_kph = up((size_t)nmodes * n * sizeof(double)), o_pos = o_kph + up((size_t)nmodes * nk * sizeof(double)), head = o_pos + up((size_t)nk * sizeof(int64_t));
-    PhaseScratch s;
-    if ((rc = phase_scratch(nmodes, a.nchunk, head, &s))) return rc;
-    double *phase = (double *)s.base, *kph = (double *)(s.base + o_kph);
+    ScratchLayout head;
+    const size_t o_phase = head.take((size_t)nmodes * n * sizeof(double)), o_kph = head.take((size_t)nmodes * nk * sizeof(double)), o_pos = head.take((size_t)nk * sizeof(int64_t));
+    UnwrapScratch s;
+    if ((rc = unwrap_scratch(SCRATCH_PILOT, nmodes, a.nchunk, head.total, &s))) return rc;
+    double *phase = (double *)(s.base + o_phase), *kph = (double *)(s.base + o_kph);
     int64_t *kpos = (int64_t *)(s.base + o_pos);
     launch_phase<R>(a, nmodes, phase, s);
     hipLaunchKernelGGL(pilot_knots_kernel, dim3((unsigned)((nk + PL_THREADS - 1) / PL_THREADS), nmodes), dim3(PL_THREADS), 0, g_stream, (const double *)phase, n, N, where, npf, F,
@@ -475,8 +399,8 @@ template <typename R> int pair_phase(const char *who, const void *rec, const voi
     a.E = (const Cx<R> *)rec; a.sent = (const Cx<R> *)ref; a.where = nullptr;
     a.L = n; a.npf = 1; a.F = 1; a.span = n; a.n = n; a.nref = n;
     a.nchunk = (n + UW_CHUNK - 1) / UW_CHUNK;
-    PhaseScratch s;
-    int rc = phase_scratch(nmodes, a.nchunk, (size_t)nmodes * n * sizeof(double), &s);
+    UnwrapScratch s;
+    int rc = unwrap_scratch(SCRATCH_PILOT, nmodes, a.nchunk, (size_t)nmodes * n * sizeof(double), &s);
     if (rc) return rc;
     *phase = (double *)s.base;
     launch_phase<R>(a, nmodes, *phase, s);

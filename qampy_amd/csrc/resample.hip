@@ -232,7 +232,7 @@ int resample_dev(const void *E, int nmodes, int64_t L, const double *h, int ntap
     const R *tab;
     if ((rc = rs_table<R>(h, ntaps, up, J, &tab))) return rc;
     const size_t lds = (size_t)(G * RS_R * down + JC + 1) * sizeof(Cx<R>) + (size_t)up * (JC + 1) * sizeof(R);
-    if (lds > 64 * 1024) QH_HIP(hipFuncSetAttribute((const void *)resample_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if ((rc = dyn_lds(resample_kernel<R>, lds))) return rc;
     const int nthr = (up * G + 63) / 64 * 64;
     hipLaunchKernelGGL((resample_kernel<R>), dim3((unsigned)ntiles, nmodes), dim3(nthr), lds, g_stream, (const Cx<R> *)E, (Cx<R> *)out, L, Lout,
                        tab, up, down, (ntaps - 1) / 2, J, JC, G, (R)gain);

@@ -166,8 +166,6 @@ __global__ void __launch_bounds__(SY_T) sync_labels_kernel(const int32_t *__rest
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static size_t sy_up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 template <typename R> int xcorr_dev(const void *x, int nx_rows, int64_t nx, const void *y, int64_t ny, void *cc)
 {
     int rc = ensure_init();
@@ -180,10 +178,11 @@ template <typename R> int xcorr_dev(const void *x, int nx_rows, int64_t nx, cons
     int lg = SY_LG_MIN;
     while (((int64_t)1 << lg) < n) lg++;
     const int64_t P = (int64_t)1 << lg;
-    const size_t b_y = sy_up256((size_t)P * sizeof(Cx<R>));
+    ScratchLayout lay;
+    const size_t o_y = lay.take((size_t)P * sizeof(Cx<R>)), o_spec = lay.take((size_t)nx_rows * P * sizeof(Cx<R>));
     void *base = nullptr;
-    if ((rc = scratch(SCRATCH_SYNC, b_y + (size_t)nx_rows * P * sizeof(Cx<R>), &base))) return rc;
-    Cx<R> *yrev = (Cx<R> *)base, *spec = (Cx<R> *)((char *)base + b_y);
+    if ((rc = scratch(SCRATCH_SYNC, lay.total, &base))) return rc;
+    Cx<R> *yrev = (Cx<R> *)((char *)base + o_y), *spec = (Cx<R> *)((char *)base + o_spec);
     hipLaunchKernelGGL((sync_reverse_kernel<R>), dim3((unsigned)((ny + SY_T - 1) / SY_T)), dim3(SY_T), 0, g_stream, (const Cx<R> *)y, ny, yrev);
     QH_HIP(hipGetLastError());
     return fft_correlate_pow2<R>(x, nx_rows, nx, yrev, ny, P, spec, cc, n);

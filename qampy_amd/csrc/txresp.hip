@@ -366,9 +366,19 @@ template <int NS> __global__ void __launch_bounds__(SOS_W) sos_carry_kernel(doub
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static size_t tx_up256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 static bool tx_sizes_ok(int nmodes, int64_t L) { return nmodes >= 1 && nmodes <= TX_MAXMODES && L >= 0 && (L + TX_TILE - 1) / TX_TILE <= 0x7fffffffLL; }
+
+// scratch slot SCRATCH_TXRESP: the row extrema a call forms for itself (own_extrema), at its base | the tile extrema, at *part
+static int extrema_scratch(int nmodes, int64_t ntiles, void **base, double **part)
+{
+    ScratchLayout lay;
+    lay.take(2 * (size_t)nmodes * sizeof(double));
+    const size_t o_part = lay.take(2 * (size_t)nmodes * ntiles * sizeof(double));
+    int rc = scratch(SCRATCH_TXRESP, lay.total, base);
+    if (rc) return rc;
+    *part = (double *)((char *)*base + o_part);
+    return QH_OK;
+}
 
 // ext: nmodes pairs of doubles on the device
 template <typename R> int row_extrema_dev(const void *E, int nmodes, int64_t L, double *ext)
@@ -378,8 +388,8 @@ template <typename R> int row_extrema_dev(const void *E, int nmodes, int64_t L, 
     QH_REQUIRE(E && ext && tx_sizes_ok(nmodes, L) && L >= 1, "row_extrema: E, ext, 1 to 1024 modes, at least one sample");
     const int64_t ntiles = (L + EXT_TILE - 1) / EXT_TILE;
     void *base = nullptr;
-    if ((rc = scratch(SCRATCH_TXRESP, tx_up256(2 * (size_t)nmodes * sizeof(double)) + 2 * (size_t)nmodes * ntiles * sizeof(double), &base))) return rc;
-    double *part = (double *)((char *)base + tx_up256(2 * (size_t)nmodes * sizeof(double)));
+    double *part = nullptr;
+    if ((rc = extrema_scratch(nmodes, ntiles, &base, &part))) return rc;
     hipLaunchKernelGGL((extrema_part_kernel<R>), dim3((unsigned)ntiles, nmodes), dim3(TX_T), 0, g_stream, (const Cx<R> *)E, L, part);
     hipLaunchKernelGGL(extrema_final_kernel, dim3(nmodes), dim3(TX_T), 0, g_stream, (const double *)part, ntiles, ext);
     QH_HIP(hipGetLastError());
@@ -390,8 +400,8 @@ template <typename R> int row_extrema_dev(const void *E, int nmodes, int64_t L, 
 template <typename R> static int own_extrema(const void *E, int nmodes, int64_t L, const double **ext)
 {
     void *base = nullptr;
-    const int64_t ntiles = (L + EXT_TILE - 1) / EXT_TILE;
-    int rc = scratch(SCRATCH_TXRESP, tx_up256(2 * (size_t)nmodes * sizeof(double)) + 2 * (size_t)nmodes * ntiles * sizeof(double), &base);
+    double *part = nullptr;
+    int rc = extrema_scratch(nmodes, (L + EXT_TILE - 1) / EXT_TILE, &base, &part);
     if (rc) return rc;
     *ext = (const double *)base;
     return row_extrema_dev<R>(E, nmodes, L, (double *)base);
@@ -436,13 +446,12 @@ template <typename R> int modulator_dev(const void *E, int nmodes, int64_t L, co
     QH_REQUIRE(!have_amp || std::isfinite(tgt_v), "modulator: the target voltage must be finite");
     if (L == 0) return QH_OK;
     if (have_amp && !ext && (rc = own_extrema<R>(E, nmodes, L, &ext))) return rc;
-    const double pi = 3.14159265358979323846;
     ModPrm p;
     p.amp = have_amp ? 1 : 0; p.tgt = tgt_v;
     p.dr = prm[0]; p.di = prm[1]; p.gr = prm[2]; p.gi = prm[3];
     p.pr = (1 + prm[4]) / 4; p.mr = (1 - prm[4]) / 4; p.pi = (1 + prm[5]) / 4; p.mi = (1 - prm[5]) / 4;
     const double d = prm[6], go = prm[7];
-    const double ca = cos(pi / 4 - pi * d / 2), sa = sin(pi / 4 - pi * d / 2), cb = cos(pi / 4 + pi * d / 2), sb = sin(pi / 4 + pi * d / 2);
+    const double ca = cos(QH_PI / 4 - QH_PI * d / 2), sa = sin(QH_PI / 4 - QH_PI * d / 2), cb = cos(QH_PI / 4 + QH_PI * d / 2), sb = sin(QH_PI / 4 + QH_PI * d / 2);
     const double fa = -1.0 / ((1 + go) * (1 + p.gr)), fb = -go / ((1 + go) * (1 + p.gi));
     p.ar = fa * ca; p.ai = fa * sa; p.br = fb * cb; p.bi = fb * sb;
     hipLaunchKernelGGL((modulator_kernel<R>), dim3((unsigned)((L + TX_TILE - 1) / TX_TILE), nmodes), dim3(TX_T), 0, g_stream, (const Cx<R> *)E, (Cx<R> *)out, L, nmodes,
