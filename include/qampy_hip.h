@@ -789,6 +789,47 @@ int qh_pilot_const_phase_c128_dev(const void *rec, const void *ref, int nmodes, 
 int qh_rotate_rows_c64_dev(const void *E, int nmodes, int64_t L, const double *phi, void *out);
 int qh_rotate_rows_c128_dev(const void *E, int nmodes, int64_t L, const double *phi, void *out);
 
+/* ---- digital pre-compensation (csrc/precomp.hip; qampy/core/digital_pre_compensation.py, qampy/core/pythran_dsp.py:201-240).  Device pointers,
+ * enqueued on the current stream, nothing read back, a repeated call bit-identical.  Rows are (nmodes, L).
+ * Pattern index: lev[k] = argmin |x[k] - levels| (the first minimum wins a tie, a NaN sample gets level 0) and
+ * p[i] = sum_j lev[(i - mem_len / 2 + j) mod L] M^(mem_len - 1 - j), j = 0 .. mem_len - 1, for any L >= 1.  Either two rail tables in device memory -
+ * lev_I (MI float64, strictly increasing) decides the real parts into idx_I with M = MI, lev_Q (MQ, 2 <= MQ <= MI) the imaginary parts into idx_Q with
+ * M = MQ, alphabet NULL - or one alphabet (M points as float64 re / im pairs, lev_I and lev_Q NULL; squared distances in double), and idx_I and idx_Q
+ * get the same numbers.  Either index row may be NULL.  1 <= mem_len <= 15, 2 <= M <= 4096, M^mem_len <= 2^24 (MI^mem_len for rails). */
+int qh_pattern_index_c64_dev(const void *E, int nmodes, int64_t L, const double *lev_I, int MI, const double *lev_Q, int MQ, const double *alphabet, int M,
+                             int mem_len, int32_t *idx_I, int32_t *idx_Q);
+int qh_pattern_index_c128_dev(const void *E, int nmodes, int64_t L, const double *lev_I, int MI, const double *lev_Q, int MQ, const double *alphabet, int M,
+                              int mem_len, int32_t *idx_I, int32_t *idx_Q);
+/* Average error per pattern: err = tx - rx (in double) at the positions where mask is not 0 (mask NULL: everywhere; mask_rows 1: one (L) mask for all
+ * rows, mask_rows nmodes: (nmodes, L)); ea (nmodes, N) complex128 = sum_I[p] / max(nI[p], 1) + 1j sum_Q[p] / max(nQ[p], 1), nI and nQ (nmodes, N)
+ * int32 the counts, so that tables of several captures can be merged.  An index outside [0, N) is left out.  The sums are 64-bit integers in fixed
+ * point at a power-of-two scale chosen from the row's max |err|: at least 37 bits below that maximum per sample, the same bits on every call.
+ * 1 <= L <= 2^24, 1 <= N <= 2^24; errors must be finite. */
+int qh_lut_accumulate_c64_dev(const void *tx, const void *rx, int nmodes, int64_t L, const int32_t *idx_I, const int32_t *idx_Q, const uint8_t *mask,
+                              int mask_rows, int64_t N, void *ea, int32_t *nI, int32_t *nQ);
+int qh_lut_accumulate_c128_dev(const void *tx, const void *rx, int nmodes, int64_t L, const int32_t *idx_I, const int32_t *idx_Q, const uint8_t *mask,
+                               int mask_rows, int64_t N, void *ea, int32_t *nI, int32_t *nQ);
+/* out = sig + gain (ea[idx_I].re + 1j ea[idx_Q].im), formed in double and rounded once; out may be sig. */
+int qh_lut_apply_c64_dev(const void *sig, int nmodes, int64_t L, const void *ea, int64_t N, const int32_t *idx_I, const int32_t *idx_Q, double gain, void *out);
+int qh_lut_apply_c128_dev(const void *sig, int nmodes, int64_t L, const void *ea, int64_t N, const int32_t *idx_I, const int32_t *idx_Q, double gain, void *out);
+/* The same with the indices of qh_pattern_index_*_dev formed on the fly from sig (no index row is written); N must be M^mem_len, and out another
+ * buffer than sig (a window reads its neighbours). */
+int qh_lut_predistort_c64_dev(const void *sig, int nmodes, int64_t L, const double *lev_I, int MI, const double *lev_Q, int MQ, const double *alphabet, int M,
+                              int mem_len, const void *ea, int64_t N, double gain, void *out);
+int qh_lut_predistort_c128_dev(const void *sig, int nmodes, int64_t L, const double *lev_I, int MI, const double *lev_Q, int MQ, const double *alphabet, int M,
+                               int mem_len, const void *ea, int64_t N, double gain, void *out);
+/* out = 2 vpi_re asin(re) + 1j 2 vpi_im asin(im), in double, rounded once; NaN where a part lies outside [-1, 1], and - as numpy's complex product
+ * 1j im leaves it - also in the real part where the imaginary part is NaN.  clip > 0: both parts are clamped to
+ * +-clip first (a NaN stays one); clip == 0: no clamp.  out may be sig. */
+int qh_comp_mod_sin_c64_dev(const void *sig, int nmodes, int64_t L, double vpi_re, double vpi_im, double clip, void *out);
+int qh_comp_mod_sin_c128_dev(const void *sig, int nmodes, int64_t L, double vpi_re, double vpi_im, double clip, void *out);
+/* p_f (sim_len bins in fftfreq order, the field's dtype) of comp_dac_resp, built in double: n_f the raised-cosine power response of roll-off beta at
+ * the symbol rate fb on the grid fftfreq(sim_len) fs, d_f the response of the nsec (1 .. 4) second-order sections sos (HOST pointer, nsec x 6, a0 = 1)
+ * at 2 pi k / sim_len, alpha = noise sum(|d_f|^2 n_f fs / sim_len) summed in a fixed order, p_f = n_f conj(d_f) / (n_f |d_f|^2 + alpha).
+ * 1 <= sim_len <= 2^24. */
+int qh_dac_preemphasis_table_c64_dev(int64_t sim_len, double fb, double fs, double beta, double noise, const double *sos, int nsec, void *p_f);
+int qh_dac_preemphasis_table_c128_dev(int64_t sim_len, double fb, double fs, double beta, double noise, const double *sos, int nsec, void *p_f);
+
 #ifdef __cplusplus
 }
 #endif

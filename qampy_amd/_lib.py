@@ -43,6 +43,10 @@ _PILOT_FRAME = [_vp, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i, C.c_double, _vp, 
 _PILOT_SPLIT = [_vp, _i, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp]                     # E, nmodes, L, F, S, R, frames, nfr, payload, pilots
 _PILOT_PHASE = [_vp, _i, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64]              # E, nmodes, L, where, npf, nframes, F, span, n, sent, nref
 
+_PATTERN = [_vp, _i, _i64, _vp, _i, _vp, _i, _vp, _i, _i]                                   # E, nmodes, L, lev_I, MI, lev_Q, MQ, alphabet, M, mem_len
+_LUT_ACC = [_vp, _vp, _i, _i64, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp]                     # tx, rx, nmodes, L, idx_I, idx_Q, mask, mask_rows, N, ea, nI, nQ
+_DAC_TABLE = [_i64, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _i, _vp]           # sim_len, fb, fs, beta, noise, sos (host), nsec, p_f
+
 
 def _train_sig(mu_ptr, dev=False):
     sig = list(_TRAIN)
@@ -178,6 +182,14 @@ SIGNATURES = {
     "qh_pilot_foe_c64_dev": [_vp, _vp, _i, _i64, _i, _vp, _vp], "qh_pilot_foe_c128_dev": [_vp, _vp, _i, _i64, _i, _vp, _vp],   # rec, ref, nmodes, n, average, fit, fo
     "qh_pilot_const_phase_c64_dev": [_vp, _vp, _i, _i64, _vp], "qh_pilot_const_phase_c128_dev": [_vp, _vp, _i, _i64, _vp],     # rec, ref, nmodes, n, phase
     "qh_rotate_rows_c64_dev": [_vp, _i, _i64, _vp, _vp], "qh_rotate_rows_c128_dev": [_vp, _i, _i64, _vp, _vp],                 # E, nmodes, L, phi, out
+    "qh_pattern_index_c64_dev": _PATTERN + [_vp, _vp], "qh_pattern_index_c128_dev": _PATTERN + [_vp, _vp],                     # ..., idx_I, idx_Q
+    "qh_lut_accumulate_c64_dev": _LUT_ACC, "qh_lut_accumulate_c128_dev": _LUT_ACC,
+    "qh_lut_apply_c64_dev": [_vp, _i, _i64, _vp, _i64, _vp, _vp, C.c_double, _vp],                                             # sig, nmodes, L, ea, N, idx_I, idx_Q, gain, out
+    "qh_lut_apply_c128_dev": [_vp, _i, _i64, _vp, _i64, _vp, _vp, C.c_double, _vp],
+    "qh_lut_predistort_c64_dev": _PATTERN + [_vp, _i64, C.c_double, _vp], "qh_lut_predistort_c128_dev": _PATTERN + [_vp, _i64, C.c_double, _vp],      # ..., ea, N, gain, out
+    "qh_comp_mod_sin_c64_dev": [_vp, _i, _i64, C.c_double, C.c_double, C.c_double, _vp],                                       # sig, nmodes, L, vpi_re, vpi_im, clip, out
+    "qh_comp_mod_sin_c128_dev": [_vp, _i, _i64, C.c_double, C.c_double, C.c_double, _vp],
+    "qh_dac_preemphasis_table_c64_dev": _DAC_TABLE, "qh_dac_preemphasis_table_c128_dev": _DAC_TABLE,
 }
 
 PIT_MAXPASS, PIT_MAXCHUNK = 24, 32
