@@ -830,6 +830,30 @@ int qh_comp_mod_sin_c128_dev(const void *sig, int nmodes, int64_t L, double vpi_
 int qh_dac_preemphasis_table_c64_dev(int64_t sim_len, double fb, double fs, double beta, double noise, const double *sos, int nsec, void *p_f);
 int qh_dac_preemphasis_table_c128_dev(int64_t sim_len, double fb, double fs, double beta, double noise, const double *sos, int nsec, void *p_f);
 
+/* ---- theory curves (csrc/metrics.hip, csrc/source.hip; qampy/theory.py cal_gmi / sim_mi_mc / generate_ps_symbols, qampy/core/pythran_dsp.py:181-197).
+ * Device pointers unless said otherwise, enqueued on the current stream, nothing read back, a repeated call bit-identical.
+ * Monte-Carlo noise: z (nsnr, ns), z[p][l] = (g0 + 1j g1) sqrt(1 / (2 snr[p])), snr (nsnr) float64 linear, (g0, g1) the two standard normals of Philox
+ * counter (l low, l high, p, stream 3) under the key seed - every SNR point its own draws.  1 <= nsnr <= 65535, 1 <= ns <= 2^31. */
+int qh_awgn_mc_noise_c64_dev(void *z, const double *snr, int nsnr, int64_t ns, uint64_t seed);
+int qh_awgn_mc_noise_c128_dev(void *z, const double *snr, int nsnr, int64_t ns, uint64_t seed);
+/* Monte-Carlo GMI and MI of the alphabet (M = 2^nbits points, nbits 1 .. 10, point g carries label g) at every SNR point over the draws z (nsnr, ns):
+ * out (nsnr, 2 + nbits) float64 = [gmi, mi, gmi of bit 0 .. nbits - 1 (MSB first)], gmi = cal_gmi_mc's value for the draws z[p], mi = cal_mi_mc(z[p],
+ * alphabet, 1 / snr[p]).  Every sum of exponentials is shifted by its own largest exponent: finite for any z and snr > 0.  The SNR points run in
+ * batches that keep the workgroup partials within 32 MiB of the calling thread's scratch, which the qh_metrics_*_dev calls use too: the scratch
+ * belongs to the host thread, not to a stream, so after qh_use_stream() a call here and a metrics call of the same thread on another library
+ * stream must be ordered by the caller (an event, or qh_stream_sync). */
+int qh_awgn_mc_c64_dev(const void *alphabet, int M, const double *snr, int nsnr, const void *z, int64_t ns, double *out);
+int qh_awgn_mc_c128_dev(const void *alphabet, int M, const double *snr, int nsnr, const void *z, int64_t ns, double *out);
+/* Probabilistically shaped symbols: out (nmodes, N) = level[i] + 1j level[q], i and q the number of entries of cdf that are <= u, u = word 2^-32 of
+ * the Philox words x (i) and y (q) of counter (n low, n high, mode, stream 4) under the key seed.  level and cdf: HOST tables of L <= 64 float64
+ * entries, cdf non-decreasing with cdf[L - 1] == 1.  labels (nmodes, N) int32, or NULL, receives label_table[i L + q], label_table (L, L) int32 in
+ * device memory.  1 <= nmodes <= 65535, 1 <= N <= 2^31 (one workgroup per 1024 samples of a mode, no stride: the limit of the
+ * other sources of csrc/source.hip). */
+int qh_ps_symbols_c64_dev(void *out, int nmodes, int64_t N, const double *level, const double *cdf, int L, uint64_t seed, int32_t *labels,
+                          const int32_t *label_table);
+int qh_ps_symbols_c128_dev(void *out, int nmodes, int64_t N, const double *level, const double *cdf, int L, uint64_t seed, int32_t *labels,
+                           const int32_t *label_table);
+
 #ifdef __cplusplus
 }
 #endif

@@ -190,6 +190,10 @@ SIGNATURES = {
     "qh_comp_mod_sin_c64_dev": [_vp, _i, _i64, C.c_double, C.c_double, C.c_double, _vp],                                       # sig, nmodes, L, vpi_re, vpi_im, clip, out
     "qh_comp_mod_sin_c128_dev": [_vp, _i, _i64, C.c_double, C.c_double, C.c_double, _vp],
     "qh_dac_preemphasis_table_c64_dev": _DAC_TABLE, "qh_dac_preemphasis_table_c128_dev": _DAC_TABLE,
+    "qh_awgn_mc_noise_c64_dev": [_vp, _vp, _i, _i64, C.c_uint64], "qh_awgn_mc_noise_c128_dev": [_vp, _vp, _i, _i64, C.c_uint64],                # z, snr, nsnr, ns, seed
+    "qh_awgn_mc_c64_dev": [_vp, _i, _vp, _i, _vp, _i64, _vp], "qh_awgn_mc_c128_dev": [_vp, _i, _vp, _i, _vp, _i64, _vp],                      # alphabet, M, snr, nsnr, z, ns, out
+    "qh_ps_symbols_c64_dev": [_vp, _i, _i64, _vp, _vp, _i, C.c_uint64, _vp, _vp],                                                               # out, nmodes, N, level (host), cdf (host), L, seed, labels, label_table
+    "qh_ps_symbols_c128_dev": [_vp, _i, _i64, _vp, _vp, _i, C.c_uint64, _vp, _vp],
 }
 
 PIT_MAXPASS, PIT_MAXCHUNK = 24, 32

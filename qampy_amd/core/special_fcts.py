@@ -23,3 +23,9 @@ def rrcos_time(t, beta, T):
     a = np.pi / (4 * beta)
     h[atq] = beta / (T * np.sqrt(2)) * ((1 + 2 / np.pi) * np.sin(a) + (1 - 2 / np.pi) * np.cos(a))
     return h
+
+
+def q_function(x):
+    """Tail probability of the standard normal distribution, ``0.5 erfc(x / sqrt 2)`` (the Gaussian co-error function of the BER formulas)."""
+    from scipy.special import erfc
+    return erfc(np.asarray(x, dtype=np.float64) * np.sqrt(0.5)) / 2

@@ -17,6 +17,7 @@
 // repeated calls give bit-identical results (the class statistics of the SNR estimate too: each class is added by one
 // owner thread in index order).
 #include "common.h"
+#include "philox.h"
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -277,10 +278,137 @@ __global__ void __launch_bounds__(MET_THREADS) mi_mc_kernel(const Cx<R> *noise, 
     block_partials<1>(acc, partial);
 }
 
-// out[f] = sum over blocks of partial[b * F + f]: one wave per field, lane j adds blocks j, j + 64, ... in order
+// 2^x for x <= 0 where a result below the smallest normal number may be flushed to zero: in float the bare instruction (exp2f spends a compare, a
+// select, an add and a scaling on the subnormal range, which no sum here needs: its largest term is 1, or the sum is redone)
+__device__ __forceinline__ float exp2_neg(float x) { return __builtin_amdgcn_exp2f(x); }
+__device__ __forceinline__ double exp2_neg(double x) { return exp2(x); }
+
+// Monte-Carlo GMI and MI of an alphabet over AWGN: cal_gmi_mc (pythran_dsp.py:181-197) and cal_mi_mc (:289-300) on the same draws.  With
+// y = s_i + conj(z_l) the reference's exponent |s_i - s_j|^2 + 2 Re(z_l (s_i - s_j)) is |y - s_j|^2 - |z_l|^2, so its nbits * 2 * (M / 2) ratios of
+// two sums per draw are the GMI terms of the synthetic received point y sent as point i: one sum over the alphabet, S_all, and its split into the
+// (bit, side) sub-sums serve every bit, and log2(S_all / e_i) is cal_mi_mc's term.  A work item is (SNR point p = blockIdx.y, sent point i, draw l);
+// the pairs (i, l) of a point are strided over the grid's x, so a capped grid loops.
+//   partial fields per (block, p): sum log2(S_all / e_i), then per bit k sum log2(S_all / S_{k, side of i}).
+// Shifts: every exponent is taken relative to the nearest point of y, so S_all lies in [1, M].  The side of the sent point can be far from y (a large
+// draw): when one of its sums falls below TINY the item is redone with each own side shifted by that side's own nearest point, as the complex64 LLRs
+// are, so no sum underflows whatever z holds.  Above TINY the largest term of the sum is a normal number with its full relative precision.
+template <typename R, int NB>
+__global__ void __launch_bounds__(MET_THREADS) awgn_mc_kernel(const Cx<R> *alphabet, const double *snr, const Cx<R> *z, int64_t ns, double *partial)
+{
+    constexpr int M = 1 << NB, F = 1 + NB, LB = NB < 6 ? NB : 6, HB = NB - LB, BLK = 1 << LB;
+    const R TINY = sizeof(R) == 4 ? (R)0x1p-100 : (R)0x1p-900;
+    __shared__ Cx<R> sy[M];
+    load_alphabet<R, M>(sy, alphabet);
+    const int p = blockIdx.y;
+    const R t = (R)snr[p] * (R)LOG2E;
+    const Cx<R> *zp = z + (size_t)p * ns;
+    const R inf = __builtin_inf();
+    double acc[F];
+#pragma unroll
+    for (int f = 0; f < F; f++) acc[f] = 0;
+    const int64_t P = ns * M;
+    for (int64_t q = (int64_t)blockIdx.x * MET_THREADS + threadIdx.x; q < P; q += (int64_t)gridDim.x * MET_THREADS) {
+        const int i = (int)(q & (M - 1));
+        const Cx<R> n = ldg(zp + (q >> NB)), si = sy[i];
+        const Cx<R> y{si.re + n.re, si.im - n.im};
+        R dmin = inf;
+#pragma unroll 16
+        for (int g = 0; g < M; g++) dmin = min_(dmin, dist2(y, sy[g]));
+        // the alphabet in blocks of BLK = 2^LB points: inside a block the low LB label bits are fixed at compile time (the block unrolls), the
+        // high HB bits are the block's number and take the block's sum
+        R s0[NB], s1[NB];
+#pragma unroll
+        for (int k = 0; k < NB; k++) s0[k] = s1[k] = 0;
+#pragma unroll 1
+        for (int h = 0; h < (1 << HB); h++) {
+            const Cx<R> *blk = sy + h * BLK;
+            R sum = 0;
+#pragma unroll
+            for (int j = 0; j < BLK; j++) {
+                const R e = exp2_neg((dmin - dist2(y, blk[j])) * t);
+                sum += e;
+#pragma unroll
+                for (int k = 0; k < LB; k++) {
+                    if ((j >> (LB - 1 - k)) & 1) s1[HB + k] += e;
+                    else s0[HB + k] += e;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < HB; k++) {
+                if ((h >> (HB - 1 - k)) & 1) s1[k] += sum;
+                else s0[k] += sum;
+            }
+        }
+        const R la = log2_(s0[NB - 1] + s1[NB - 1]);
+        acc[0] += (double)((dist2(y, si) - dmin) * t) + (double)la;
+        R own[NB], low = inf;
+#pragma unroll
+        for (int k = 0; k < NB; k++) {
+            own[k] = (i >> (NB - 1 - k)) & 1 ? s1[k] : s0[k];
+            low = min_(low, own[k]);
+        }
+        if (low >= TINY) {
+#pragma unroll
+            for (int k = 0; k < NB; k++) acc[1 + k] += (double)la - (double)log2_(own[k]);
+        } else {                             // rare: per-side shifts; bit k of g ^ i is 0 on the sent point's side
+            R m[NB];
+#pragma unroll
+            for (int k = 0; k < NB; k++) { m[k] = inf; own[k] = 0; }
+#pragma unroll 1
+            for (int g = 0; g < M; g++) {
+                const R d = dist2(y, sy[g]);
+#pragma unroll
+                for (int k = 0; k < NB; k++) if ((((g ^ i) >> (NB - 1 - k)) & 1) == 0) m[k] = min_(m[k], d);
+            }
+#pragma unroll 1
+            for (int g = 0; g < M; g++) {
+                const R d = dist2(y, sy[g]);
+#pragma unroll
+                for (int k = 0; k < NB; k++) if ((((g ^ i) >> (NB - 1 - k)) & 1) == 0) own[k] += exp2_neg((m[k] - d) * t);
+            }
+#pragma unroll
+            for (int k = 0; k < NB; k++) acc[1 + k] += (double)la - (double)log2_(own[k]) + ((double)m[k] - (double)dmin) * (double)t;
+        }
+    }
+    block_partials<F>(acc, partial + (size_t)p * gridDim.x * F);
+}
+
+// z[p][l] = (g0 + j g1) sqrt(1 / (2 snr_p)), (g0, g1) the draw of counter (l, p, IMP_STREAM_MC): every SNR point its own noise, as the reference
+// draws anew per call; the draws depend on (seed, p, l) alone.
+template <typename R>
+__global__ void __launch_bounds__(MET_THREADS) awgn_mc_noise_kernel(Cx<R> *z, const double *snr, int64_t ns, unsigned k0, unsigned k1)
+{
+    const int64_t l = (int64_t)blockIdx.x * MET_THREADS + threadIdx.x;
+    if (l >= ns) return;
+    const int p = blockIdx.y;
+    const R sigma = (R)sqrt(1.0 / (2.0 * snr[p]));
+    R g0, g1;
+    imp_gauss(l, p, IMP_STREAM_MC, k0, k1, g0, g1);
+    stg(z + (size_t)p * ns + l, Cx<R>{g0 * sigma, g1 * sigma});
+}
+
+// out[p] = [gmi, mi, gmi_per_bit ...] from the sums of point p over its count = M ns items
+__global__ void __launch_bounds__(64) awgn_mc_finish_kernel(const double *sums, int nsnr, int nb, double count, double *out)
+{
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= nsnr) return;
+    const double *s = sums + (size_t)p * (1 + nb);
+    double *o = out + (size_t)p * (2 + nb), tot = 0;
+    for (int k = 0; k < nb; k++) {
+        o[2 + k] = 1.0 - s[1 + k] / count;
+        tot += s[1 + k];
+    }
+    o[0] = (double)nb - tot / count;
+    o[1] = (double)nb - s[0] / count;
+}
+
+// out[f] = sum over blocks of partial[b * F + f]: one wave per field, lane j adds blocks j, j + 64, ... in order (blockIdx.y: one such set of
+// nblk partials and F outputs after another)
 __global__ void __launch_bounds__(64) reduce_partials_kernel(const double *partial, int nblk, int F, double *out)
 {
     const int f = blockIdx.x;
+    partial += (size_t)blockIdx.y * nblk * F;
+    out += (size_t)blockIdx.y * F;
     double s = 0;
     for (int b = threadIdx.x; b < nblk; b += 64) s += partial[(size_t)b * F + f];
     s = wave_sum(s);
@@ -417,10 +545,10 @@ int nbits_of(int M)
     default: { constexpr int NB = 10; __VA_ARGS__; } break;                                                                    \
     }
 
-// sum of F fields over nblk block partials into out (device), fixed order
-int reduce_fields(const double *partial, int nblk, int F, double *out)
+// sum of F fields over nblk block partials into out (device), fixed order; batch: that many sets of partials and outputs, one behind the other
+int reduce_fields(const double *partial, int nblk, int F, double *out, int batch = 1)
 {
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(F), dim3(64), 0, g_stream, partial, nblk, F, out);
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(F, batch), dim3(64), 0, g_stream, partial, nblk, F, out);
     QH_HIP(hipGetLastError());
     return QH_OK;
 }
@@ -602,9 +730,70 @@ template <typename R> int mi_mc_host(const void *noise, int64_t L, const void *a
     return QH_OK;
 }
 
+constexpr int MC_MAXSNR = 65535;                 // SNR points of one launch (the grid's y)
+constexpr int64_t MC_MAXNS = (int64_t)1 << 31;    // draws per SNR point
+
+static int awgn_mc_sizes(int nsnr, int64_t ns)
+{
+    QH_REQUIRE(nsnr >= 1 && nsnr <= MC_MAXSNR, "awgn_mc: between 1 and 65535 SNR points");
+    QH_REQUIRE(ns >= 1 && ns <= MC_MAXNS, "awgn_mc: between 1 and 2^31 draws per SNR point");
+    return QH_OK;
+}
+
+template <typename R> int awgn_mc_noise_dev(void *z, const double *snr, int nsnr, int64_t ns, uint64_t seed)
+{
+    int rc = awgn_mc_sizes(nsnr, ns);
+    if (rc) return rc;
+    QH_REQUIRE(z && snr, "awgn_mc_noise: z and snr must be given");
+    if ((rc = ensure_init())) return rc;
+    hipLaunchKernelGGL((awgn_mc_noise_kernel<R>), dim3((unsigned)((ns + MET_THREADS - 1) / MET_THREADS), nsnr), dim3(MET_THREADS), 0, g_stream, (Cx<R> *)z,
+                       snr, ns, (unsigned)seed, (unsigned)(seed >> 32));
+    QH_HIP(hipGetLastError());
+    return QH_OK;
+}
+
+constexpr size_t MC_PARTIAL_DOUBLES = (size_t)1 << 22;      // most doubles of workgroup partials held at once (32 MiB)
+
+// out (nsnr, 2 + nbits) = [gmi, mi, gmi per bit] of every SNR point, nothing read back.  The SNR points go through in batches whose partials fit
+// MC_PARTIAL_DOUBLES - three launches per batch; a 31-point curve of 1024-QAM is one batch, 65535 points of it are 177 - and a point's result does
+// not depend on the batch it falls into.  The partials share slot 13 with metrics_dev: the slots belong to the calling host thread, whichever of
+// its library streams is current, so calls of the two on different streams of one thread have to be ordered by the caller.
+template <typename R> int awgn_mc_dev(const void *alphabet, int M, const double *snr, int nsnr, const void *z, int64_t ns, double *out)
+{
+    int rc = awgn_mc_sizes(nsnr, ns);
+    if (rc) return rc;
+    const int nb = nbits_of(M);
+    QH_REQUIRE(nb > 0, "awgn_mc: M must be 2^nbits, nbits in 1..10");
+    QH_REQUIRE(alphabet && snr && z && out, "awgn_mc: alphabet, snr, z and out must be given");
+    if ((rc = ensure_init())) return rc;
+    const int F = 1 + nb;
+    const unsigned g = grid_for(ns * M);
+    const int batch = (int)std::min<size_t>((size_t)nsnr, std::max<size_t>(1, MC_PARTIAL_DOUBLES / (((size_t)g + 1) * F)));
+    void *buf = nullptr;
+    if ((rc = scratch(13, ((size_t)g + 1) * batch * F * sizeof(double), &buf))) return rc;
+    double *part = (double *)buf, *tot = part + (size_t)g * batch * F;
+    for (int p0 = 0; p0 < nsnr; p0 += batch) {
+        const int n = std::min(batch, nsnr - p0);
+        QH_NB_DISPATCH(nb, hipLaunchKernelGGL((awgn_mc_kernel<R, NB>), dim3(g, n), dim3(MET_THREADS), 0, g_stream, (const Cx<R> *)alphabet, snr + p0,
+                                               (const Cx<R> *)z + (size_t)p0 * ns, ns, part))
+        QH_HIP(hipGetLastError());
+        if ((rc = reduce_fields(part, (int)g, F, tot, n))) return rc;
+        hipLaunchKernelGGL(awgn_mc_finish_kernel, dim3((n + 63) / 64), dim3(64), 0, g_stream, (const double *)tot, n, nb, (double)ns * (double)M,
+                           out + (size_t)p0 * (2 + nb));
+        QH_HIP(hipGetLastError());
+    }
+    return QH_OK;
+}
+
 }  // namespace qh
 
 extern "C" {
+int qh_awgn_mc_noise_c64_dev(void *z, const double *snr, int nsnr, int64_t ns, uint64_t seed) { return qh::awgn_mc_noise_dev<float>(z, snr, nsnr, ns, seed); }
+int qh_awgn_mc_noise_c128_dev(void *z, const double *snr, int nsnr, int64_t ns, uint64_t seed) { return qh::awgn_mc_noise_dev<double>(z, snr, nsnr, ns, seed); }
+int qh_awgn_mc_c64_dev(const void *alphabet, int M, const double *snr, int nsnr, const void *z, int64_t ns, double *out)
+{ return qh::awgn_mc_dev<float>(alphabet, M, snr, nsnr, z, ns, out); }
+int qh_awgn_mc_c128_dev(const void *alphabet, int M, const double *snr, int nsnr, const void *z, int64_t ns, double *out)
+{ return qh::awgn_mc_dev<double>(alphabet, M, snr, nsnr, z, ns, out); }
 int qh_soft_l_value_demapper_c64(const void *rx, int64_t N, int nbits, double snr, const void *alphabet, int M, double *L)
 { return qh::llr_host<float>(rx, N, nbits, snr, alphabet, M, 0, L); }
 int qh_soft_l_value_demapper_c128(const void *rx, int64_t N, int nbits, double snr, const void *alphabet, int M, double *L)

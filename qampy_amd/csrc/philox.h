@@ -31,6 +31,8 @@ __device__ __forceinline__ void gauss2(unsigned a, unsigned b, float &g0, float 
 
 // The impairments' draws (impair.hip, txresp.hip): counter (sample index low word, high word, mode, stream), key = the seed.
 constexpr unsigned IMP_STREAM_PHASE = 1u, IMP_STREAM_NOISE = 2u;
+// The theory curves' draws: the Monte-Carlo noise of metrics.hip (counter: draw, SNR point) and the shaped source of source.hip (counter: sample, mode).
+constexpr unsigned IMP_STREAM_MC = 3u, IMP_STREAM_SHAPE = 4u;
 constexpr double IMP_TWO_PI = QH_TWO_PI;
 
 // two independent standard normals of sample n of a mode, in the precision of the signal

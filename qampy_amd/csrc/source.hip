@@ -11,10 +11,12 @@
 //             workgroup SRC_SYMS = 8192 symbols, whatever nb: no symbol straddles a thread or a workgroup.
 //   map       bits (bytes, any non-zero value is a one) -> labels and / or alphabet[label], one thread per symbol; a label outside [0, M) -> 0.
 //   unmap     labels -> bits, one thread per symbol; the low nb bits of a label.
+//   shaped    probabilistically shaped symbols: two counter-based uniform draws per sample pick the I and the Q level (see ps_symbols_kernel).
 //
 // No atomics, no scratch: a repeated call is bit-identical.  Every launch is bounded by the call's arguments alone.
 #include "common.h"
 #include "prbs_core.h"
+#include "philox.h"
 
 namespace qh {
 
@@ -113,7 +115,65 @@ __global__ void __launch_bounds__(SRC_T) source_unmap_kernel(const int32_t *__re
     for (int j = 0; j < nb; j++) b[j] = (uint8_t)((label >> (nb - 1 - j)) & 1u);
 }
 
+// The shaped source (theory.generate_ps_symbols): rail I and rail Q of sample n of mode m each pick one of L levels with the probabilities px.
+// The Philox words x (I) and y (Q) of counter (n low, n high, m, IMP_STREAM_SHAPE) become u = word 2^-32 in double, and the level's index is the
+// number of entries of the cumulative table that are <= u (np.searchsorted(cdf, u, side="right")).  The table comes by value, padded to PS_LMAX
+// entries with 2 (never <= u), its last real entry 1 (never <= u either): the search is six fixed steps and its answer lies in [0, L).
+constexpr int PS_LMAX = 64;                         // most levels of a rail
+constexpr int PS_T = 256, PS_PER = 4, PS_TILE = PS_T * PS_PER;      // samples of one mode per workgroup
+struct PsTables { double cdf[PS_LMAX], level[PS_LMAX]; };
+
+template <typename R>
+__global__ void __launch_bounds__(PS_T) ps_symbols_kernel(const PsTables tab, int L, int64_t N, unsigned k0, unsigned k1, const int32_t *__restrict__ label_table,
+                                                           Cx<R> *__restrict__ out, int32_t *__restrict__ labels)
+{
+    __shared__ double cdf[PS_LMAX];
+    __shared__ R level[PS_LMAX];
+    if (threadIdx.x < PS_LMAX) { cdf[threadIdx.x] = tab.cdf[threadIdx.x]; level[threadIdx.x] = (R)tab.level[threadIdx.x]; }
+    __syncthreads();
+    const int m = blockIdx.y;
+#pragma unroll
+    for (int j = 0; j < PS_PER; j++) {
+        const int64_t n = (int64_t)blockIdx.x * PS_TILE + j * PS_T + threadIdx.x;
+        if (n >= N) break;
+        const Philox w = philox4x32_10((unsigned)n, (unsigned)((uint64_t)n >> 32), (unsigned)m, IMP_STREAM_SHAPE, k0, k1);
+        const double ui = (double)w.x * 0x1p-32, uq = (double)w.y * 0x1p-32;
+        int i = 0, q = 0;
+#pragma unroll
+        for (int step = PS_LMAX / 2; step >= 1; step >>= 1) {
+            if (cdf[i + step - 1] <= ui) i += step;
+            if (cdf[q + step - 1] <= uq) q += step;
+        }
+        stg(out + (size_t)m * N + n, Cx<R>{level[i], level[q]});
+        if (labels) labels[(size_t)m * N + n] = label_table[i * L + q];
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
+// cdf, level: HOST tables of L entries; label_table (L, L) int32 in device memory, needed when labels is given
+template <typename R>
+static int ps_symbols_dev(void *out, int nmodes, int64_t N, const double *level, const double *cdf, int L, uint64_t seed, int32_t *labels,
+                          const int32_t *label_table)
+{
+    QH_REQUIRE(nmodes >= 1 && nmodes <= 65535 && N >= 1 && N <= SRC_NMAX, "ps_symbols: 1 .. 65535 modes of 1 .. 2^31 samples");      // one workgroup per tile: 2^21 at the most
+    QH_REQUIRE(L >= 1 && L <= PS_LMAX, "ps_symbols: between 1 and 64 levels");
+    QH_REQUIRE(out && level && cdf, "ps_symbols: out, the levels and the cumulative table must be given");
+    QH_REQUIRE(!labels || label_table, "ps_symbols: labels need the label table");
+    PsTables tab;
+    for (int i = 0; i < PS_LMAX; i++) { tab.cdf[i] = 2.0; tab.level[i] = 0.0; }
+    for (int i = 0; i < L; i++) {
+        QH_REQUIRE(cdf[i] >= 0 && cdf[i] <= 1 && (i == 0 || cdf[i] >= cdf[i - 1]), "ps_symbols: the cumulative table must rise from >= 0 to 1");
+        tab.cdf[i] = cdf[i]; tab.level[i] = level[i];
+    }
+    QH_REQUIRE(cdf[L - 1] == 1.0, "ps_symbols: the last entry of the cumulative table must be 1");
+    int rc = ensure_init();
+    if (rc) return rc;
+    hipLaunchKernelGGL((ps_symbols_kernel<R>), dim3((unsigned)((N + PS_TILE - 1) / PS_TILE), nmodes), dim3(PS_T), 0, g_stream, tab, L, N, (unsigned)seed,
+                       (unsigned)(seed >> 32), label_table, (Cx<R> *)out, labels);
+    QH_HIP(hipGetLastError());
+    return QH_OK;
+}
+
 static int src_check_prbs(int order, int kind, int64_t seed, int64_t start)
 {
     QH_REQUIRE(order == 7 || order == 15 || order == 23 || order == 31, "prbs: the order must be one of 7, 15, 23, 31");
@@ -191,6 +251,12 @@ static int labels_to_bits_dev(const int32_t *labels, int64_t nsym, int nb, uint8
 }  // namespace qh
 
 extern "C" {
+int qh_ps_symbols_c64_dev(void *out, int nmodes, int64_t N, const double *level, const double *cdf, int L, uint64_t seed, int32_t *labels,
+                          const int32_t *label_table)
+{ return qh::ps_symbols_dev<float>(out, nmodes, N, level, cdf, L, seed, labels, label_table); }
+int qh_ps_symbols_c128_dev(void *out, int nmodes, int64_t N, const double *level, const double *cdf, int L, uint64_t seed, int32_t *labels,
+                           const int32_t *label_table)
+{ return qh::ps_symbols_dev<double>(out, nmodes, N, level, cdf, L, seed, labels, label_table); }
 int qh_prbs_bits_dev(int order, int kind, int64_t seed, int64_t start, int invert, int64_t n, uint8_t *bits)
 { return qh::prbs_bits_dev(order, kind, seed, start, invert, n, bits); }
 int qh_bits_to_labels_dev(const uint8_t *bits, int64_t nsym, int nb, int32_t *labels)

@@ -185,6 +185,37 @@ def make_symbols_dev(M, nsym, nmodes=2, order=(15, 23), seed=(None, None), kind=
     return out
 
 
+def make_ps_symbols_dev(M, nu, nsym, nmodes=2, seed=0, dtype=np.complex64):
+    """
+    Probabilistically shaped square M-QAM symbols made in HBM (``hip_dsp.ps_symbols_dev``, csrc/source.hip): the rails' levels drawn with the
+    Maxwell-Boltzmann probabilities ``theory.cal_ps_probablts(cal_symbols_qam(M), nu)`` (``nu`` on the un-normalised odd-integer levels), one launch
+    for all modes.  The alphabet is scaled analytically to unit mean power under ``px`` - ``scale**2 = 1 / (2 sum(px level**2))`` - so
+    ``alphabet[idx_tx] == symbols`` exactly and nothing is measured or read back.
+
+    Returns the keys of :func:`make_symbols_dev` - ``symbols (nmodes, nsym)``, ``idx_tx (nmodes, nsym) int32`` (Gray labels, ready for
+    ``cal_metrics_dev``), ``alphabet (M,)`` of :class:`qampy_amd._lib.DeviceArray`, ``alphabet_host``, ``M`` - and ``px`` and ``levels`` (the scaled
+    levels), host arrays.
+    """
+    from ._lib import DeviceArray
+    from .core import hip_dsp
+    if theory._is_cross(M) or M < 4:
+        raise ValueError("make_ps_symbols_dev: square QAM only (M = 4, 16, 64, ...)")
+    if nmodes < 1 or nsym < 1:
+        raise ValueError("make_ps_symbols_dev: at least one mode and one symbol")
+    if not np.isfinite(nu):
+        raise ValueError("make_ps_symbols_dev: the shaping factor must be finite")
+    levels, px = theory.cal_ps_probablts(theory.cal_symbols_qam(M), nu)
+    levels = levels / np.sqrt(2 * np.sum(px * levels ** 2))
+    side = levels.size
+    table = np.ascontiguousarray(theory.gray_code_qam(M).reshape(side, side).astype(np.int32))      # (I level, Q level) -> label: the raster order
+    alphabet = np.empty(M, dtype=dtype)
+    alphabet[table.ravel()] = (np.repeat(levels, side) + 1j * np.tile(levels, side)).astype(dtype)
+    hip_dsp.ps_cdf(px)                                       # the checks, before the device is touched
+    sy, idx = DeviceArray((nmodes, nsym), dtype), DeviceArray((nmodes, nsym), np.int32)
+    hip_dsp.ps_symbols_dev(sy, levels, px, seed, labels=idx, label_table=table)
+    return dict(symbols=sy, idx_tx=idx, alphabet=DeviceArray.from_host(alphabet), alphabet_host=alphabet, M=M, px=px, levels=levels)
+
+
 def make_pilot_frames_dev(M, frame_len, seq_len, ins_rat, nframes=1, nmodes=2, Mpilots=4, order=(15, 23), seed=(None, None), dtype=np.complex64,
                           repeat_data=True):
     """
