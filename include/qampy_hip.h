@@ -854,6 +854,31 @@ int qh_ps_symbols_c64_dev(void *out, int nmodes, int64_t N, const double *level,
 int qh_ps_symbols_c128_dev(void *out, int nmodes, int64_t N, const double *level, const double *cdf, int L, uint64_t seed, int32_t *labels,
                            const int32_t *label_table);
 
+/* ---- blind signal quality (csrc/blind.hip; qampy/core/signal_quality.py:122-271 norm_to_s0, cal_evm, cal_snr_qam, cal_s0, cal_snr_blind_qpsk).
+ * Device pointers, E (nrows, L) dense rows, enqueued on the current stream, nothing read back, no atomics: a repeated call is bit-identical.
+ * 1 <= nrows <= 65535, L >= 1.  The workgroup partials live in the calling thread's scratch (see qh_awgn_mc_*_dev on streams).
+ * Moments: block = 0: mom (nrows, 4) float64 = mean |E|^2, mean |E|^4, mean re, mean im of every row; block > 0: mom (nrows, L / block, 4), the
+ * same of every whole block of `block` samples (a shorter tail is left out); block > L is an argument error.  Terms and sums in double. */
+int qh_blind_moments_c64_dev(const void *E, int nrows, int64_t L, int64_t block, double *mom);
+int qh_blind_moments_c128_dev(const void *E, int nrows, int64_t L, int64_t block, double *mom);
+/* stats (n, 6) float64 = (r2, r4, S1, S2, snr, s0) from mom (n, 4): k = r2^2 / r4, S1 = 1 - 2 k - sqrt((2 - gamma)(2 k^2 - k)), S2 = gamma k - 1,
+ * snr = S1 / S2 (linear), s0 = r2 / (1 + S2 / S1); gamma = mean |a|^4 of the unit-power alphabet.  NaN / inf where the formula gives them. */
+int qh_blind_finish_dev(const double *mom, int64_t n, double gamma, double *stats);
+/* out = E / sqrt(stats[row][5]) in the precision of the row; out may be E. */
+int qh_scale_by_stat_c64_dev(const void *E, int nrows, int64_t L, const double *stats, void *out);
+int qh_scale_by_stat_c128_dev(const void *E, int nrows, int64_t L, const double *stats, void *out);
+/* evm_sum (nrows) float64: known NULL: the sum over a row's samples of min_j |E / sqrt(stats[row][5]) - alphabet[j]|^2, alphabet M <= 1024 points
+ * of E's type (already normalised); else the sum of |known / sqrt(stats_known[row][5]) - E / sqrt(stats[row][5])|^2, known (nrows, L) of E's type
+ * (alphabet and M are then ignored).  Distances in the precision of the row, sums in double. */
+int qh_blind_evm_c64_dev(const void *E, int nrows, int64_t L, const double *stats, const void *alphabet, int M, const void *known,
+                         const double *stats_known, double *evm_sum);
+int qh_blind_evm_c128_dev(const void *E, int nrows, int64_t L, const double *stats, const void *alphabet, int M, const void *known,
+                          const double *stats_known, double *evm_sum);
+/* out (nrows, 3) float64, or (nrows, L / block, 3) with block > 0 as above: P = mean |Eref|^2, var = P - |mean Eref|^2, 10 log10(P / var),
+ * Eref = (-E^4)^(1/4) on the principal branch. */
+int qh_qpsk_blind_c64_dev(const void *E, int nrows, int64_t L, int64_t block, double *out);
+int qh_qpsk_blind_c128_dev(const void *E, int nrows, int64_t L, int64_t block, double *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -194,6 +194,12 @@ SIGNATURES = {
     "qh_awgn_mc_c64_dev": [_vp, _i, _vp, _i, _vp, _i64, _vp], "qh_awgn_mc_c128_dev": [_vp, _i, _vp, _i, _vp, _i64, _vp],                      # alphabet, M, snr, nsnr, z, ns, out
     "qh_ps_symbols_c64_dev": [_vp, _i, _i64, _vp, _vp, _i, C.c_uint64, _vp, _vp],                                                               # out, nmodes, N, level (host), cdf (host), L, seed, labels, label_table
     "qh_ps_symbols_c128_dev": [_vp, _i, _i64, _vp, _vp, _i, C.c_uint64, _vp, _vp],
+    "qh_blind_moments_c64_dev": [_vp, _i, _i64, _i64, _vp], "qh_blind_moments_c128_dev": [_vp, _i, _i64, _i64, _vp],                            # E, nrows, L, block, mom
+    "qh_blind_finish_dev": [_vp, _i64, C.c_double, _vp],                                                                                        # mom, n, gamma, stats
+    "qh_scale_by_stat_c64_dev": [_vp, _i, _i64, _vp, _vp], "qh_scale_by_stat_c128_dev": [_vp, _i, _i64, _vp, _vp],                              # E, nrows, L, stats, out
+    "qh_blind_evm_c64_dev": [_vp, _i, _i64, _vp, _vp, _i, _vp, _vp, _vp],                                                                       # E, nrows, L, stats, alphabet, M, known, stats_known, evm_sum
+    "qh_blind_evm_c128_dev": [_vp, _i, _i64, _vp, _vp, _i, _vp, _vp, _vp],
+    "qh_qpsk_blind_c64_dev": [_vp, _i, _i64, _i64, _vp], "qh_qpsk_blind_c128_dev": [_vp, _i, _i64, _i64, _vp],                                  # E, nrows, L, block, out
 }
 
 PIT_MAXPASS, PIT_MAXCHUNK = 24, 32

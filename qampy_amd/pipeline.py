@@ -30,6 +30,38 @@ from .core import hip_dsp as _dsp
 # undamped, so a looser first stage would show up one-to-one in the result (round 2 used 0.06 there).
 
 
+def _blind_metrics(rows, M, block, ws):
+    """The blind estimators of hip_dsp on the rows of one DeviceArray: what ``blind_metrics`` of a receiver and of a bank return.  ``ws``: the
+    caller's dict of work buffers, made again when the shape or the block changes."""
+    nrows, N = rows.shape
+    block, nblocks = _dsp._blind_block("blind_metrics", block, N)
+    key = (nrows, N, block)
+    if ws.get("key") != key:
+        ws.clear()
+        D = DeviceArray
+        ws.update(key=key, mom=D((nrows, 4), np.float64), stats=D((nrows, 6), np.float64), evm=D((nrows,), np.float64),
+                  qpsk=D((nrows, 3), np.float64) if M == 4 else None)
+        if block:
+            ws.update(tmom=D((nrows, nblocks, 4), np.float64), tstats=D((nrows, nblocks, 6), np.float64))
+    stats = _dsp.blind_stats_dev(rows, M, stats=ws["stats"], mom=ws["mom"])
+    evm = _dsp.blind_evm_dev(rows, M, stats=stats, evm_sum=ws["evm"])
+    st = stats.to_host()
+    qpsk = _dsp.qpsk_blind_snr_dev(rows, out=ws["qpsk"]).to_host() if M == 4 else None
+    trace = None
+    if block:
+        trace = _dsp.blind_stats_dev(rows, M, block=block, stats=ws["tstats"], mom=ws["tmom"]).to_host()
+    out = []
+    with np.errstate(all="ignore"):
+        for i in range(nrows):
+            d = dict(snr=float(st[i, 4]), snr_db=float(10 * np.log10(st[i, 4])), s0=float(st[i, 5]), evm_blind=float(evm[i]))
+            if qpsk is not None:
+                d["snr_qpsk_db"] = float(qpsk[i, 2])
+            if trace is not None:
+                d["snr_trace"], d["s0_trace"] = trace[i, :, 4].copy(), trace[i, :, 5].copy()
+            out.append(d)
+    return out
+
+
 class ResidentReceiver:
     """
     One capture's worth of preallocated device state.
@@ -150,6 +182,7 @@ class ResidentReceiver:
         self._cd_buf = self._fe_buf = self._fe_mom = self._fe_coef = self._foe_fo = self._foe_stats = self._tx_mom = self._raw_buf = self._raw_mom = None
         self._idx_tx = self._idx_tx_src = None             # ser() / metrics(): the transmitted indices, cached per symbols_tx object
         self._sync_ws = {}                                 # buffers of sync="full" (symbols, correlation, peak table, label rows), kept from call to call
+        self._blind_ws = {}                                # buffers of blind_metrics() (moments, stats, distance sums), kept from call to call
         self._load_power = None                            # tier b: the clean power the last load() read (impair(snr=...) scales it)
         self._acq_asked = [False] * self.nstage            # tier b: the stage's acquisition chunk is known, or the device has been asked for it once
         self._gram = self._basis = None                    # what build_gram() made for this capture
@@ -809,6 +842,15 @@ class ResidentReceiver:
         return _ber.cal_metrics_dev(self.out if self.Mtestangles else self.eq, self._idx_tx, self.alphabet, snr_db, maxlag, window, trim,
                                     llr_minmax, sync=sync, sync_ws=self._sync_ws)
 
+    def blind_metrics(self, block=None):
+        """Signal quality of the recovered (else equalised) rows WITHOUT the transmitted symbols, computed in HBM (csrc/blind.hip) after the
+        pending post-processing: one dict per row with ``snr`` (linear, the second / fourth-moment estimate ``cal_snr_qam``), ``snr_db``, ``s0``
+        (``cal_s0``), ``evm_blind`` (``cal_evm`` on the S0-normalised row) and, for ``M == 4``, ``snr_qpsk_db`` (``cal_snr_blind_qpsk``).
+        ``block``: additionally ``snr_trace`` and ``s0_trace`` ``(N // block,)``, the estimator on every whole block of ``block`` symbols.
+        Only these scalars and traces cross to the host."""
+        self.wait_post()
+        return _blind_metrics(self.out if self.Mtestangles else self.eq, self.M, block, self._blind_ws)
+
     def _sync_workspace(self):
         return self._sync_ws
 
@@ -1097,6 +1139,11 @@ class ChannelBank:
         idx_tx = _ber.tx_indices_dev(np.ascontiguousarray(symbols_tx, dtype=self.ct), r.alphabet)
         return _ber.cal_metrics_dev((self.out if r.Mtestangles else self.eq).row(ch), idx_tx, r.alphabet, snr_db, maxlag, window, trim, llr_minmax, sync=sync,
                                     sync_ws=r._sync_ws)
+
+    def blind_metrics(self, ch, block=None):
+        """Per-row blind signal quality of channel ``ch`` (see :meth:`ResidentReceiver.blind_metrics`)."""
+        r = self.rx
+        return _blind_metrics((self.out if r.Mtestangles else self.eq).row(ch), r.M, block, r._blind_ws)
 
     def fetch(self, ch):
         _lib.sync()

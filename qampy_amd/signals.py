@@ -206,6 +206,23 @@ class SignalQAM(np.ndarray):
         est = est.reshape(-1, 3)
         return (est[:, 0], est[:, 1], est[:, 2]) if verbose else est[:, 0]
 
+    def normalize_and_center(self, symbol_based=False, synced=False):
+        """Every mode minus its mean and scaled to unit power, in place (signals.py:549-568).  Plain: the mean power of the centred row, on the
+        device (``row_moments_dev`` + ``center_scale_dev``).  ``symbol_based``: the signal power ``est_snr`` finds from the attached symbols
+        (``synced`` as there) - what low SNRs need, where the mean power is mostly noise."""
+        if not symbol_based:
+            from . import _lib
+            from .core import resample as _rs
+            rows = np.atleast_2d(np.asarray(self))
+            E = _lib.DeviceArray.from_host(rows if rows.dtype == np.complex64 else rows.astype(np.complex128))
+            _rs.center_scale_dev(E, _rs.row_moments_dev(E), power=1.0)
+            self[...] = E.to_host().reshape(self.shape)
+        else:
+            self -= np.asarray(self).mean(axis=-1)[:, None]
+            p = self.est_snr(synced=synced, verbose=True)[1]
+            for i in range(self.shape[0]):
+                self[i] /= np.sqrt(p[i])
+
     def _snr_linear(self, snr, tx, rx):
         """Per-mode linear SNR: estimated on the aligned rows when ``snr`` is None, else ``snr`` in dB (one value or one per mode)."""
         if snr is None:
