@@ -879,6 +879,38 @@ int qh_blind_evm_c128_dev(const void *E, int nrows, int64_t L, const double *sta
 int qh_qpsk_blind_c64_dev(const void *E, int nrows, int64_t L, int64_t block, double *out);
 int qh_qpsk_blind_c128_dev(const void *E, int nrows, int64_t L, int64_t block, double *out);
 
+/* ---- time-domain hybrid QAM (csrc/hybrid.hip; qampy/signals.py:1182-1427 TDHQAMSymbols, finished: DESIGN.md 3.21).  Two formats share a frame of
+ * fM symbols, 2 <= fM <= 256: position n of a row carries format 1 when n % fM < fM1 (1 <= fM1 < fM), else format 2, whose symbols are stored
+ * divided by sqrt(powratio) (powratio > 0, finite).  Device pointers, rows of whole frames (L % fM == 0, fM <= L < 2^31), 1 <= nmodes <= 65535,
+ * enqueued on the current stream, nothing read back, no atomics: a repeated call is bit-identical.  Partials live in the calling thread's scratch.
+ * Assemble: out (nmodes, nframes fM) from part1 (nmodes, nframes fM1) and part2 (nmodes, nframes fM2), part2 times 1 / sqrt(powratio) (the product
+ * in double, rounded once); lab1, lab2 (int32, the parts' shapes) and idx_out (nmodes, nframes fM) int32 all given or all NULL: the labels laid
+ * out like the symbols.  out must not be one of the parts. */
+int qh_tdh_assemble_c64_dev(const void *part1, const void *part2, const int32_t *lab1, const int32_t *lab2, int nmodes, int64_t nframes, int fM, int fM1,
+                            double powratio, void *out, int32_t *idx_out);
+int qh_tdh_assemble_c128_dev(const void *part1, const void *part2, const int32_t *lab1, const int32_t *lab2, int nmodes, int64_t nframes, int fM, int fM1,
+                             double powratio, void *out, int32_t *idx_out);
+/* sums (nmodes, fM) float64: the sum of |E[row][n]| over n = r (mod fM), terms and sums in double, in a fixed order. */
+int qh_tdh_class_sums_c64_dev(const void *E, int nmodes, int64_t L, int fM, double *sums);
+int qh_tdh_class_sums_c128_dev(const void *E, int nmodes, int64_t L, int fM, double *sums);
+/* shift (nmodes) int32 from the class sums: with H the residues of the higher-order format - [0, fM1) when high_first, else [fM1, fM) - the first j
+ * in [0, fM) at which the sum over r in H of sums[row][(r + j) % fM] is strictly largest. */
+int qh_tdh_align_dev(const double *sums, int nmodes, int fM, int fM1, int high_first, int32_t *shift);
+/* part1[k] = E[(idx1[k] + shift) % L], part2[k] = E[(idx2[k] + shift) % L] sqrt(powratio), idx1 / idx2 the positions of the two formats in a row;
+ * shift: shift_dev[row] (int32, device) when shift_dev is given, else shift_host for every row.  The parts must not be E. */
+int qh_tdh_split_c64_dev(const void *E, int nmodes, int64_t L, int fM, int fM1, double powratio, const int32_t *shift_dev, int shift_host, void *part1,
+                         void *part2);
+int qh_tdh_split_c128_dev(const void *E, int nmodes, int64_t L, int fM, int fM1, double powratio, const int32_t *shift_dev, int shift_host, void *part1,
+                          void *part2);
+/* sums (nmodes, 8) float64 = (symbol errors, bit errors, symbols compared, sum |r - s_label|^2) of format 1, then of format 2: r = E[(n + shift) % L],
+ * times sqrt(powratio) in format 2, decided against the alphabet of position n (the nearest point by squared distance in E's precision, the first
+ * on a tie) and compared with idx_tx[row][n], the label into that alphabet (nmodes, L) int32; bit errors are popc(decision ^ label).  A label
+ * outside [0, M) is skipped.  alphabet1 (M1) and alphabet2 (M2) of E's type, 1 <= M <= 1024.  shift as in the split. */
+int qh_tdh_metrics_c64_dev(const void *E, int nmodes, int64_t L, int fM, int fM1, double powratio, const int32_t *shift_dev, int shift_host,
+                           const int32_t *idx_tx, const void *alphabet1, int M1, const void *alphabet2, int M2, double *sums);
+int qh_tdh_metrics_c128_dev(const void *E, int nmodes, int64_t L, int fM, int fM1, double powratio, const int32_t *shift_dev, int shift_host,
+                            const int32_t *idx_tx, const void *alphabet1, int M1, const void *alphabet2, int M2, double *sums);
+
 #ifdef __cplusplus
 }
 #endif

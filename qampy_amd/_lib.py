@@ -46,6 +46,8 @@ _PILOT_PHASE = [_vp, _i, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64]    
 _PATTERN = [_vp, _i, _i64, _vp, _i, _vp, _i, _vp, _i, _i]                                   # E, nmodes, L, lev_I, MI, lev_Q, MQ, alphabet, M, mem_len
 _LUT_ACC = [_vp, _vp, _i, _i64, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp]                     # tx, rx, nmodes, L, idx_I, idx_Q, mask, mask_rows, N, ea, nI, nQ
 _DAC_TABLE = [_i64, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _i, _vp]           # sim_len, fb, fs, beta, noise, sos (host), nsec, p_f
+_TDH_ASSEMBLE = [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, C.c_double, _vp, _vp]                # part1, part2, lab1, lab2, nmodes, nframes, fM, fM1, powratio, out, idx_out
+_TDH_ROWS = [_vp, _i, _i64, _i, _i, C.c_double, _vp, _i]                                    # E, nmodes, L, fM, fM1, powratio, shift_dev, shift_host
 
 
 def _train_sig(mu_ptr, dev=False):
@@ -200,6 +202,11 @@ SIGNATURES = {
     "qh_blind_evm_c64_dev": [_vp, _i, _i64, _vp, _vp, _i, _vp, _vp, _vp],                                                                       # E, nrows, L, stats, alphabet, M, known, stats_known, evm_sum
     "qh_blind_evm_c128_dev": [_vp, _i, _i64, _vp, _vp, _i, _vp, _vp, _vp],
     "qh_qpsk_blind_c64_dev": [_vp, _i, _i64, _i64, _vp], "qh_qpsk_blind_c128_dev": [_vp, _i, _i64, _i64, _vp],                                  # E, nrows, L, block, out
+    "qh_tdh_assemble_c64_dev": _TDH_ASSEMBLE, "qh_tdh_assemble_c128_dev": _TDH_ASSEMBLE,
+    "qh_tdh_class_sums_c64_dev": [_vp, _i, _i64, _i, _vp], "qh_tdh_class_sums_c128_dev": [_vp, _i, _i64, _i, _vp],                              # E, nmodes, L, fM, sums
+    "qh_tdh_align_dev": [_vp, _i, _i, _i, _i, _vp],                                                                                             # sums, nmodes, fM, fM1, high_first, shift
+    "qh_tdh_split_c64_dev": _TDH_ROWS + [_vp, _vp], "qh_tdh_split_c128_dev": _TDH_ROWS + [_vp, _vp],                                            # ..., part1, part2
+    "qh_tdh_metrics_c64_dev": _TDH_ROWS + [_vp, _vp, _i, _vp, _i, _vp], "qh_tdh_metrics_c128_dev": _TDH_ROWS + [_vp, _vp, _i, _vp, _i, _vp],    # ..., idx_tx, alphabet1, M1, alphabet2, M2, sums
 }
 
 PIT_MAXPASS, PIT_MAXCHUNK = 24, 32

@@ -42,7 +42,7 @@ double gram_budget_gb();         // scratch the Gram tables of one call may take
 int pit_timing_mode();            // which relaxation passes of a tier-b sweep get HIP events: 0 none, 1 pass 1 (default), 2 all (qh_set_pit_timing)
 int default_tier();               // 0: tier a (exact), 1: tier b - what the drop-in host-array trainers run (qh_set_default_tier)
 double default_tier_tol();        // tolerance of the default tier b (qh_set_default_tier)
-constexpr int SCRATCH_SLOTS = 29;
+constexpr int SCRATCH_SLOTS = 30;
 constexpr int SCRATCH_TWOSTAGE = 16;             // tables of the two-stage phase search (bps.hip)
 constexpr int SCRATCH_FOE = 17;                  // tables, spectrum and intermediates of the frequency-offset estimate (foe.hip)
 constexpr int SCRATCH_IMPAIR = 18;               // tile totals, power partials and sigma of the point-wise impairment pass (impair.hip)
@@ -56,6 +56,7 @@ constexpr int SCRATCH_PEAK = 25;                 // one partial per tile of the 
 constexpr int SCRATCH_PILOT = 26;                // pilot phases, knots and wrap counts of the pilot-aided estimates (pilot.hip)
 constexpr int SCRATCH_PRECOMP = 27;              // tile maxima and scales of the pattern table, tile sums of the DAC pre-emphasis (precomp.hip)
 constexpr int SCRATCH_BLIND = 28;                // workgroup partials of the blind moments, distance sums and QPSK sums (blind.hip)
+constexpr int SCRATCH_HYBRID = 29;               // tile sums of the frame classes, workgroup partials of the hybrid metrics (hybrid.hip)
 int scratch(int slot, size_t bytes, void **p);   // grow-only device scratch, slots 0..SCRATCH_SLOTS - 1
 unsigned scratch_epoch();        // changes whenever the calling thread's scratch slots are released (contents cached in a slot are gone)
 

@@ -10,8 +10,9 @@ exposing the same attributes - including a real ``qampy.signals.SignalQAMGrayCod
 The source of a signal is here too, with the reference's call surface (qampy/signals.py:53-137, :611-905): :class:`RandomBits`,
 :class:`PRBSBits` (the generator runs on the device, csrc/source.hip) and :class:`SignalQAMGrayCoded` - bits to Gray-mapped symbols on the
 device, ``from_bit_array``, ``from_symbol_array``, ``modulate``, ``bits`` - and :class:`SignalWithPilots` (:1430-1645), which lays pilots and
-payload out as frames on the device (csrc/pilot.hip).  ``QPSKfromBERT``, ``TDHQAMSymbols``, ``SignalPSKGrayCoded`` and ``SymbolOnlySignal`` stay out
-of scope.
+payload out as frames on the device (csrc/pilot.hip) - :class:`SignalPSKGrayCoded`, :class:`ResampledQAM` and :class:`TDHQAMSymbols` (:932-947,
+:1142-1427), time-domain hybrid QAM, whose split and metrics the reference left unfinished and csrc/hybrid.hip runs on the device.
+``QPSKfromBERT`` and ``SymbolOnlySignal`` stay out of scope.
 """
 import warnings
 
@@ -338,9 +339,15 @@ class SignalQAMGrayCoded(SignalQAM):
 
     def __new__(cls, M, N, nmodes=1, fb=1, bitclass=RandomBits, dtype=np.complex128, **kwargs):
         _check_dtype(dtype)
-        coded = _gray_alphabet(M, np.sqrt(theory.cal_scaling_factor_qam(M)), dtype)
+        coded = cls._alphabet(M, dtype)
         bits = bitclass(int(N * np.log2(M)), nmodes=nmodes, **kwargs)
         return cls._wrap(cls._modulate(bits, coded), M, fb, coded, bits)
+
+    @classmethod
+    def _alphabet(cls, M, dtype, power=None):
+        """``coded_symbols`` of the class: the M-QAM constellation of mean power ``power`` (None: 1) in Gray-label order (``_generate_mapping``)."""
+        scale = np.sqrt(theory.cal_scaling_factor_qam(M))
+        return _gray_alphabet(M, scale if power is None else scale / np.sqrt(power), dtype)
 
     @classmethod
     def _wrap(cls, data, M, fb, coded, bits):
@@ -369,6 +376,8 @@ class SignalQAMGrayCoded(SignalQAM):
         nsym = data.shape[1] // nb
         if nsym < 1 or data.shape[0] < 1:
             return np.empty((data.shape[0], nsym), dtype=coded_symbols.dtype)
+        if nb == 1:                          # two points (BPSK): a bit is its own label, and the device mapper starts at two bits per symbol
+            return coded_symbols[(data != 0).astype(np.intp)]
         bits = _lib.DeviceArray.from_host(np.ascontiguousarray(data[:, :nsym * nb] != 0).view(np.uint8))
         out = _lib.DeviceArray((data.shape[0], nsym), coded_symbols.dtype)
         hip_dsp.modulate_bits_dev(bits, _lib.DeviceArray.from_host(np.ascontiguousarray(coded_symbols)), out)
@@ -392,7 +401,7 @@ class SignalQAMGrayCoded(SignalQAM):
         if arr.shape[1] % nb > 0:
             warnings.warn("Length of bits not divisible by log2(M) truncating")
             arr = arr[:, :arr.shape[1] // nb * nb]
-        coded = _gray_alphabet(M, np.sqrt(theory.cal_scaling_factor_qam(M)), dtype)
+        coded = cls._alphabet(M, dtype)
         return cls._wrap(cls._modulate(arr, coded), M, fb, coded, arr)
 
     @classmethod
@@ -415,16 +424,292 @@ class SignalQAMGrayCoded(SignalQAM):
         P = (abs(np.unique(symbs)) ** 2).mean()
         if not np.isclose(P, 1):
             warnings.warn("Power of symbols is not normalized to 1, this might cause issues later")
-        scale = np.sqrt(theory.cal_scaling_factor_qam(M)) / np.sqrt((abs(np.unique(symbs)) ** 2).mean())
-        coded = _gray_alphabet(M, scale, dtype)
+        coded = cls._alphabet(M, dtype, power=(abs(np.unique(symbs)) ** 2).mean())
         nb = int(np.log2(M))
         E = _lib.DeviceArray.from_host(np.ascontiguousarray(symbs, dtype=dtype))
         alphabet = _lib.DeviceArray.from_host(np.ascontiguousarray(coded))
         det, labels = _lib.DeviceArray(E.shape, dtype), _lib.DeviceArray(E.shape, np.int32)
         bits = _lib.DeviceArray((E.shape[0], E.shape[1] * nb), np.uint8)
         hk.make_decision_dev(E, alphabet, det, None, labels)
+        if nb == 1:                          # (a label of two points is its bit)
+            return cls._wrap(det.to_host(), M, fb, coded, labels.to_host().astype(bool))
         hip_dsp.labels_to_bits_dev(labels, nb, bits)
         return cls._wrap(det.to_host(), M, fb, coded, bits.to_host().view(bool))
+
+
+class SignalPSKGrayCoded(SignalQAMGrayCoded):
+    """
+    ``SignalPSKGrayCoded(M, N, nmodes=1, fb=1, bitclass=RandomBits, dtype=np.complex128, **kwargs)``: Gray-coded M-PSK symbols
+    (qampy/signals.py:932-947).  ``coded_symbols[g]`` is the point of ``theory.cal_symbols_psk(M)`` whose binary-reflected Gray label is ``g``, so
+    neighbours on the circle differ in one bit; bits map to labels MSB first, as in the QAM class, on the device.  Decisions and the ``cal_*``
+    metrics run through the same nearest-point kernels: they take any alphabet.
+    """
+
+    @classmethod
+    def _alphabet(cls, M, dtype, power=None):
+        """The unit circle's points in Gray-label order; like the reference's mapping it ignores the power asked for."""
+        points = theory.cal_symbols_psk(M).astype(dtype)
+        n = np.arange(M)
+        place = np.zeros(M, dtype=np.intp)
+        place[n ^ (n >> 1)] = n
+        return points[place]
+
+
+class ResampledQAM(SignalQAMGrayCoded):
+    """
+    ``ResampledQAM(M, N, fb=1, fs=1, resamplekwargs={"beta": 0.1}, **kwargs)``: a :class:`SignalQAMGrayCoded` made at the symbol rate ``fb`` and
+    resampled to ``fs`` with a root-raised-cosine filter (qampy/signals.py:1142-1178) - :meth:`SignalQAM.resample` with ``resamplekwargs`` on the
+    GPU.  ``**kwargs`` go to :class:`SignalQAMGrayCoded`.  The default ``resamplekwargs`` leave the filter length to ``rrcos_resample``; its
+    whole-row spectral form (``taps=None``) is not implemented.
+    """
+
+    def __new__(cls, M, N, fb=1, fs=1, resamplekwargs={"beta": 0.1}, **kwargs):
+        return super().__new__(cls, M, N, fb=fb, **kwargs).resample(fs, **resamplekwargs)
+
+    @classmethod
+    def from_symbol_array(cls, array, fs, **kwargs):
+        """``array`` (a signal object) resampled to ``fs``; ``**kwargs`` are those of ``rrcos_resample``.  The result keeps ``array``'s class."""
+        return array.resample(fs, **kwargs)
+
+
+# ------------------------------------------------------------------------------------------------ time-domain hybrid QAM
+_TATTRS = ("_symbols_M1", "_symbols_M2", "_fr", "_powratio", "_power_method", "_fb", "_fs")
+
+
+def _nearest(rows, alphabet):
+    """Labels of the nearest point of ``alphabet`` per sample of the host rows, by squared distance in double, the first on a tie."""
+    rows = np.atleast_2d(np.asarray(rows)).astype(np.complex128)
+    a = np.asarray(alphabet).astype(np.complex128)
+    out = np.empty(rows.shape, dtype=np.int32)
+    for m, row in enumerate(rows):
+        for lo in range(0, row.size, 1 << 14):
+            d = row[lo:lo + (1 << 14), None] - a[None, :]
+            out[m, lo:lo + (1 << 14)] = np.argmin(d.real ** 2 + d.imag ** 2, axis=1)
+    return out
+
+
+class TDHQAMSymbols(np.ndarray):
+    """
+    ``TDHQAMSymbols(M, N, fr=0.5, power_method="dist", M1class=SignalQAMGrayCoded, M2class=SignalQAMGrayCoded, **kwargs)``: time-domain hybrid
+    QAM ``(nmodes, N)`` at one sample per symbol - two formats ``M = (M1, M2)`` interleaved in a fixed frame (qampy/signals.py:1182-1427).  With
+    ``f_M, f_M1, f_M2`` of ``Fraction(fr).limit_denominator()``, position ``n`` carries format 1 when ``n % f_M < f_M1``, else format 2, whose
+    symbols are divided by ``sqrt(powratio)`` so that both alphabets keep the same spacing (``power_method="dist"``).  ``N`` is cut to whole
+    frames with a warning; ``**kwargs`` go to both part classes, as in the reference (two PRBS sources then start from the same bits).
+
+    ``symbols_M1`` and ``symbols_M2`` are the parts as signal objects (``symbols_M2`` holds the scaled values, as the reference's does; its own
+    ``symbols`` the unit-power ones).  The array values are the reference's, bit for bit.
+
+    The reference stops there: its split and every ``cal_*`` raise.  Here :meth:`divide` aligns a received signal to the frame and takes it
+    apart, and :meth:`cal_ser`, :meth:`cal_ber`, :meth:`cal_evm` and :meth:`cal_gmi` measure it per format and combined - ``method="pyt"`` in
+    numpy, ``"hip"`` through csrc/hybrid.hip (DESIGN.md 3.21 has the semantics).
+    """
+
+    def __new__(cls, M, N, fr=0.5, power_method="dist", M1class=SignalQAMGrayCoded, M2class=SignalQAMGrayCoded, **kwargs):
+        fM, fM1, fM2 = cls._cal_fractions(fr)
+        frames = int(N) // fM
+        if N % fM > 0:
+            warnings.warn("length of overall pattern not divisable by number of frames, truncating to %d symbols" % (fM * frames))
+        return cls._interleave(M1class(M[0], frames * fM1, **kwargs), M2class(M[1], frames * fM2, **kwargs), fr, power_method)
+
+    @classmethod
+    def _interleave(cls, syms1, syms2, fr, power_method):
+        """The hybrid signal of two whole-frame parts; ``syms2`` is divided by ``sqrt(powratio)`` in place."""
+        fM, fM1, fM2 = cls._cal_fractions(fr)
+        scale = cls.calculate_power_ratio(syms1.coded_symbols, syms2.coded_symbols, power_method)
+        syms2 /= np.sqrt(scale)
+        N = syms1.shape[1] + syms2.shape[1]
+        out = np.zeros((syms1.shape[0], N), dtype=syms1.dtype)
+        _, idx1, idx2 = cls._cal_symbol_idx(N, fM, fM1)
+        out[:, idx1] = syms1
+        out[:, idx2] = syms2
+        obj = out.view(cls)
+        obj._symbols_M1, obj._symbols_M2, obj._powratio, obj._fr, obj._power_method = syms1, syms2, scale, fr, power_method
+        obj._fb = obj._fs = syms1.fb
+        return obj
+
+    def __array_finalize__(self, obj):
+        if obj is None:
+            return
+        for a in _TATTRS:
+            setattr(self, a, getattr(obj, a, None))
+
+    @staticmethod
+    def _cal_fractions(fr):
+        from .core import hip_dsp
+        return hip_dsp.tdh_geometry(fr)
+
+    @staticmethod
+    def _cal_symbol_idx(N, f_M, f_M1):
+        idx = np.arange(N)
+        return idx, idx % f_M < f_M1, idx % f_M >= f_M1
+
+    @staticmethod
+    def calculate_power_ratio(M1symbols, M2symbols, method="dist"):
+        """Power ratio of two alphabets at equal spacing (``hip_dsp.tdh_power_ratio``); only ``"dist"`` exists."""
+        from .core import hip_dsp
+        return hip_dsp.tdh_power_ratio(M1symbols, M2symbols, method)
+
+    powratio = property(lambda self: self._powratio)
+    f_M = property(lambda self: self._cal_fractions(self.fr)[0])
+    f_M1 = property(lambda self: self._cal_fractions(self.fr)[1])
+    f_M2 = property(lambda self: self._cal_fractions(self.fr)[2])
+    M = property(lambda self: (self._symbols_M1.M, self._symbols_M2.M))
+    symbols_M1 = property(lambda self: self._symbols_M1)
+    symbols_M2 = property(lambda self: self._symbols_M2)
+    fr = property(lambda self: self._fr)
+    fb = property(lambda self: self._fb)
+    fs = property(lambda self: self._fs)
+    os = property(lambda self: int(self.fs / self.fb))
+
+    @classmethod
+    def from_symbol_arrays(cls, syms_M1, syms_M2, fr, power_method="dist"):
+        """A hybrid signal from two signal objects of one dtype and one number of modes (qampy/signals.py:1318-1366).  When the parts do not
+        fill whole frames at the ratio ``fr`` a warning is given and each is cut to ``nframes * f_M1`` / ``nframes * f_M2`` symbols (the
+        reference then fails on a shape mismatch).  The parts are copied: ``syms_M2`` itself is left unscaled."""
+        assert syms_M1.ndim == 2 and syms_M2.ndim == 2, "input needs to have two dimensions"
+        assert syms_M1.dtype == syms_M2.dtype, "both input symbol arrays need to have the same dtype"
+        assert syms_M1.shape[0] == syms_M2.shape[0], "Number of modes must be the same"
+        fM, fM1, fM2 = cls._cal_fractions(fr)
+        N1, N2 = syms_M1.shape[1], syms_M2.shape[1]
+        nframes = (N1 + N2) // fM
+        if nframes * fM1 > N1 or nframes * fM2 > N2:
+            warnings.warn("Need to truncate input arrays as ratio is not possible otherwise")
+            nframes = min(N1 // fM1, N2 // fM2)
+        return cls._interleave(cls._cut(syms_M1, nframes * fM1), cls._cut(syms_M2, nframes * fM2), fr, power_method)
+
+    @staticmethod
+    def _cut(sig, n):
+        """A copy of the first ``n`` symbols of a part with its metadata (its ``symbols`` cut alike)."""
+        out = sig.recreate_from_np_array(np.array(sig)[:, :n])
+        if getattr(sig, "_symbols", None) is not None:
+            out._symbols = np.array(sig._symbols)[:, :n]
+        return out
+
+    def recreate_from_np_array(self, arr, **kwargs):
+        """Re-wrap a plain array with this signal's class and attributes."""
+        out = np.atleast_2d(np.asarray(arr)).view(type(self))
+        for a in _TATTRS:
+            setattr(out, a, getattr(self, a))
+        if "fb" in kwargs and "fs" not in kwargs:
+            kwargs["fs"] = self.os * kwargs["fb"]
+        for k, v in kwargs.items():
+            setattr(out, "_" + k if "_" + k in _TATTRS else k, v)
+        return out
+
+    def _demodulate(self):
+        raise NotImplementedError("Use demodulation of subclasses")
+
+    def _modulate(self):
+        raise NotImplementedError("Use modulation of subclasses")
+
+    # ---- what the reference left unfinished (its _divide_signal_frame and every cal_* raise): DESIGN.md 3.21
+    def _received(self, signal):
+        rx = np.atleast_2d(np.asarray(self if signal is None else signal))
+        if rx.shape[1] % self.f_M:
+            raise ValueError("a row of %d symbols does not hold whole frames of %d" % (rx.shape[1], self.f_M))
+        return rx
+
+    def divide(self, signal=None, method="pyt", return_shifts=False):
+        """``(part1, part2)`` of ``signal`` (default: this signal), as objects of the parts' classes carrying the transmitted parts as
+        ``symbols``: every row is aligned to the frame - the cyclic shift at which the positions of the higher-order format have the largest
+        mean magnitude - and split, part 2 times ``sqrt(powratio)``, back on its unit-power alphabet.  The split aligns the format, not the
+        sequence.  ``method="hip"``: on the device (``hip_dsp.tdh_divide``); ``return_shifts``: also the shift per row."""
+        from .core import hip_dsp
+        p1, p2, shifts = hip_dsp.tdh_divide(self._received(signal), self.fr, self.M, self.powratio, method=method)
+        parts = (self._symbols_M1.recreate_from_np_array(p1), self._symbols_M2.recreate_from_np_array(p2))
+        return parts + (shifts,) if return_shifts else parts
+
+    def _tx_labels(self, n1, n2):
+        """Transmitted labels of the two parts, repeated or cut to ``n1`` / ``n2`` symbols."""
+        out = []
+        for part, n in ((self._symbols_M1, n1), (self._symbols_M2, n2)):
+            lab = _nearest(part.symbols, part.coded_symbols)
+            out.append(np.ascontiguousarray(np.tile(lab, (1, -(-n // lab.shape[1])))[:, :n]))
+        return out
+
+    def _hard_sums(self, signal_rx, synced, method):
+        """The eight sums per mode, ``(nmodes, 2, 4)``: symbol errors, bit errors, compared, squared error of either format."""
+        from . import _lib
+        from .core import ber_functions as bf, hip_dsp
+        if method not in ("pyt", "hip"):
+            raise ValueError("method must be 'pyt' (host) or 'hip' (device), not %r" % (method,))
+        rx = self._received(signal_rx)
+        nm, L = rx.shape
+        fM, fM1, fM2 = self._cal_fractions(self.fr)
+        coded = [np.asarray(self._symbols_M1.coded_symbols), np.asarray(self._symbols_M2.coded_symbols)]
+        if synced and method == "hip":
+            ct = _lib.suffix(rx.dtype)[2]
+            lab1, lab2 = self._tx_labels(L // fM * fM1, L // fM * fM2)
+            idx = np.empty((nm, L), dtype=np.int32)
+            _, i1, i2 = self._cal_symbol_idx(L, fM, fM1)
+            idx[:, i1], idx[:, i2] = lab1[:nm], lab2[:nm]
+            D = _lib.DeviceArray
+            E = D.from_host(np.ascontiguousarray(rx, dtype=ct))
+            shift = hip_dsp.tdh_align_dev(hip_dsp.tdh_class_sums_dev(E, fM), fM1, self.M)
+            sums = hip_dsp.tdh_metrics_dev(E, D.from_host(idx), fM, fM1, self.powratio, D.from_host(np.ascontiguousarray(coded[0], dtype=ct)),
+                                           D.from_host(np.ascontiguousarray(coded[1], dtype=ct)), shift)
+            return sums.to_host().reshape(nm, 2, 4)
+        parts = hip_dsp.tdh_divide(rx, self.fr, self.M, self.powratio, method=method)[:2]
+        sums = np.zeros((nm, 2, 4))
+        for k, (part, tx_part) in enumerate(zip(parts, (self._symbols_M1, self._symbols_M2))):
+            a = coded[k].astype(np.complex128)
+            tx_all = np.atleast_2d(np.asarray(tx_part.symbols))
+            for m in range(nm):
+                r = part[m]
+                if synced:
+                    t = np.tile(tx_all[m], -(-r.size // tx_all.shape[1]))[:r.size]
+                else:
+                    (t, r), _ = bf.sync_and_adjust(tx_all[m], r, method=method)
+                lt, lr = _nearest(t, a)[0], _nearest(r, a)[0]
+                d = r.astype(np.complex128) - a[lt]
+                bit_errors = int(np.unpackbits((lt ^ lr).astype(">u4").view(np.uint8)).sum())
+                sums[m, k] = (np.count_nonzero(lt != lr), bit_errors, r.size, np.sum(d.real ** 2 + d.imag ** 2))
+        return sums
+
+    def _rates(self, key, signal_rx, synced, method):
+        from .core import hip_dsp
+        return hip_dsp.tdh_rates(self._hard_sums(signal_rx, synced, method), self.M)[key]
+
+    def make_decision(self, signal=None, method="pyt"):
+        """The decisions of ``signal`` (default: this signal) in the hybrid layout: the rows aligned and split (:meth:`divide`), every part
+        decided on its own alphabet, and the decisions interleaved again, format 2 over ``sqrt(powratio)``."""
+        p1, p2 = self.divide(signal, method=method)
+        d1 = np.asarray(p1.coded_symbols)[_nearest(p1, p1.coded_symbols)].astype(p1.dtype)
+        d2 = (np.asarray(p2.coded_symbols)[_nearest(p2, p2.coded_symbols)] * (1 / np.sqrt(self.powratio))).astype(p2.dtype)
+        out = np.empty((d1.shape[0], d1.shape[1] + d2.shape[1]), dtype=d1.dtype)
+        _, i1, i2 = self._cal_symbol_idx(out.shape[1], self.f_M, self.f_M1)
+        out[:, i1], out[:, i2] = d1, d2
+        return out
+
+    def cal_ser(self, signal_rx=None, synced=True, method="pyt"):
+        """Symbol error rate ``(per format (nmodes, 2), combined (nmodes,))`` of ``signal_rx`` (default: this signal) against the transmitted
+        parts.  The rows are aligned to the frame first; ``synced=False``: every part is then synchronised to its transmitted part
+        (``ber_functions.sync_and_adjust``).  ``method="hip"``: alignment and the fused metrics pass on the device, eight sums come back;
+        with ``synced=False`` the split and the synchronisation run on the device and the synchronised parts are counted on the host."""
+        return self._rates("ser", signal_rx, synced, method)
+
+    def cal_ber(self, signal_rx=None, synced=True, method="pyt"):
+        """Bit error rate, as :meth:`cal_ser`; the combined rate is weighted by bits, ``(b1 + b2) / (n1 log2 M1 + n2 log2 M2)``."""
+        return self._rates("ber", signal_rx, synced, method)
+
+    def cal_evm(self, signal_rx=None, synced=True, method="pyt"):
+        """RMS error vector magnitude against the transmitted symbols, as :meth:`cal_ser`; format 2 after its rescale to unit power."""
+        return self._rates("evm", signal_rx, synced, method)
+
+    def cal_gmi(self, signal_rx=None, synced=True, snr=None, method="pyt"):
+        """Generalised mutual information ``(per format (nmodes, 2), combined (nmodes,))`` in bits per symbol: the signal is split and every
+        part goes through its class's ``cal_gmi`` (one fused device pass per mode); the combined value weights the formats by their share of
+        the frame.  ``snr``: Es / N0 of the hybrid signal in dB, turned into each format's own - format 1 has the power ``1 / mix`` of the mean,
+        format 2 after its rescale ``1 / (powratio mix)``, ``mix = f_M1 / f_M + f_M2 / (f_M powratio)`` - or None: estimated per part."""
+        p1, p2 = self.divide(signal_rx, method=method)
+        fM, fM1, fM2 = self._cal_fractions(self.fr)
+        own = (None, None)
+        if snr is not None:
+            powratio = float(self.powratio)               # (a complex64 signal carries it in single precision)
+            mix = fM1 / fM + fM2 / fM / powratio
+            own = (np.asarray(snr) - 10 * np.log10(mix), np.asarray(snr) - 10 * np.log10(mix * powratio))
+        gmi = np.stack([p.cal_gmi(synced=synced, snr=s)[0] for p, s in zip((p1, p2), own)], axis=1)
+        return gmi, (gmi[:, 0] * fM1 + gmi[:, 1] * fM2) / fM
 
 
 # ------------------------------------------------------------------------------------------------ pilot frames

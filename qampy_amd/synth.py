@@ -248,6 +248,35 @@ def make_pilot_frames_dev(M, frame_len, seq_len, ins_rat, nframes=1, nmodes=2, M
                 seq_len=int(seq_len), ins_rat=int(ins_rat or 0), nframes=nframes, NP=NP, ND=ND, M=M, Mpilots=Mpilots)
 
 
+def make_tdh_symbols_dev(M, nsym, fr, nmodes=2, order=(15, 23), seed=(None, None), kind="ext", dtype=np.complex64):
+    """
+    Time-domain hybrid QAM symbols made in HBM: what ``TDHQAMSymbols(M, nsym, fr, nmodes=nmodes, dtype=dtype, bitclass=PRBSBits, order=order,
+    seed=seed)`` holds.  ``M = (M1, M2)``; the two parts are two PRBS sources (:func:`make_symbols_dev`; both start from the seed, as in the
+    reference), interleaved by one launch of ``hip_dsp.tdh_assemble_dev`` with part 2 over ``sqrt(powratio)``.  ``nsym`` is cut to whole frames.
+    Nothing is read back.
+
+    Returns a dict of :class:`qampy_amd._lib.DeviceArray`: ``symbols (nmodes, nframes * f_M)``, ``idx_tx`` (same shape, int32: the label of the
+    format at every position, ready for ``hip_dsp.tdh_metrics_dev``), ``part1``, ``part2`` (unit-power parts), ``idx_tx1``, ``idx_tx2``,
+    ``alphabet1``, ``alphabet2``; and the geometry: ``f_M``, ``f_M1``, ``f_M2``, ``nframes``, ``powratio``, ``M``, ``fr``, ``alphabet1_host``,
+    ``alphabet2_host``.  A sweep is then ``impair_pointwise_dev(snr=...)`` -> ``tdh_class_sums_dev`` / ``tdh_align_dev`` -> ``tdh_metrics_dev``.
+    """
+    from ._lib import DeviceArray
+    from .core import hip_dsp
+    fM, fM1, fM2 = hip_dsp.tdh_geometry(fr)
+    hip_dsp._tdh_frame("make_tdh_symbols_dev", fM, fM1)
+    nframes = int(nsym) // fM
+    if nframes < 1:
+        raise ValueError("make_tdh_symbols_dev: at least one frame of %d symbols" % fM)
+    p1 = make_symbols_dev(M[0], nframes * fM1, nmodes=nmodes, order=order, seed=seed, kind=kind, dtype=dtype)
+    p2 = make_symbols_dev(M[1], nframes * fM2, nmodes=nmodes, order=order, seed=seed, kind=kind, dtype=dtype)
+    powratio = float(hip_dsp.tdh_power_ratio(p1["alphabet_host"], p2["alphabet_host"]))
+    out, idx = DeviceArray((nmodes, nframes * fM), dtype), DeviceArray((nmodes, nframes * fM), np.int32)
+    hip_dsp.tdh_assemble_dev(p1["symbols"], p2["symbols"], fM, fM1, powratio, out, labels1=p1["idx_tx"], labels2=p2["idx_tx"], idx_out=idx)
+    return dict(symbols=out, idx_tx=idx, part1=p1["symbols"], part2=p2["symbols"], idx_tx1=p1["idx_tx"], idx_tx2=p2["idx_tx"], alphabet1=p1["alphabet"],
+                alphabet2=p2["alphabet"], alphabet1_host=p1["alphabet_host"], alphabet2_host=p2["alphabet_host"], f_M=fM, f_M1=fM1, f_M2=fM2,
+                nframes=nframes, powratio=powratio, M=tuple(M), fr=fr)
+
+
 # ------------------------------------------------------------------------------------------------- SER harness
 def normalise_and_center(E):
     """Per-mode mean removal and unit-power scaling (behaviour of qampy/helpers.py:46-58)."""
