@@ -119,6 +119,7 @@ int ensure_init()
 }
 
 // grow-only scratch slots so that the resident pipeline never allocates (and never synchronises) inside a timed region
+constexpr int SCRATCH_SLOTS = (int)Slot::COUNT;
 thread_local void *g_scratch[SCRATCH_SLOTS] = {nullptr};
 thread_local size_t g_scratch_n[SCRATCH_SLOTS] = {0};
 thread_local unsigned g_scratch_epoch = 0;
@@ -247,8 +248,9 @@ static void hpool_release()
     g_hpool_bytes = 0;
 }
 
-int scratch(int slot, size_t bytes, void **p)
+int scratch(Slot id, size_t bytes, void **p)
 {
+    const int slot = (int)id;
     if (bytes > g_scratch_n[slot]) {
         if (g_scratch[slot]) QH_HIP(hipFree(g_scratch[slot]));
         g_scratch[slot] = nullptr; g_scratch_n[slot] = 0;

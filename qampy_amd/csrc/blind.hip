@@ -17,7 +17,7 @@
 //
 // One reduction serves all of them and repeats bit for bit.  A segment (a row or a block) is cut into nb <= 256 slices of at least 1024 samples;
 // a workgroup of 256 threads sums one slice - every thread its samples in ascending order, wave_sum (DPP), the four wave totals in order - and
-// writes its partial sums with plain stores (scratch slot SCRATCH_BLIND).  A second launch, one wave per segment, adds the nb partials in a
+// writes its partial sums with plain stores (scratch slot Slot::BLIND).  A second launch, one wave per segment, adds the nb partials in a
 // fixed order and applies what follows the sum.  No atomics anywhere.
 //
 // What bounds them: the moments, the scaling and the QPSK sums read (and the scaling writes) every sample once and do a dozen operations on
@@ -233,7 +233,7 @@ template <typename R, typename T, int FIN> int blind_sums_dev(const char *what, 
     const int64_t nseg = nblocks * nrows;
     const BlSplit sp = bl_split(seglen);
     void *part = nullptr;
-    if ((rc = scratch(SCRATCH_BLIND, (size_t)nseg * sp.nb * T::C * sizeof(double), &part))) return rc;
+    if ((rc = scratch(Slot::BLIND, (size_t)nseg * sp.nb * T::C * sizeof(double), &part))) return rc;
     hipLaunchKernelGGL((blind_sums_kernel<R, T>), dim3((unsigned)nseg, sp.nb), dim3(BL_T), 0, g_stream, (const Cx<R> *)E, L, nblocks, seglen, sp.chunk,
                        (double *)part);
     QH_HIP(hipGetLastError());
@@ -275,7 +275,7 @@ template <typename R> int blind_evm_dev(const void *E, int nrows, int64_t L, con
     else QH_REQUIRE(alphabet && M >= 1 && M <= BL_M_MAX, "blind_evm: an alphabet of 1 .. 1024 points");
     const BlSplit sp = bl_split(L);
     void *part = nullptr;
-    if ((rc = scratch(SCRATCH_BLIND, (size_t)nrows * sp.nb * sizeof(double), &part))) return rc;
+    if ((rc = scratch(Slot::BLIND, (size_t)nrows * sp.nb * sizeof(double), &part))) return rc;
     hipLaunchKernelGGL((blind_evm_kernel<R>), dim3(sp.nb, nrows), dim3(BL_T), 0, g_stream, (const Cx<R> *)E, L, sp.chunk, stats, (const Cx<R> *)alphabet,
                        known ? 0 : M, (const Cx<R> *)known, stats_known, (double *)part);
     QH_HIP(hipGetLastError());

@@ -588,7 +588,7 @@ template <typename R> static int analyse_alphabet(const void *symbols, int M, vo
 {
     void *ring = nullptr;
     static thread_local unsigned desc_next = 0;
-    int rc = scratch(3, BPS_DESC_RING * sizeof(AlphabetDesc<double>), &ring);
+    int rc = scratch(Slot::BPS_ALPHABET, BPS_DESC_RING * sizeof(AlphabetDesc<double>), &ring);
     if (rc) return rc;
     *desc = (char *)ring + (size_t)(desc_next++ % BPS_DESC_RING) * sizeof(AlphabetDesc<double>);
     hipLaunchKernelGGL((analyse_alphabet_kernel<R>), dim3(1), dim3(64), 0, g_stream, (const Cx<R> *)symbols, M, (AlphabetDesc<R> *)*desc);
@@ -850,7 +850,7 @@ template <typename R> static int device_grid(int A, void **dang)
     void *ring = nullptr;
     static thread_local unsigned grid_next = 0;
     const size_t one = ((size_t)A * sizeof(R) + 255) & ~(size_t)255;
-    int rc = scratch(0, BPS_DESC_RING * one, &ring);
+    int rc = scratch(Slot::BPS_ANGLES, BPS_DESC_RING * one, &ring);
     if (rc) return rc;
     *dang = (char *)ring + (size_t)(grid_next++ % BPS_DESC_RING) * one;
     hipLaunchKernelGGL((linspace_kernel<R>), dim3((A + 63) / 64), dim3(64), 0, g_stream, (R *)*dang, A);
@@ -870,7 +870,7 @@ int bps_recover_dev(const void *E, int nm, int64_t L, const void *angles, int A,
     QH_REQUIRE(nparts >= 1 && part >= 0 && part < nparts, "bps_recover: bad part");
     const int64_t nchunk = (L + UW_CHUNK - 1) / UW_CHUNK;
     void *dang = const_cast<void *>(angles), *dchunk = nullptr;     // grow-only library scratch: no allocation / sync in the steady state
-    if ((rc = scratch(1, (size_t)nm * nchunk * sizeof(int), &dchunk))) return rc;
+    if ((rc = scratch(Slot::BPS_CHUNKS, (size_t)nm * nchunk * sizeof(int), &dchunk))) return rc;
     if (!dang && (rc = device_grid<R>(A, &dang))) return rc;       // (formed by every part)
     if ((rc = bps_dev<R>(E, L, dang, 1, A, symbols, M, N, idx, nm, part, nparts))) return rc;
     if (part != nparts - 1) return QH_OK;
@@ -1066,7 +1066,7 @@ int bps_twostage_recover_dev(const void *E, int nm, int64_t L, const void *angle
     void *ring = nullptr, *desc = nullptr, *dchunk = nullptr;
     static thread_local unsigned table_next = 0;
     const size_t n_fine = ((size_t)A * B * sizeof(R) + 255) & ~(size_t)255, n_rot = ((size_t)A * B * sizeof(Cx<R>) + 255) & ~(size_t)255;
-    if ((rc = scratch(SCRATCH_TWOSTAGE, BPS_DESC_RING * (n_fine + n_rot), &ring))) return rc;
+    if ((rc = scratch(Slot::TWOSTAGE, BPS_DESC_RING * (n_fine + n_rot), &ring))) return rc;
     R *fine = (R *)((char *)ring + (size_t)(table_next++ % BPS_DESC_RING) * (n_fine + n_rot));
     Cx<R> *rot = (Cx<R> *)((char *)fine + n_fine);
     hipLaunchKernelGGL((twostage_table_kernel<R>), dim3((unsigned)((A * B + 255) / 256)), dim3(256), 0, g_stream, (const R *)dang, A, B, o, fine, rot);
@@ -1098,7 +1098,7 @@ int bps_twostage_recover_dev(const void *E, int nm, int64_t L, const void *angle
     hipLaunchKernelGGL((bps_fine_kernel<R>), dim3((unsigned)((L + (int64_t)S * runs - 1) / ((int64_t)S * runs)), nm), dim3(64), lds, g_stream, f);
     // unwrap + de-rotation
     const int64_t nchunk = (L + UW_CHUNK - 1) / UW_CHUNK;
-    if ((rc = scratch(1, (size_t)nm * nchunk * sizeof(int), &dchunk))) return rc;
+    if ((rc = scratch(Slot::BPS_CHUNKS, (size_t)nm * nchunk * sizeof(int), &dchunk))) return rc;
     const UwFine<R> src{idx1, idx2, fine, L, 0, L, B};
     hipLaunchKernelGGL((unwrap_partial_kernel<R, UwFine<R>>), dim3((unsigned)nchunk, nm), dim3(UW_THREADS), 0, g_stream, src, (int *)dchunk, nchunk);
     hipLaunchKernelGGL(unwrap_scan_kernel, dim3(nm), dim3(1024), 0, g_stream, (int *)dchunk, nchunk);

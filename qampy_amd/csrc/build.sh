@@ -14,7 +14,7 @@ for f in $UNITS; do
     stale=0
     [ -f build/$f.o ] || stale=1
     # dependencies: the headers the compiler reported for this unit last time (build/<unit>.d, -MMD), else every header
-    deps="$f.hip common.h train_impl.h train_la.h train_bi.h train_pit.h train_seg.h fft_lds.h philox.h unwrap_scan.h prbs_core.h ../../include/qampy_hip.h"
+    deps="$f.hip common.h train_impl.h train_la.h train_bi.h train_pit.h train_seg.h fft_lds.h block_filter.h philox.h unwrap_scan.h prbs_core.h ../../include/qampy_hip.h"
     if [ -f build/$f.d ]; then
         deps="$f.hip $(tr -d '\\\n' < build/$f.d | sed 's/^[^:]*://' | tr ' ' '\n' | grep -v '^/opt/' | grep -v '^/usr/' | grep -v '^$' | sort -u | tr '\n' ' ')"
     fi

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <vector>
 #include "../../include/qampy_hip.h"
 
 namespace qh {
@@ -42,23 +43,81 @@ double gram_budget_gb();         // scratch the Gram tables of one call may take
 int pit_timing_mode();            // which relaxation passes of a tier-b sweep get HIP events: 0 none, 1 pass 1 (default), 2 all (qh_set_pit_timing)
 int default_tier();               // 0: tier a (exact), 1: tier b - what the drop-in host-array trainers run (qh_set_default_tier)
 double default_tier_tol();        // tolerance of the default tier b (qh_set_default_tier)
-constexpr int SCRATCH_SLOTS = 30;
-constexpr int SCRATCH_TWOSTAGE = 16;             // tables of the two-stage phase search (bps.hip)
-constexpr int SCRATCH_FOE = 17;                  // tables, spectrum and intermediates of the frequency-offset estimate (foe.hip)
-constexpr int SCRATCH_IMPAIR = 18;               // tile totals, power partials and sigma of the point-wise impairment pass (impair.hip)
-constexpr int SCRATCH_PMD = 19;                  // twiddles and H of the PMD filter (impair.hip)
-constexpr int SCRATCH_TXRESP = 20;               // tile extrema and the row extrema a call forms for itself (txresp.hip)
-constexpr int SCRATCH_SOS = 21;                  // tile end states / start states of the sections filter (txresp.hip)
-constexpr int SCRATCH_CPR = 22;                  // angles, wrap counts and partial moments of the feed-forward carrier recovery (cpr.hip)
-constexpr int SCRATCH_FFT = 23;                  // tables and work buffers of the whole-row transforms (fft.hip); tile totals of the IQ moments (iq.hip)
-constexpr int SCRATCH_SYNC = 24;                 // reversed conjugate of y and its transform, spectra of the rows of x (sync.hip)
-constexpr int SCRATCH_PEAK = 25;                 // one partial per tile of the correlation's peak search (sync.hip)
-constexpr int SCRATCH_PILOT = 26;                // pilot phases, knots and wrap counts of the pilot-aided estimates (pilot.hip)
-constexpr int SCRATCH_PRECOMP = 27;              // tile maxima and scales of the pattern table, tile sums of the DAC pre-emphasis (precomp.hip)
-constexpr int SCRATCH_BLIND = 28;                // workgroup partials of the blind moments, distance sums and QPSK sums (blind.hip)
-constexpr int SCRATCH_HYBRID = 29;               // tile sums of the frame classes, workgroup partials of the hybrid metrics (hybrid.hip)
-int scratch(int slot, size_t bytes, void **p);   // grow-only device scratch, slots 0..SCRATCH_SLOTS - 1
+// The scratch slots: grow-only device buffers of the calling host thread (not of a stream).  Every slot has ONE owning source file, so two units
+// never meet in a buffer whatever streams they run on; the one exception is GRAM (tests/test_scratch_slots.py holds the sources to this).
+enum class Slot : int {
+    BPS_ANGLES,          // ring of test-angle tables of the phase search (bps.hip)
+    BPS_CHUNKS,          // wrap counts per chunk of the phase search's unwrap, one- and two-stage (bps.hip)
+    BPS_ALPHABET,        // ring of alphabet descriptors of the phase search (bps.hip)
+    TWOSTAGE,            // ring of fine-angle and rotator tables of the two-stage phase search (bps.hip)
+    STEP_SIZES,          // the per-mode step sizes of an adaptive trainer call (train_impl.h)
+    GRAM,                // Gram tables of the lookahead (train_la.h) and block-iterative (train_bi.h) trainers: two forms of one trainer in one
+                         // translation unit, of which a call runs one - the only slot with two owners
+    BI_LEVELS,           // decision levels and their counts of the block-iterative trainer (train_bi.h)
+    PIT_WORK,            // tier b: segment taps, estimates and the selection of a sweep (train_pit.h)
+    PIT_CTRL,            // tier b: the control block PitCtrl that steers the relaxation passes (train_pit.h)
+    PIT_COV,             // tier b: covariance blocks of the basis (train_pit.h)
+    PIT_BASIS,           // tier b: the basis and the products of the correction (train_pit.h)
+    PIT_ROTATIONS,       // tier b: Jacobi rotations of the eigen-solver's sweeps (train_pit.h)
+    PIT_ACQ,             // tier b: acquisition head, and the adaptive form's per-segment state (train_pit.h)
+    PIT_MODEL,           // tier b: partials and fits of the coarse model (train_pit.h)
+    SER,                 // symbol indices and lag counts of the symbol-error count (ser.hip)
+    SYNTH,               // filter taps, PMD parameters and tile phases of the test-capture synthesis (synth.hip)
+    METRICS,             // workgroup partials and totals of metrics_dev (metrics.hip)
+    SNR_EST,             // per-symbol partials and totals of estimate_snr (metrics.hip)
+    AWGN_MC,             // workgroup partials and totals of the Monte-Carlo curves, awgn_mc_dev (metrics.hip)
+    CD_TABLE,            // twiddles and H of the dispersion filter (cd.hip)
+    RESAMPLE_TABLE,      // phase-major taps of the polyphase resampler (resample.hip)
+    ROW_MOMENTS,         // partial sums of the per-row moments (resample.hip)
+    FOE,                 // tables, spectrum and intermediates of the frequency-offset estimate (foe.hip)
+    IMPAIR,              // tile totals, power partials and sigma of the point-wise impairment pass (impair.hip)
+    PMD,                 // twiddles and H of the PMD filter (impair.hip)
+    TXRESP,              // tile extrema and the row extrema a call forms for itself (txresp.hip)
+    SOS,                 // tile end states / start states of the sections filter (txresp.hip)
+    CPR,                 // angles, wrap counts and partial moments of the feed-forward carrier recovery (cpr.hip)
+    FFT,                 // tables and work buffers of the whole-row transforms (fft.hip)
+    IQ,                  // tile totals of the IQ moments (iq.hip)
+    SYNC,                // reversed conjugate of y and its transform, spectra of the rows of x (sync.hip)
+    PEAK,                // one partial per tile of the correlation's peak search (sync.hip)
+    PILOT,               // pilot phases, knots and wrap counts of the pilot-aided estimates (pilot.hip)
+    PRECOMP,             // tile maxima and scales of the pattern table, tile sums of the DAC pre-emphasis (precomp.hip)
+    BLIND,               // workgroup partials of the blind moments, distance sums and QPSK sums (blind.hip)
+    HYBRID,              // tile sums of the frame classes, workgroup partials of the hybrid metrics (hybrid.hip)
+    COUNT
+};
+int scratch(Slot slot, size_t bytes, void **p);  // grow-only device scratch of the calling thread
 unsigned scratch_epoch();        // changes whenever the calling thread's scratch slots are released (contents cached in a slot are gone)
+
+// A table formed on the host and kept in a scratch slot until its key changes: one upload per key.  `key` is an opaque byte string the caller
+// fills with everything the contents depend on (sizes, sizeof(R), coefficients or taps); fill(host) writes the `bytes` of the table.  The table is
+// formed again when the key differs, the scratch was released (scratch_epoch) or the slot has grown; whatever still reads the old table (a launch
+// on another of this thread's streams) or the host copy (the last upload) finishes first.  One instance per slot and host thread.
+struct TableCache {
+    std::string key;
+    std::vector<char> host;          // kept alive for the asynchronous upload
+    void *dev = nullptr;
+    unsigned epoch = 0;
+    template <typename F> int get(Slot slot, const std::string &k, size_t bytes, F fill, const void **tab)
+    {
+        void *p = nullptr;
+        int rc;
+        if (dev && key == k && epoch == scratch_epoch()) {
+            if ((rc = scratch(slot, bytes, &p))) return rc;
+            if (p == dev) { *tab = p; return QH_OK; }
+        }
+        if (dev) QH_HIP(hipDeviceSynchronize());
+        dev = nullptr;
+        if ((rc = scratch(slot, bytes, &p))) return rc;
+        host.resize(bytes);
+        fill(host.data());
+        QH_HIP(hipMemcpyAsync(p, host.data(), bytes, hipMemcpyHostToDevice, g_stream));
+        key = k; dev = p; epoch = scratch_epoch();
+        *tab = p;
+        return QH_OK;
+    }
+};
+// appends the bytes of a value to a TableCache key
+template <typename T> inline void key_add(std::string &k, const T &v) { k.append(reinterpret_cast<const char *>(&v), sizeof(T)); }
 
 constexpr double QH_PI = 3.14159265358979323846, QH_TWO_PI = 2 * QH_PI;      // (the doubling is exact: QH_TWO_PI is the double nearest 2 pi)
 

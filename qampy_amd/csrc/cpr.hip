@@ -193,7 +193,7 @@ int vv_recover_dev(const void *E, int nmodes, int64_t L, int N, int M, void *tra
     QH_REQUIRE(nchunk <= 0x7fffffff, "vv_recover: row too long");
     // scratch: theta | chunk sums | wrap count of every chunk's first output
     UnwrapScratch us;
-    if ((rc = unwrap_scratch(SCRATCH_CPR, nmodes, nchunk, (size_t)nmodes * nout * sizeof(double), &us))) return rc;
+    if ((rc = unwrap_scratch(Slot::CPR, nmodes, nchunk, (size_t)nmodes * nout * sizeof(double), &us))) return rc;
     double *theta = (double *)us.base;
     int *csum = us.csum, *first = us.first;
     const dim3 grid((unsigned)nchunk, nmodes);
@@ -386,7 +386,7 @@ int partition16_recover_dev(const void *E, int nmodes, int64_t L, int Nblock, vo
     const size_t o_part = lay.take((size_t)nmodes * nparts * 2 * sizeof(double)), o_theta = lay.take((size_t)nmodes * nb * sizeof(double)),
                  o_K = lay.take((size_t)nmodes * nb * sizeof(int)), o_sum = lay.take((size_t)nmodes * nchunk * sizeof(int));
     void *sb = nullptr;
-    if ((rc = scratch(SCRATCH_CPR, lay.total, &sb))) return rc;
+    if ((rc = scratch(Slot::CPR, lay.total, &sb))) return rc;
     double *part = (double *)((char *)sb + o_part), *theta = (double *)((char *)sb + o_theta);
     int *Kb = (int *)((char *)sb + o_K), *csum = (int *)((char *)sb + o_sum);
     const double phi = QH_PI / 4 + atan(1. / 3.);

@@ -25,7 +25,7 @@
 // fft_correlate_pow2 (for sync.hip) is the filter's chain with a caller's geometry: rows of any length zero-extended to a power of two as they
 // are loaded, the table the transform of a second sequence, and only the first n values of the inverse transform stored, densely.
 //
-// Scratch slot SCRATCH_FFT: W_N1 | W_N2 | chirp (L) | transform of the chirp filter (M) | T (rows M, four-step) | W (rows M, Bluestein): the
+// Scratch slot Slot::FFT: W_N1 | W_N2 | chirp (L) | transform of the chirp filter (M) | T (rows M, four-step) | W (rows M, Bluestein): the
 // work buffers are 2 nmodes M complex values at most.  No atomics: a repeated call is bit-identical.  Every launch is bounded by the
 // call's arguments alone.
 #include "common.h"
@@ -311,7 +311,7 @@ template <typename R> static int fft_plan(int nmodes, int64_t L, FftPlan<R> &p)
                  o_B = lay.take(p.blue ? (size_t)p.M * cx : 0), o_T = lay.take(p.N1 > 1 ? (size_t)nmodes * p.M * cx : 0),
                  o_W = lay.take(p.blue ? (size_t)nmodes * p.M * cx : 0);
     void *base = nullptr;
-    int rc = scratch(SCRATCH_FFT, lay.total, &base);
+    int rc = scratch(Slot::FFT, lay.total, &base);
     if (rc) return rc;
     char *sb = (char *)base;
     p.tw1 = (Cx<R> *)(sb + o_tw1); p.tw2 = (Cx<R> *)(sb + o_tw2); p.chirp = (Cx<R> *)(sb + o_chirp); p.Bhat = (Cx<R> *)(sb + o_B);

@@ -19,7 +19,7 @@
 //
 // A call proceeds in chunks of c blocks, c = max(1, min(B, FOE_CHUNK / (nmodes N))): the per-block powers (nmodes c N reals) and the
 // four-step intermediate T (nmodes c N complex values) never exceed the blocks they come from (c N <= L whenever B N <= L; one zero-padded
-// block otherwise).  Tables, accumulator, partial results and intermediates live in scratch slot SCRATCH_FOE.  The tables W_N1^m and
+// block otherwise).  Tables, accumulator, partial results and intermediates live in scratch slot Slot::FOE.  The tables W_N1^m and
 // W_N2^m are formed on the device in double at every call (at most 8192 + 1024 entries): nothing is cached across calls and nothing is
 // copied from the host.  No atomics: a repeated call is bit-identical.  Every launch is bounded by the call's arguments alone.
 #include "common.h"
@@ -237,7 +237,7 @@ int find_freq_offset_dev(const void *E, int nmodes, int64_t L, int os, int fft_s
                  o_part = lay.take((size_t)nmodes * nparts * 3 * sizeof(double)), o_stats = lay.take((size_t)nmodes * 3 * sizeof(double)),
                  o_Pb = lay.take((size_t)nmodes * chunk * N * sizeof(R)), o_T = lay.take(N1 > 1 ? (size_t)nmodes * chunk * N * sizeof(Cx<R>) : 0);
     void *base = nullptr;
-    if ((rc = scratch(SCRATCH_FOE, lay.total, &base))) return rc;
+    if ((rc = scratch(Slot::FOE, lay.total, &base))) return rc;
     char *sb = (char *)base;
     Cx<R> *tw1 = (Cx<R> *)(sb + o_tw1), *tw2 = (Cx<R> *)(sb + o_tw2), *T = (Cx<R> *)(sb + o_T);
     R *P = (R *)(sb + o_P), *Pb = (R *)(sb + o_Pb);

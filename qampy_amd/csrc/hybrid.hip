@@ -304,7 +304,7 @@ template <typename R> int tdh_class_sums_dev(const void *E, int nmodes, int64_t 
     if ((rc = ensure_init())) return rc;
     const int ntiles = (int)((L + TDH_TILE - 1) / TDH_TILE);
     void *part = nullptr;
-    if ((rc = scratch(SCRATCH_HYBRID, (size_t)nmodes * ntiles * fM * sizeof(double), &part))) return rc;
+    if ((rc = scratch(Slot::HYBRID, (size_t)nmodes * ntiles * fM * sizeof(double), &part))) return rc;
     hipLaunchKernelGGL((tdh_class_tile_kernel<R>), dim3(ntiles, nmodes), dim3(TDH_T), 0, g_stream, (const Cx<R> *)E, (unsigned)L, (unsigned)fM, (double *)part);
     QH_HIP(hipGetLastError());
     hipLaunchKernelGGL(tdh_class_combine_kernel, dim3(fM, nmodes), dim3(64), 0, g_stream, (const double *)part, ntiles, sums);
@@ -355,7 +355,7 @@ int tdh_metrics_dev(const void *E, int nmodes, int64_t L, int fM, int fM1, doubl
     int64_t nblk = (most + TDH_T * TDH_S - 1) / (TDH_T * TDH_S);
     if (nblk > TDH_MAXBLK) nblk = TDH_MAXBLK;
     void *part = nullptr;
-    if ((rc = scratch(SCRATCH_HYBRID, (size_t)nmodes * nblk * TDH_F * sizeof(double), &part))) return rc;
+    if ((rc = scratch(Slot::HYBRID, (size_t)nmodes * nblk * TDH_F * sizeof(double), &part))) return rc;
     hipLaunchKernelGGL((tdh_metrics_kernel<R>), dim3((unsigned)nblk, nmodes), dim3(TDH_T), 0, g_stream, (const Cx<R> *)E, (unsigned)L, g, std::sqrt(powratio),
                        shift_dev, shift_host, idx_tx, (const Cx<R> *)alphabet1, M1, (const Cx<R> *)alphabet2, M2, (double *)part);
     QH_HIP(hipGetLastError());

@@ -20,15 +20,12 @@
 // bit-identical.
 //
 // PMD: R(-theta) diag(H, conj H) R(theta) with H = exp(-j w dgd / 2).  R commutes with the transform, so a workgroup rotates its block of
-// one row on load, transforms it in LDS (fft_lds.h), multiplies by H (row 0) or conj H (row 1), transforms back and stores; a second
-// point-wise launch rotates by -theta in place.  Block sizes and boundary rule of cd.hip's circular mode: a row length that is a power of
-// two from 256 to 8192 is one exact transform per row, every other length overlap-save with N = 8192 (N / 2 kept, N / 4 of halo on each
-// side, the input taken modulo L).
-#include "common.h"
-#include "fft_lds.h"
+// one row on load, transforms it in LDS, multiplies by H (row 0) or conj H (row 1), transforms back and stores - cd.hip's kernel with another
+// source policy (block_filter.h PmdRow); a second point-wise launch rotates by -theta in place.  Block sizes and boundary rule of cd.hip's
+// circular mode: a row length that is a power of two from 256 to 8192 is one exact transform per row, every other length overlap-save with
+// N = 8192 (N / 2 kept, N / 4 of halo on each side, the input taken modulo L).
+#include "block_filter.h"
 #include "philox.h"
-#include <cmath>
-#include <vector>
 
 namespace qh {
 
@@ -184,50 +181,6 @@ __global__ void __launch_bounds__(IMP_T) rotate_field_kernel(const Cx<R> *E, Cx<
     stg(out + L + n, Cx<R>{s * u.re + c * v.re, s * u.im + c * v.im});
 }
 
-// grid (blocks, 2): block blockIdx.x of row blockIdx.y of R(theta) E through H (row 0) or conj H (row 1); cd.hip's circular mode otherwise
-template <typename R, int N>
-__global__ void __launch_bounds__(CD_T) pmd_filter_kernel(const Cx<R> *__restrict__ E, Cx<R> *__restrict__ out, int64_t L, const Cx<R> *__restrict__ tab, R c,
-                                                          R s, int whole)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem_pmd[];
-    Cx<R> *buf = reinterpret_cast<Cx<R> *>(smem_pmd);
-    const Cx<R> *tw = tab, *H = tab + N;
-    constexpr int n = N / 2, q = N / 4;
-    const int row = blockIdx.y;
-    const R a = row == 0 ? c : s, b = row == 0 ? -s : c;                // the row of R(theta)
-    const int64_t blk = blockIdx.x;
-    int64_t base = 0;
-    if (!whole) {
-        base = (blk * n - q) % L;
-        if (base < 0) base += L;
-    }
-    for (int t = threadIdx.x; t < N; t += CD_T) {
-        int64_t p = base + t;                                           // whole: L == N, p = t
-        if (p >= L) p = L >= N ? p - L : p % L;
-        const Cx<R> u = ldg(E + p), v = ldg(E + L + p);
-        buf[t] = Cx<R>{a * u.re + b * v.re, a * u.im + b * v.im};
-    }
-    __syncthreads();
-    fft_from<R, N, 1>(buf, tw);
-    for (int t = threadIdx.x; t < N; t += CD_T) {
-        Cx<R> h = ldg(H + t);
-        if (row) h.im = -h.im;
-        const Cx<R> v = cmul(buf[t], h);
-        buf[t] = Cx<R>{v.re, -v.im};
-    }
-    __syncthreads();
-    fft_from<R, N, 1>(buf, tw);
-    Cx<R> *y = out + (size_t)row * L;
-    const int off = whole ? 0 : q, keep = whole ? N : n;
-    for (int t = threadIdx.x; t < keep; t += CD_T) {
-        const int64_t p = blk * keep + t;
-        if (p < L) {
-            const Cx<R> v = buf[off + t];
-            stg(y + p, Cx<R>{v.re, -v.im});
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ host side
 // E == nullptr: phase only (trace must be given).  noise_mode 0: none; 1: sigma = noise; 2: sigma = noise sqrt(mean |E|^2 over all modes)
 template <typename R>
@@ -249,7 +202,7 @@ int impair_pointwise_dev(const void *E, int nmodes, int64_t L, int noise_mode, d
     ScratchLayout lay;
     const size_t o_tot = lay.take((size_t)nmodes * ntiles * sizeof(double)), o_pw = lay.take((size_t)nmodes * ntiles * sizeof(double)), o_sig = lay.take(sizeof(double));
     void *base = nullptr;
-    if ((rc = scratch(SCRATCH_IMPAIR, lay.total, &base))) return rc;
+    if ((rc = scratch(Slot::IMPAIR, lay.total, &base))) return rc;
     double *tot = (double *)((char *)base + o_tot), *pw = (double *)((char *)base + o_pw), *sig = (double *)((char *)base + o_sig);
     const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
     const double sphase = have_phase ? sqrt(phase_var) : 0.0;
@@ -298,55 +251,15 @@ template <typename R> int rotate_field_dev(const void *E, int nmodes, int64_t L,
     return QH_OK;
 }
 
-// twiddles of the block transform and H[k] = exp(-j pi dgd k / N) / N on the fftfreq grid (dgd in samples), formed in double with the phase
-// reduced modulo 2 pi, uploaded once per (N, dgd, precision) into scratch slot SCRATCH_PMD (cd.hip cd_table)
-struct PmdTable {
-    int N = 0, rsize = 0;
-    double dgd = 0;
-    void *dev = nullptr;
-    unsigned epoch = 0;
-    std::vector<char> host;                // kept alive for the asynchronous upload
-};
-static thread_local PmdTable g_pmd;
+// twiddles of the block transform and H[k] = exp(-j pi dgd k / N) / N on the fftfreq grid (dgd in samples), uploaded once per
+// (N, dgd, precision) into scratch slot Slot::PMD
+static thread_local TableCache g_pmd;
 
 template <typename R> static int pmd_table(int N, double dgd, const Cx<R> **tab)
 {
-    const size_t bytes = 2 * (size_t)N * sizeof(Cx<R>);
-    void *p = nullptr;
-    int rc;
-    if (g_pmd.dev && g_pmd.N == N && g_pmd.rsize == (int)sizeof(R) && g_pmd.dgd == dgd && g_pmd.epoch == scratch_epoch()) {
-        if ((rc = scratch(SCRATCH_PMD, bytes, &p))) return rc;
-        if (p == g_pmd.dev) { *tab = (const Cx<R> *)p; return QH_OK; }
-    }
-    // a new table: whatever still reads the old one finishes first, and so does the upload that reads the host copy
-    if (g_pmd.dev) QH_HIP(hipDeviceSynchronize());
-    g_pmd.dev = nullptr;
-    if ((rc = scratch(SCRATCH_PMD, bytes, &p))) return rc;
-    g_pmd.host.resize(bytes);
-    Cx<R> *h = reinterpret_cast<Cx<R> *>(g_pmd.host.data());
-    for (int m = 0; m < N; m++) {
-        const double a = -QH_TWO_PI * (double)m / (double)N;
-        h[m] = Cx<R>{(R)cos(a), (R)sin(a)};
-        const int k = m < N / 2 ? m : m - N;                              // fftfreq order
-        const double ph = remainder(-QH_PI * dgd * (double)k / (double)N, QH_TWO_PI);
-        h[N + m] = Cx<R>{(R)(cos(ph) / N), (R)(sin(ph) / N)};
-    }
-    QH_HIP(hipMemcpyAsync(p, h, bytes, hipMemcpyHostToDevice, g_stream));
-    g_pmd.N = N; g_pmd.rsize = (int)sizeof(R); g_pmd.dgd = dgd; g_pmd.dev = p; g_pmd.epoch = scratch_epoch();
-    *tab = (const Cx<R> *)p;
-    return QH_OK;
-}
-
-template <typename R, int N> static int pmd_launch(const Cx<R> *E, Cx<R> *out, int64_t L, const Cx<R> *tab, R c, R s)
-{
-    const size_t lds = (size_t)N * sizeof(Cx<R>);
-    int rc = dyn_lds(pmd_filter_kernel<R, N>, lds);
-    if (rc) return rc;
-    const int whole = L == N;
-    const int64_t nblk = whole ? 1 : (L + N / 2 - 1) / (N / 2);
-    hipLaunchKernelGGL((pmd_filter_kernel<R, N>), dim3((unsigned)nblk, 2), dim3(CD_T), lds, g_stream, E, out, L, tab, c, s, whole);
-    QH_HIP(hipGetLastError());
-    return QH_OK;
+    std::string key;
+    key_add(key, dgd);
+    return filter_table<R>(g_pmd, Slot::PMD, N, key, [=](int k) { return -QH_PI * dgd * (double)k / (double)N; }, tab);
 }
 
 // dgd in samples (t_dgd fs)
@@ -363,18 +276,9 @@ template <typename R> int apply_pmd_dev(const void *E, int nmodes, int64_t L, do
     const int N = whole ? (int)L : PMD_N;
     const Cx<R> *tab;
     if ((rc = pmd_table<R>(N, dgd, &tab))) return rc;
-    const Cx<R> *e = (const Cx<R> *)E;
     Cx<R> *o = (Cx<R> *)out;
     const R c = (R)cos(theta), s = (R)sin(theta);
-    switch (N) {
-    case 256: rc = pmd_launch<R, 256>(e, o, L, tab, c, s); break;
-    case 512: rc = pmd_launch<R, 512>(e, o, L, tab, c, s); break;
-    case 1024: rc = pmd_launch<R, 1024>(e, o, L, tab, c, s); break;
-    case 2048: rc = pmd_launch<R, 2048>(e, o, L, tab, c, s); break;
-    case 4096: rc = pmd_launch<R, 4096>(e, o, L, tab, c, s); break;
-    default: rc = pmd_launch<R, 8192>(e, o, L, tab, c, s); break;
-    }
-    if (rc) return rc;
+    if ((rc = block_filter<R>(N, (const Cx<R> *)E, o, 2, L, L, tab, PmdRow<R>{c, s}, 0))) return rc;
     // R(-theta), in place
     hipLaunchKernelGGL((rotate_field_kernel<R>), dim3((unsigned)((L + IMP_T - 1) / IMP_T)), dim3(IMP_T), 0, g_stream, (const Cx<R> *)o, o, L, c, -s);
     QH_HIP(hipGetLastError());

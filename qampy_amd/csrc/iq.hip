@@ -7,7 +7,7 @@
 //   coeffs    one workgroup turns the moments into y = A (I, Q)^T + b per row: coef[row] = (a00, a01, a10, a11, b0, b1), nothing read back.
 //   affine    one point-wise pass, evaluated in double, stored in the signal's precision; `out` may be `E`.
 //
-// The tile totals live in scratch slot SCRATCH_FFT, which holds nothing across calls.  The derivation of the two maps is in DESIGN.md 3.14.
+// The tile totals live in scratch slot Slot::IQ.  The derivation of the two maps is in DESIGN.md 3.14.
 #include "common.h"
 #include <cmath>
 
@@ -130,7 +130,7 @@ template <typename R> int iq_moments_dev(const void *E, int nmodes, int64_t L, i
     const int64_t tiles = (L + IQ_TILE - 1) / IQ_TILE;
     QH_REQUIRE(tiles <= 0x7fffffffLL, "iq_moments: L too long");
     void *part = nullptr;
-    if ((rc = scratch(SCRATCH_FFT, (size_t)nmodes * tiles * IQ_NMOM * sizeof(double), &part))) return rc;
+    if ((rc = scratch(Slot::IQ, (size_t)nmodes * tiles * IQ_NMOM * sizeof(double), &part))) return rc;
     hipLaunchKernelGGL((iq_moments_tile_kernel<R>), dim3((unsigned)tiles, nmodes), dim3(IQ_T), 0, g_stream, (const Cx<R> *)E, L, os, (double *)part);
     hipLaunchKernelGGL(iq_moments_final_kernel, dim3(nmodes), dim3(IQ_T), 0, g_stream, (const double *)part, tiles, mom);
     QH_HIP(hipGetLastError());

@@ -597,7 +597,7 @@ int metrics_dev(const void *E, int64_t N, const int32_t *idx_tx, int64_t ntx, co
     const int F = 5 + nb;
     const unsigned g = grid_for(N - 2 * trim);
     void *buf = nullptr;
-    if ((rc = scratch(13, ((size_t)g + 1) * F * sizeof(double), &buf))) return rc;
+    if ((rc = scratch(Slot::METRICS, ((size_t)g + 1) * F * sizeof(double), &buf))) return rc;
     double *part = (double *)buf, *tot = part + (size_t)g * F;
     if (minmax) {
         QH_NB_DISPATCH(nb, hipLaunchKernelGGL((metrics_kernel<R, NB, true>), dim3(g), dim3(MET_THREADS), 0, g_stream, (const Cx<R> *)E, trim, N - trim, rot, lag,
@@ -624,7 +624,7 @@ int snr_stats(const void *E, int64_t i0, int64_t i1, int rot, int64_t lag, const
     void *buf = nullptr;
     const size_t np = (size_t)g * M * 3, nt = (size_t)M * 3 + (size_t)M * 2 + M;
     int rc;
-    if ((rc = scratch(14, (np + nt) * sizeof(double), &buf))) return rc;
+    if ((rc = scratch(Slot::SNR_EST, (np + nt) * sizeof(double), &buf))) return rc;
     double *part = (double *)buf, *sums = part + np, *mu = sums + (size_t)M * 3, *sse = mu + (size_t)M * 2;
     if (M <= MET_THREADS) hipLaunchKernelGGL((class_stats_kernel<R, false, 1>), dim3(g), dim3(MET_THREADS), 0, g_stream, (const Cx<R> *)E, i0, i1, rot, lag,
                                              idx_tx, ntx, M, (const double *)nullptr, part);
@@ -756,8 +756,7 @@ constexpr size_t MC_PARTIAL_DOUBLES = (size_t)1 << 22;      // most doubles of w
 
 // out (nsnr, 2 + nbits) = [gmi, mi, gmi per bit] of every SNR point, nothing read back.  The SNR points go through in batches whose partials fit
 // MC_PARTIAL_DOUBLES - three launches per batch; a 31-point curve of 1024-QAM is one batch, 65535 points of it are 177 - and a point's result does
-// not depend on the batch it falls into.  The partials share slot 13 with metrics_dev: the slots belong to the calling host thread, whichever of
-// its library streams is current, so calls of the two on different streams of one thread have to be ordered by the caller.
+// not depend on the batch it falls into.
 template <typename R> int awgn_mc_dev(const void *alphabet, int M, const double *snr, int nsnr, const void *z, int64_t ns, double *out)
 {
     int rc = awgn_mc_sizes(nsnr, ns);
@@ -770,7 +769,7 @@ template <typename R> int awgn_mc_dev(const void *alphabet, int M, const double 
     const unsigned g = grid_for(ns * M);
     const int batch = (int)std::min<size_t>((size_t)nsnr, std::max<size_t>(1, MC_PARTIAL_DOUBLES / (((size_t)g + 1) * F)));
     void *buf = nullptr;
-    if ((rc = scratch(13, ((size_t)g + 1) * batch * F * sizeof(double), &buf))) return rc;
+    if ((rc = scratch(Slot::AWGN_MC, ((size_t)g + 1) * batch * F * sizeof(double), &buf))) return rc;
     double *part = (double *)buf, *tot = part + (size_t)g * batch * F;
     for (int p0 = 0; p0 < nsnr; p0 += batch) {
         const int n = std::min(batch, nsnr - p0);

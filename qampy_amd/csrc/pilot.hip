@@ -340,7 +340,7 @@ int pilot_phase_dev(const void *E, int nmodes, int64_t L, const int64_t *where, 
     if ((rc = phase_args<R>(&a, "pilot_phase", E, nmodes, L, where, npf, nframes, F, span, n, sent, nref))) return rc;
     QH_REQUIRE(phase, "pilot_phase: phase must be given");
     UnwrapScratch s;
-    if ((rc = unwrap_scratch(SCRATCH_PILOT, nmodes, a.nchunk, 0, &s))) return rc;
+    if ((rc = unwrap_scratch(Slot::PILOT, nmodes, a.nchunk, 0, &s))) return rc;
     launch_phase<R>(a, nmodes, phase, s);
     QH_HIP(hipGetLastError());
     return QH_OK;
@@ -376,7 +376,7 @@ int pilot_cpe_dev(const void *E, int nmodes, int64_t L, const int64_t *where, in
     ScratchLayout head;
     const size_t o_phase = head.take((size_t)nmodes * n * sizeof(double)), o_kph = head.take((size_t)nmodes * nk * sizeof(double)), o_pos = head.take((size_t)nk * sizeof(int64_t));
     UnwrapScratch s;
-    if ((rc = unwrap_scratch(SCRATCH_PILOT, nmodes, a.nchunk, head.total, &s))) return rc;
+    if ((rc = unwrap_scratch(Slot::PILOT, nmodes, a.nchunk, head.total, &s))) return rc;
     double *phase = (double *)(s.base + o_phase), *kph = (double *)(s.base + o_kph);
     int64_t *kpos = (int64_t *)(s.base + o_pos);
     launch_phase<R>(a, nmodes, phase, s);
@@ -400,7 +400,7 @@ template <typename R> int pair_phase(const char *who, const void *rec, const voi
     a.L = n; a.npf = 1; a.F = 1; a.span = n; a.n = n; a.nref = n;
     a.nchunk = (n + UW_CHUNK - 1) / UW_CHUNK;
     UnwrapScratch s;
-    int rc = unwrap_scratch(SCRATCH_PILOT, nmodes, a.nchunk, (size_t)nmodes * n * sizeof(double), &s);
+    int rc = unwrap_scratch(Slot::PILOT, nmodes, a.nchunk, (size_t)nmodes * n * sizeof(double), &s);
     if (rc) return rc;
     *phase = (double *)s.base;
     launch_phase<R>(a, nmodes, *phase, s);

@@ -436,7 +436,7 @@ int lut_accumulate_dev(const void *tx, const void *rx, int nmodes, int64_t L, co
     ScratchLayout lay;
     const size_t o_part = lay.take((size_t)nmodes * ntiles * sizeof(double)), o_scale = lay.take((size_t)nmodes * 2 * sizeof(double));
     void *base = nullptr;
-    if ((rc = scratch(SCRATCH_PRECOMP, lay.total, &base))) return rc;
+    if ((rc = scratch(Slot::PRECOMP, lay.total, &base))) return rc;
     double *part = (double *)((char *)base + o_part), *scale = (double *)((char *)base + o_scale);
     int hb = 0;
     while (((int64_t)1 << hb) < L + 1) hb++;
@@ -492,7 +492,7 @@ int dac_preemphasis_table_dev(int64_t n, double fb, double fs, double beta, doub
         }
     const int64_t ntiles = (n + PC_TILE - 1) / PC_TILE;
     void *base = nullptr;
-    if ((rc = scratch(SCRATCH_PRECOMP, (size_t)(ntiles + 1) * sizeof(double), &base))) return rc;
+    if ((rc = scratch(Slot::PRECOMP, (size_t)(ntiles + 1) * sizeof(double), &base))) return rc;
     hipLaunchKernelGGL(dac_part_kernel, dim3((unsigned)ntiles), dim3(PC_THREADS), 0, g_stream, a, (double *)base);
     hipLaunchKernelGGL(dac_alpha_kernel, dim3(1), dim3(PC_THREADS), 0, g_stream, a.c, (double *)base, ntiles);
     hipLaunchKernelGGL((dac_table_kernel<R>), dim3((unsigned)ntiles), dim3(PC_THREADS), 0, g_stream, a, (const double *)base, ntiles, (Cx<R> *)pf);

@@ -11,7 +11,7 @@
 // Supported: 1 <= up, down <= 64, 1 <= ntaps <= 8191, 1 <= nmodes <= 65535, Lout <= ceil(L up / down), out another buffer than E.
 //
 // Layout.  The host reorders the taps phase-major, tab[p][j] = h[p + j up] (zero-padded to J), and uploads the table once per distinct
-// (taps, up, precision) into scratch slot 12; a kept host copy of h tells a new tap set from the last one.  A workgroup owns a tile of
+// (taps, up, precision) into scratch slot Slot::RESAMPLE_TABLE; the taps are part of the table's key.  A workgroup owns a tile of
 // up * G * 4 consecutive outputs of one row.  Thread (i, g), i = t % up the fast index, keeps the 4 outputs k = K0 + (r G + g) up + i,
 // r = 0 .. 3, in registers: they share the phase p, so one coefficient read feeds 4 complex FMAs, their inputs lie r G down samples apart,
 // and for each r a wave stores a contiguous run of outputs.  The sum over j runs in chunks of JC taps per phase; for each chunk the
@@ -31,13 +31,11 @@
 //
 // Renormalisation (the reference's renormalise=True: normalise_and_center(out) * sqrt(mean |in|^2)), without the host:
 //   row_moments   mean re, mean im, mean |.|^2 of every row, accumulated in double: RM_NB partial sums per row in a fixed order (scratch
-//                 slot 5), then one wave per row adds them, again in a fixed order.  3 doubles per row in device memory.
+//                 slot Slot::ROW_MOMENTS), then one wave per row adds them, again in a fixed order.  3 doubles per row in device memory.
 //   center_scale  x <- (x - mean) sqrt(P / (mean |x|^2 - |mean|^2)) in place, the moments read from device memory; P is the mean
 //                 |.|^2 of a second moments buffer (the input's), or a given target power when that pointer is NULL.
 #include "common.h"
 #include <cmath>
-#include <cstring>
-#include <vector>
 
 namespace qh {
 
@@ -166,39 +164,22 @@ __global__ void __launch_bounds__(RM_T) center_scale_kernel(Cx<R> *__restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-struct RsTable {
-    int up = 0, rsize = 0;
-    std::vector<double> h;                 // the taps the device table was formed from
-    void *dev = nullptr;
-    unsigned epoch = 0;
-    std::vector<char> host;                // kept alive for the asynchronous upload
-};
-static thread_local RsTable g_rs;
+static thread_local TableCache g_rs;
 
 template <typename R> static int rs_table(const double *h, int ntaps, int up, int J, const R **tab)
 {
-    const size_t bytes = (size_t)up * J * sizeof(R);
-    void *p = nullptr;
-    int rc;
-    if (g_rs.dev && g_rs.up == up && g_rs.rsize == (int)sizeof(R) && (int)g_rs.h.size() == ntaps && g_rs.epoch == scratch_epoch() &&
-        std::memcmp(g_rs.h.data(), h, (size_t)ntaps * sizeof(double)) == 0) {
-        if ((rc = scratch(12, bytes, &p))) return rc;
-        if (p == g_rs.dev) { *tab = (const R *)p; return QH_OK; }
-    }
-    // a new table: whatever still reads the old one (a launch on another of this thread's streams) finishes first
-    if (g_rs.dev) QH_HIP(hipDeviceSynchronize());
-    if ((rc = scratch(12, bytes, &p))) return rc;
-    g_rs.host.resize(bytes);
-    R *pm = reinterpret_cast<R *>(g_rs.host.data());
-    for (int ph = 0; ph < up; ph++)
-        for (int j = 0; j < J; j++) {
-            const int idx = ph + j * up;
-            pm[(size_t)ph * J + j] = idx < ntaps ? (R)h[idx] : (R)0;
-        }
-    QH_HIP(hipMemcpyAsync(p, pm, bytes, hipMemcpyHostToDevice, g_stream));
-    g_rs.up = up; g_rs.rsize = (int)sizeof(R); g_rs.h.assign(h, h + ntaps); g_rs.dev = p; g_rs.epoch = scratch_epoch();
-    *tab = (const R *)p;
-    return QH_OK;
+    std::string key;
+    key_add(key, up);
+    key_add(key, (int)sizeof(R));
+    key.append(reinterpret_cast<const char *>(h), (size_t)ntaps * sizeof(double));
+    return g_rs.get(Slot::RESAMPLE_TABLE, key, (size_t)up * J * sizeof(R), [=](char *host) {
+        R *pm = reinterpret_cast<R *>(host);
+        for (int ph = 0; ph < up; ph++)
+            for (int j = 0; j < J; j++) {
+                const int idx = ph + j * up;
+                pm[(size_t)ph * J + j] = idx < ntaps ? (R)h[idx] : (R)0;
+            }
+    }, (const void **)tab);
 }
 
 static int rs_check(int nmodes, int64_t L, const double *h, int ntaps, int up, int down, double gain, int64_t Lout)
@@ -266,7 +247,7 @@ template <typename R> int row_moments_dev(const void *E, int nmodes, int64_t L, 
     if (chunk < RM_T) chunk = RM_T;
     const int nb = (int)((L + chunk - 1) / chunk);
     void *part = nullptr;
-    if ((rc = scratch(5, (size_t)nmodes * nb * 3 * sizeof(double), &part))) return rc;
+    if ((rc = scratch(Slot::ROW_MOMENTS, (size_t)nmodes * nb * 3 * sizeof(double), &part))) return rc;
     hipLaunchKernelGGL((row_moments_part_kernel<R>), dim3(nb, nmodes), dim3(RM_T), 0, g_stream, (const Cx<R> *)E, L, chunk, (double *)part);
     QH_HIP(hipGetLastError());
     hipLaunchKernelGGL(row_moments_final_kernel, dim3(nmodes), dim3(64), 0, g_stream, (const double *)part, nb, L, mom);

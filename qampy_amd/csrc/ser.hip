@@ -99,7 +99,7 @@ int ser_dev(const void *E, int64_t N, const int32_t *idx_tx, int nmodes, int64_t
     void *buf = nullptr;
     const size_t b_idx4 = (size_t)4 * W * sizeof(int32_t), b_cnt = (size_t)nmodes * 4 * nlag * sizeof(unsigned);
     const size_t b_rx = (size_t)N * sizeof(int32_t);
-    if ((rc = scratch(8, b_idx4 + b_cnt + b_rx + 64, &buf))) return rc;
+    if ((rc = scratch(Slot::SER, b_idx4 + b_cnt + b_rx + 64, &buf))) return rc;
     int32_t *idx4 = (int32_t *)buf;
     unsigned *counts = (unsigned *)((char *)buf + b_idx4);
     int32_t *rx = (int32_t *)((char *)buf + b_idx4 + b_cnt);

@@ -14,7 +14,7 @@
 //             rotation is a swap and a sign.  One read, one write.
 //   labels    out[i] = alphabet[idx[i]], 0 for a label outside [0, M).
 //
-// No atomics: a repeated call is bit-identical.  Scratch slot SCRATCH_SYNC: reversed y (P) | spectra (rows, P); SCRATCH_PEAK: the partials.
+// No atomics: a repeated call is bit-identical.  Scratch slot Slot::SYNC: reversed y (P) | spectra (rows, P); Slot::PEAK: the partials.
 // Grow-only, so a call at a shape seen before allocates nothing.  Every launch is bounded by the call's arguments alone.
 #include "common.h"
 #include <cmath>
@@ -181,7 +181,7 @@ template <typename R> int xcorr_dev(const void *x, int nx_rows, int64_t nx, cons
     ScratchLayout lay;
     const size_t o_y = lay.take((size_t)P * sizeof(Cx<R>)), o_spec = lay.take((size_t)nx_rows * P * sizeof(Cx<R>));
     void *base = nullptr;
-    if ((rc = scratch(SCRATCH_SYNC, lay.total, &base))) return rc;
+    if ((rc = scratch(Slot::SYNC, lay.total, &base))) return rc;
     Cx<R> *yrev = (Cx<R> *)((char *)base + o_y), *spec = (Cx<R> *)((char *)base + o_spec);
     hipLaunchKernelGGL((sync_reverse_kernel<R>), dim3((unsigned)((ny + SY_T - 1) / SY_T)), dim3(SY_T), 0, g_stream, (const Cx<R> *)y, ny, yrev);
     QH_HIP(hipGetLastError());
@@ -196,7 +196,7 @@ template <typename R> int xcorr_peak_dev(const void *cc, int rows, int64_t n, do
     QH_REQUIRE(cc && res, "xcorr_peak: cc and res must be given");
     const int tiles = (int)((n + PK_TILE - 1) / PK_TILE);
     void *part = nullptr;
-    if ((rc = scratch(SCRATCH_PEAK, (size_t)rows * tiles * PK_F * sizeof(double), &part))) return rc;
+    if ((rc = scratch(Slot::PEAK, (size_t)rows * tiles * PK_F * sizeof(double), &part))) return rc;
     hipLaunchKernelGGL((sync_peak_tile_kernel<R>), dim3(tiles, rows), dim3(SY_T), 0, g_stream, (const Cx<R> *)cc, n, (double *)part);
     hipLaunchKernelGGL((sync_peak_final_kernel<R>), dim3(rows), dim3(SY_T), 0, g_stream, (const double *)part, tiles, res);
     QH_HIP(hipGetLastError());

@@ -240,7 +240,7 @@ int synth_capture(void *E, void *symbols, int32_t *idx_tx, const void *alphabet,
     const int ntiles = (int)((L + SYNTH_T - 1) / SYNTH_T);
     void *buf = nullptr;
     const size_t b_h = (size_t)NH * 4, b_pm = 3 * SYNTH_NP * 4, b_ph = (size_t)nmodes * ntiles * 4;
-    if ((rc = scratch(9, b_h + b_pm + b_ph + 64, &buf))) return rc;
+    if ((rc = scratch(Slot::SYNTH, b_h + b_pm + b_ph + 64, &buf))) return rc;
     float *d_h = (float *)buf, *d_pm = d_h + NH, *d_ph = d_pm + 3 * SYNTH_NP;
     QH_HIP(hipMemcpyAsync(d_h, h.data(), b_h, hipMemcpyHostToDevice, g_stream));
     QH_HIP(hipMemcpyAsync(d_pm, pm.data(), b_pm, hipMemcpyHostToDevice, g_stream));

@@ -527,7 +527,7 @@ template <typename R> int slicer_tables(const void *symbols, int nmodes, int64_t
     *npart = -1;
     if (nsy > 1024 || nsy < 4) return QH_OK;
     void *buf = nullptr;
-    int rc = scratch(7, (size_t)nmodes * 2 * BI_DD_MAXLEV * sizeof(Cx<R>) + (size_t)nmodes * sizeof(int), &buf);
+    int rc = scratch(Slot::BI_LEVELS, (size_t)nmodes * 2 * BI_DD_MAXLEV * sizeof(Cx<R>) + (size_t)nmodes * sizeof(int), &buf);
     if (rc) return rc;
     int *info = reinterpret_cast<int *>((char *)buf + (size_t)nmodes * 2 * BI_DD_MAXLEV * sizeof(Cx<R>));
     hipLaunchKernelGGL((slicer_table_kernel<R>), dim3(nmodes), dim3(64), 0, g_stream, (const Cx<R> *)symbols, (int)nsy, (Cx<R> *)buf, info);
@@ -559,7 +559,7 @@ template <typename R> int gram_cur_build(const void *E, int nmodes, int64_t L, i
     if (rc) return rc;
     void *G = nullptr;
     const size_t bytes = gram_cur_bytes<R>(TrSyms);
-    if ((rc = scratch(4, bytes * (size_t)nch, &G))) return rc;
+    if ((rc = scratch(Slot::GRAM, bytes * (size_t)nch, &G))) return rc;
     const int64_t nblk = (TrSyms + LA_B - 1) / LA_B;
     const size_t lds = (size_t)nmodes * ((LA_B - 1) * os + ntaps) * sizeof(Cx<R>);
     QH_REQUIRE(lds <= 64 * 1024, "gram: nmodes*(63*os+ntaps) samples exceed the LDS tile");

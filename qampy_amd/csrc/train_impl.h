@@ -675,7 +675,7 @@ int train_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Niter, i
             R *mu_modes = nullptr;
             if (per_mode) {
                 void *pm = nullptr;
-                if ((rc = scratch(6, (size_t)nch * nsel * sizeof(R), &pm))) return rc;
+                if ((rc = scratch(Slot::STEP_SIZES, (size_t)nch * nsel * sizeof(R), &pm))) return rc;
                 mu_modes = (R *)pm;
                 hipLaunchKernelGGL((spread_kernel<R>), dim3((unsigned)((nch * nsel + 63) / 64)), dim3(64), 0, g_stream, mu_modes, (const R *)mu_dev, nsel, nch * nsel);
                 la.mu = mu_modes; la.mu_out = mu_modes; la.mu_cs = nsel; la.mu_ms = 1;
@@ -718,7 +718,7 @@ int train_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Niter, i
         QH_REQUIRE(!chan_stride && !row_pitch, "train_equaliser: strided channels need a block form of the trainer");
         if (per_mode) {                            // one call per mode, each from the initial step size
             void *pm = nullptr;
-            if ((rc = scratch(6, (size_t)nch * sizeof(R), &pm))) return rc;
+            if ((rc = scratch(Slot::STEP_SIZES, (size_t)nch * sizeof(R), &pm))) return rc;
             QH_HIP(hipMemcpyAsync(pm, mu_dev, (size_t)nch * sizeof(R), hipMemcpyDeviceToDevice, g_stream));
             for (int j = 0; j < nsel; j++) {
                 QH_HIP(hipMemcpyAsync(mu_dev, pm, (size_t)nch * sizeof(R), hipMemcpyDeviceToDevice, g_stream));

@@ -595,7 +595,7 @@ template <typename R> int gram_build(const void *E, int nmodes, int64_t L, int o
     if (rc) return rc;
     const size_t bytes = gram_bytes<R>(TrSyms);
     void *G0 = into;                                             // (the caller's buffer - gram_bytes(TrSyms) x nch - or the library's scratch)
-    if (!G0 && (rc = scratch(4, bytes * (size_t)nch, &G0))) return rc;
+    if (!G0 && (rc = scratch(Slot::GRAM, bytes * (size_t)nch, &G0))) return rc;
     const int64_t nblk = (TrSyms + LA_B - 1) / LA_B;
     const size_t lds = (size_t)nmodes * ((2 * LA_B - 1) * os + ntaps) * sizeof(Cx<R>);
     QH_REQUIRE(lds <= 64 * 1024, "gram: nmodes*(127*os+ntaps) samples exceed the LDS tile");

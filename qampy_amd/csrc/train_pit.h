@@ -2162,7 +2162,7 @@ int pit_basis(const void *E, int nmodes, int64_t L, int os, int ntaps, int64_t T
     QH_REQUIRE(TrSyms >= 1 && (TrSyms - 1) * os + ntaps <= L, "pit basis: field shorter than TrSyms*os + ntaps");
     const size_t msz = (size_t)ntot * ntot;
     void *cb = nullptr;
-    if ((rc = scratch(9, (1 + (size_t)PIT_COVB) * msz * sizeof(Z), &cb))) return rc;
+    if ((rc = scratch(Slot::PIT_COV, (1 + (size_t)PIT_COVB) * msz * sizeof(Z), &cb))) return rc;
     Z *Rc = (Z *)cb, *part = Rc + msz;
     const int ncov = (int)(TrSyms < PIT_COVW * PIT_COVB ? TrSyms : PIT_COVW * PIT_COVB);
     const int ept = (int)((msz + 255) / 256);
@@ -2182,7 +2182,7 @@ int pit_basis(const void *E, int nmodes, int64_t L, int os, int ntaps, int64_t T
     {
         void *gl = nullptr;
         const int mm = (ntot + 1) & ~1;
-        if ((rc = scratch(11, (size_t)nsweep * (mm - 1) * (mm / 2) * sizeof(float4) + 64, &gl))) return rc;
+        if ((rc = scratch(Slot::PIT_ROTATIONS, (size_t)nsweep * (mm - 1) * (mm / 2) * sizeof(float4) + 64, &gl))) return rc;
         glog = (float4 *)gl;
     }
     const size_t blds = 2 * (size_t)ntot * (ntot + 1) * sizeof(Zf) + 256;
@@ -2412,7 +2412,7 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
         if (exact_only) {
             QH_REQUIRE(!o.exchange, "train_equaliser: a capture split over processes needs the parallel-in-time solver (blind / decision-directed method, fixed step)");
             void *cb0 = nullptr;
-            if ((rc = scratch(8, sizeof(PitCtrl) + 64, &cb0))) return rc;
+            if ((rc = scratch(Slot::PIT_CTRL, sizeof(PitCtrl) + 64, &cb0))) return rc;
             PitCtrl *c0 = report_dev ? (PitCtrl *)report_dev : (PitCtrl *)cb0;
             PitSeg s1; s1.S = 1; s1.len = TrSyms; s1.extra = 0; s1.tail = 0;
             hipLaunchKernelGGL((pit_setup_kernel<R>), dim3(1), dim3(256), 0, g_stream, (const Cx<R> *)E, nmodes, L, (int64_t)(L < 4096 ? L : 4096), nmodes * ntaps, (const R *)mu_dev, 1.0, 1.0,
@@ -2435,7 +2435,7 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
 
     // ---- control block / report
     void *cbuf = nullptr;
-    if ((rc = scratch(8, sizeof(PitCtrl) + 64, &cbuf))) return rc;
+    if ((rc = scratch(Slot::PIT_CTRL, sizeof(PitCtrl) + 64, &cbuf))) return rc;
     PitCtrl *ctrl = report_dev ? (PitCtrl *)report_dev : (PitCtrl *)cbuf;
     R *mu_acq = (R *)((char *)cbuf + sizeof(PitCtrl));            // 8-byte aligned: sizeof(PitCtrl) is a multiple of 8
 
@@ -2506,7 +2506,7 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
     void *wbuf = nullptr;
     const size_t nsj = (size_t)sg.S * nsel;
     const size_t bytes_w = ((2 * (size_t)sg.S + 2) * wbytes + 63) / 64 * 64;
-    if ((rc = scratch(2, bytes_w + 10 * nsj * sizeof(double) + (size_t)nsel * sizeof(int64_t) + 320 + nsj * 16 + 4 * ((nsj + 63) / 64) * sizeof(float) + 64, &wbuf))) return rc;
+    if ((rc = scratch(Slot::PIT_WORK, bytes_w + 10 * nsj * sizeof(double) + (size_t)nsel * sizeof(int64_t) + 320 + nsj * 16 + 4 * ((nsj + 63) / 64) * sizeof(float) + 64, &wbuf))) return rc;
     Cx<R> *X = (Cx<R> *)wbuf, *Y = X + (size_t)sg.S * wset, *w_start = Y + (size_t)sg.S * wset, *w_call = w_start + wset;
     double *z = (double *)((char *)wbuf + bytes_w), *rot = z + 2 * nsj, *dfc = rot + 2 * nsj, *pw = dfc + nsj, *gph = pw + nsj, *theta = gph + 2 * nsj;
     int64_t *modes_dev = (int64_t *)(theta + 2 * nsj);
@@ -2524,13 +2524,13 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
     float *ad_M = nullptr, *ad_chg = nullptr, *ad_rP = nullptr, *ad_dP = nullptr;
     if (!adaptive && head > 0) {
         void *ab = nullptr;
-        if ((rc = scratch(13, (size_t)nmodes * head * sizeof(Cx<R>) + 64, &ab))) return rc;
+        if ((rc = scratch(Slot::PIT_ACQ, (size_t)nmodes * head * sizeof(Cx<R>) + 64, &ab))) return rc;
         ad_errh = (Cx<R> *)ab;
     }
     if (adaptive) {
         void *ab = nullptr;
         const size_t nS = ((size_t)sg.S + 15) / 16 * 16;
-        if ((rc = scratch(13, nS * (2 * sizeof(R) + 2 * sizeof(Cx<R>) + 3 * sizeof(float)) + 64 + (size_t)nmodes * head * sizeof(Cx<R>), &ab))) return rc;
+        if ((rc = scratch(Slot::PIT_ACQ, nS * (2 * sizeof(R) + 2 * sizeof(Cx<R>) + 3 * sizeof(float)) + 64 + (size_t)nmodes * head * sizeof(Cx<R>), &ab))) return rc;
         ad_eS = (Cx<R> *)ab; ad_eE = ad_eS + nS; ad_errh = ad_eE + nS;
         ad_rS = (R *)(ad_errh + (size_t)nmodes * head); ad_rE = ad_rS + nS;
         ad_M = (float *)(ad_rE + nS); ad_rP = ad_M + nS; ad_dP = ad_rP + nS; ad_chg = ad_dP + nS;
@@ -2573,7 +2573,7 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
     Zf *Xe = nullptr, *Ye = nullptr, *Yprev = nullptr;
     if (want_corr) {
         void *cb = nullptr;
-        if ((rc = scratch(10, pit_basis_bytes(ntot) + 4 * (size_t)ntot * ncol * sizeof(Zf) + (size_t)ntot * nsel * sizeof(Zf) + 256, &cb))) return rc;
+        if ((rc = scratch(Slot::PIT_BASIS, pit_basis_bytes(ntot) + 4 * (size_t)ntot * ncol * sizeof(Zf) + (size_t)ntot * nsel * sizeof(Zf) + 256, &cb))) return rc;
         void *basis = o.basis ? o.basis : cb;
         if (!o.basis && (rc = pit_basis<R>(E, nmodes, L, os, ntaps, TrSyms, basis))) return rc;
         lam = (const double *)basis; Vb = (const Zf *)((const char *)basis + (size_t)ntot * sizeof(double));
@@ -2604,7 +2604,7 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
         const size_t pw_ = 2 * PIT_EIGMAX + 8;
         const size_t b_part = (size_t)PIT_MODB * 4 * nsel * pw_ * sizeof(float), b_u = ((size_t)nsel * ntot * sizeof(Cx<R>) + 63) / 64 * 64;
         const size_t b_ua = ((size_t)ncol * sizeof(float4) + 63) / 64 * 64, b_uq = ((size_t)ncol * sizeof(float2) + 63) / 64 * 64;
-        if ((rc = scratch(14, b_part + b_u + b_ua + b_uq + 16 * sizeof(PitModel) + 128, &mb))) return rc;
+        if ((rc = scratch(Slot::PIT_MODEL, b_part + b_u + b_ua + b_uq + 16 * sizeof(PitModel) + 128, &mb))) return rc;
         ma.part = (float *)mb; ma.u = (Cx<R> *)((char *)mb + b_part);
         ualpha = (float4 *)((char *)mb + b_part + b_u); uqv = (float2 *)((char *)ualpha + b_ua);
         model = (PitModel *)((char *)uqv + b_uq); ma.model = model; ma.ticket = (unsigned *)(model + 16);

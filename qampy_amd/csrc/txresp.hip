@@ -368,13 +368,13 @@ template <int NS> __global__ void __launch_bounds__(SOS_W) sos_carry_kernel(doub
 // ------------------------------------------------------------------------------------------------ host side
 static bool tx_sizes_ok(int nmodes, int64_t L) { return nmodes >= 1 && nmodes <= TX_MAXMODES && L >= 0 && (L + TX_TILE - 1) / TX_TILE <= 0x7fffffffLL; }
 
-// scratch slot SCRATCH_TXRESP: the row extrema a call forms for itself (own_extrema), at its base | the tile extrema, at *part
+// scratch slot Slot::TXRESP: the row extrema a call forms for itself (own_extrema), at its base | the tile extrema, at *part
 static int extrema_scratch(int nmodes, int64_t ntiles, void **base, double **part)
 {
     ScratchLayout lay;
     lay.take(2 * (size_t)nmodes * sizeof(double));
     const size_t o_part = lay.take(2 * (size_t)nmodes * ntiles * sizeof(double));
-    int rc = scratch(SCRATCH_TXRESP, lay.total, base);
+    int rc = scratch(Slot::TXRESP, lay.total, base);
     if (rc) return rc;
     *part = (double *)((char *)*base + o_part);
     return QH_OK;
@@ -513,7 +513,7 @@ template <typename R, int NS> static int sosfilt_launch(const Cx<R> *E, Cx<R> *o
     for (int i = 0; i < n * n; i++) { pt.m[6][i] = (double)Q[i]; pc.m[6][i] = (double)Q[i]; }
     void *base = nullptr;
     int rc;
-    if ((rc = scratch(SCRATCH_SOS, (size_t)nmodes * ntiles * 2 * n * sizeof(double), &base))) return rc;
+    if ((rc = scratch(Slot::SOS, (size_t)nmodes * ntiles * 2 * n * sizeof(double), &base))) return rc;
     double *st = (double *)base;
     const dim3 grid((unsigned)ntiles, nmodes);
     if (ntiles > 1) {

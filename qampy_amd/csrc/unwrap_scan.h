@@ -114,7 +114,7 @@ static __global__ void __launch_bounds__(1024) unwrap_scan_kernel(int *chunk_sum
 // Scratch of the three launches in a caller's slot, behind `head` bytes the caller keeps for itself (at base): chunk sums | wrap count of
 // every chunk's first element
 struct UnwrapScratch { char *base; int *csum, *first; };
-inline int unwrap_scratch(int slot, int nmodes, int64_t nchunk, size_t head, UnwrapScratch *s)
+inline int unwrap_scratch(Slot slot, int nmodes, int64_t nchunk, size_t head, UnwrapScratch *s)
 {
     ScratchLayout lay;
     lay.take(head);

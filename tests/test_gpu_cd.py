@@ -13,6 +13,7 @@ import cd_ref
 from qampy_amd import _lib, synth
 from qampy_amd._lib import DeviceArray
 from qampy_amd.core import filter as cdf
+from table_cache_check import assert_sequence_matches_fresh_calls
 
 pytestmark = pytest.mark.gpu
 
@@ -134,6 +135,32 @@ def test_repeat_calls_bit_identical():
     cdf.cd_filter_dev(E, a, FS, D, 1000e3, WL)
     cdf.cd_filter_dev(E, b, FS, D, 1000e3, WL)
     assert np.array_equal(a.to_host(), b.to_host())
+    # the table follows its key (N, coefficients, precision): key A, key B, A again; the other precision in between; a larger table, which
+    # regrows the slot, in between - every call gives the bits it gives as the first call after qh_release_scratch
+    x = cd_ref.bandlimited(2, 389, 6)
+    co = (-16 / (4 * np.pi), 0.3, 0.7)
+    for dt, other in ((np.complex64, np.complex128), (np.complex128, np.complex64)):
+        calls = {"256": lambda: run_dev(x.astype(dt), 256, co, "circular"), "512": lambda: run_dev(x.astype(dt), 512, co, "circular"),
+                 "256 other coefficients": lambda: run_dev(x.astype(dt), 256, (co[0], 0.2, 0.7), "circular"),
+                 "256 other precision": lambda: run_dev(x.astype(other), 256, co, "circular"),
+                 "8192": lambda: run_dev(x.astype(dt), 8192, co, "circular")}
+        want = assert_sequence_matches_fresh_calls(calls, ["256", "512", "256", "256 other coefficients", "256", "256 other precision", "256",
+                                                           "256 other precision", "8192", "256", "512"])
+        assert not np.array_equal(want["256"], want["512"]) and not np.array_equal(want["256"], want["256 other coefficients"])
+        assert rel_max(want["256"], cd_ref.cd_filter(x.astype(dt), 256, *co)) <= BAR[dt]
+
+
+@pytest.mark.parametrize("dtype", [np.complex64, np.complex128])
+@pytest.mark.parametrize("L", [1, 100, 256, 257, 3 * 128 + 5])
+def test_circular_edges_at_the_smallest_block(L, dtype):
+    """N = 256: a row shorter than the block, whose halo wraps round it several times; the whole row; one sample more; a partial last block."""
+    coeffs = (-(256 / 16) / (4 * np.pi), 0.3, 0.7)
+    x = cd_ref.bandlimited(2, L, 40 + L).astype(dtype)
+    want = cd_ref.cd_filter(x, 256, *coeffs)
+    got = run_dev(x, 256, coeffs, "circular")
+    assert got.shape == want.shape and got.dtype == dtype
+    print("cd edge", L, np.dtype(dtype).name, rel_max(got, want))
+    assert rel_max(got, want) <= BAR[dtype], (L, rel_max(got, want))
 
 
 def test_bad_arguments_rejected_by_the_library():

@@ -24,6 +24,7 @@ from qampy_amd import _lib, synth
 from qampy_amd._lib import DeviceArray
 from qampy_amd.core import hip_dsp
 from qampy_amd.pipeline import ResidentReceiver
+from table_cache_check import assert_sequence_matches_fresh_calls
 
 pytestmark = pytest.mark.gpu
 
@@ -124,7 +125,9 @@ def pmd_field(L):
 
 
 @pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("L", [256, 4096, 8192, 8193, 12388])      # whole rows; a partial last block; 12388 = 3 * 4096 + 100: a wrap-around halo too
+# whole rows; a partial last block; 12388 = 3 * 4096 + 100: a wrap-around halo too; 1, 100, 255: rows shorter than the block, the halo wraps round
+# them several times
+@pytest.mark.parametrize("L", [256, 4096, 8192, 8193, 12388, 1, 100, 255])
 def test_pmd_against_restatement(gold, dtype, L):
     x = x_of(gold, L) if L in (4096, 12388) else pmd_field(L)
     th = float(gold["theta"])
@@ -154,6 +157,22 @@ def test_overlap_save_pmd_against_reference(gold, dtype):
     # a delay of whole samples has no tail: the blocks are the reference
     got = dev(lambda E, out: hip_dsp.apply_pmd_dev(E, out, th, 200e-12, FS), x, dtype)
     assert relerr(got[:, gold["cols_200"]], gold["pmd_12388_200"], x) <= BAR[dtype]
+
+
+def test_pmd_table_follows_its_key():
+    """The table of the PMD filter is kept from call to call under the key (N, delay, precision): key A, key B, A again; the other precision
+    in between; the block size of every other row length (L = 300: N = 8192, a larger table that regrows the slot) in between."""
+    th = 0.4
+    for dt, other in ((np.complex64, np.complex128), (np.complex128, np.complex64)):
+        def call(L, dgd, dtype):
+            return lambda: dev(lambda E, out: hip_dsp.apply_pmd_dev(E, out, th, dgd, FS), pmd_field(L), dtype)
+        calls = {"256 a": call(256, 30e-12, dt), "256 b": call(256, 200e-12, dt), "256 a other precision": call(256, 30e-12, other),
+                 "300 a": call(300, 30e-12, dt), "300 b": call(300, 200e-12, dt)}
+        want = assert_sequence_matches_fresh_calls(calls, ["256 a", "256 b", "256 a", "256 a other precision", "256 a", "256 a other precision",
+                                                           "300 a", "256 a", "300 b", "300 a", "256 b"])
+        assert not np.array_equal(want["256 a"], want["256 b"]) and not np.array_equal(want["300 a"], want["300 b"])
+        for L, key in ((256, "256 a"), (300, "300 a")):
+            assert relerr(want[key], ir.pmd(pmd_field(L), th, 30e-12 * FS), pmd_field(L)) <= BAR[dt]
 
 
 def test_pmd_and_rotation_need_two_modes():

@@ -14,6 +14,7 @@ import resample_ref as ref
 from qampy_amd import _lib, synth
 from qampy_amd._lib import DeviceArray
 from qampy_amd.core import resample as rs
+from table_cache_check import assert_sequence_matches_fresh_calls
 
 pytestmark = pytest.mark.gpu
 
@@ -194,6 +195,18 @@ def test_repeat_calls_bit_identical_across_tap_sets():
     assert not np.array_equal(a1, b1) and c1.shape != a1.shape
     assert rel_max(a1, ref.resample(x, h1, 7, 10)) <= 1e-5 and rel_max(b2, ref.resample(x, h2, 7, 10)) <= 1e-5
     assert rel_max(d1, ref.resample(x, h1, 7, 10)) <= 1e-11
+    # the table follows its key (taps, up, precision) on the smallest shapes: tap set A, B, A again; the other precision in between; a larger
+    # table, which regrows the slot, in between - every call gives the bits it gives as the first call after qh_release_scratch
+    x = ref.unit_noise(2, 64, 5).astype(np.complex64)
+    h5, h7, h5b = taps_of(5), taps_of(7), taps_of(5, seed=1)
+    for dt, other in ((np.complex64, np.complex128), (np.complex128, np.complex64)):
+        calls = {"5": lambda: run_dev(x.astype(dt), h5, 2, 1, 2.0), "7": lambda: run_dev(x.astype(dt), h7, 2, 1, 2.0),
+                 "5 other taps": lambda: run_dev(x.astype(dt), h5b, 2, 1, 2.0), "5 other precision": lambda: run_dev(x.astype(other), h5, 2, 1, 2.0),
+                 "5 up 3": lambda: run_dev(x.astype(dt), h5, 3, 1, 3.0), "401": lambda: run_dev(x.astype(dt), h1, 2, 1, 2.0)}
+        want = assert_sequence_matches_fresh_calls(calls, ["5", "7", "5", "5 other taps", "5", "5 other precision", "5", "5 other precision",
+                                                           "5 up 3", "5", "401", "5", "7"])
+        assert not np.array_equal(want["5"], want["7"]) and not np.array_equal(want["5"], want["5 other taps"])
+        assert rel_max(want["5"], ref.resample(x, h5, 2, 1, 2.0)) <= BAR[dt] and rel_max(want["7"], ref.resample(x, h7, 2, 1, 2.0)) <= BAR[dt]
 
 
 def test_bad_arguments_rejected_by_the_library():
