@@ -186,6 +186,12 @@ int qh_apply_filter_c64_dev(const void *E, int nmodes, int64_t L, int os, const 
                             int nsel, void *out);
 int qh_apply_filter_c128_dev(const void *E, int nmodes, int64_t L, int os, const void *wx, int ntaps, const int64_t *modes,
                              int nsel, void *out);
+/* The launch form a call of these sizes takes (is_complex != 0: the complex kernel; elem_real_bytes 4 or 8): output symbols per thread
+ * (*per_thread: 4, or 1 when four rows per thread do not fit the LDS) and per workgroup (*tile), the dynamic LDS of a workgroup (*lds_bytes)
+ * and the workgroups along the selected modes (*grid_y: pairs of modes for the complex kernel, one row each for the real one).  QH_ERR_ARG
+ * exactly when the entry points above refuse the same sizes.  Any pointer may be NULL.  No device needed. */
+int qh_apply_plan(int is_complex, int elem_real_bytes, int nmodes, int os, int ntaps, int nsel, int *per_thread, int *tile, int64_t *lds_bytes,
+                  int *grid_y);
 
 /* ---- bps: blind phase search index ---------------------------------------------------------------------------
  *   E (L,) one mode; testangles (p, A) real with p == 1 (one grid) or p == L (per-symbol grid); symbols (M,)

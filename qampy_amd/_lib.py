@@ -87,6 +87,7 @@ SIGNATURES = {
     "qh_train_equaliser_real_f64": _train_sig(_pd),
     "qh_apply_filter_c64": _APPLY, "qh_apply_filter_c128": _APPLY, "qh_apply_filter_f32": _APPLY, "qh_apply_filter_f64": _APPLY,
     "qh_apply_filter_c64_dev": _APPLY, "qh_apply_filter_c128_dev": _APPLY,
+    "qh_apply_plan": [_i, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i64), C.POINTER(_i)],      # is_complex, elem_real_bytes, nmodes, os, ntaps, nsel, per_thread, tile, lds_bytes, grid_y
     "qh_bps_c64": _BPS, "qh_bps_c128": _BPS, "qh_bps_c64_dev": _BPS, "qh_bps_c128_dev": _BPS,
     "qh_bps_recover_c64_dev": _RECOVER, "qh_bps_recover_c128_dev": _RECOVER,
     "qh_bps_recover_part_c64_dev": _RECOVER + [_i, _i], "qh_bps_recover_part_c128_dev": _RECOVER + [_i, _i],

@@ -175,15 +175,60 @@ __global__ void __launch_bounds__(AP_THREADS) apply_real_kernel(ApplyArgs<R> a)
     }
 }
 
-template <typename T> static int apply_check(int nmodes, int64_t L, int os, int ntaps, const int64_t *modes, int nsel, int nrows_w)
+// The launch plan of a call: outputs per thread, the tile they make, the dynamic LDS of a workgroup and the extent of blockIdx.y.  ONE function
+// per kernel forms it; the argument check, the launch and qh_apply_plan all read that function, so they agree on what fits.
+struct ApplyPlan { int per_thread, tile, grid_y; size_t lds; };
+
+// what both plans ask of the sizes; a size that would not fit the LDS by itself is refused here, before any product is formed
+static int apply_plan_sizes(int nmodes, int os, int ntaps, int nsel)
 {
     QH_REQUIRE(os >= 1, "apply_filter_to_signal: oversampling factor must be larger than 0");
-    QH_REQUIRE(nmodes >= 1 && ntaps >= 1 && L >= 0, "apply_filter_to_signal: bad sizes");
+    QH_REQUIRE(nmodes >= 1 && ntaps >= 1, "apply_filter_to_signal: bad sizes");
     QH_REQUIRE(nsel >= 1 && nsel <= 16, "apply_filter_to_signal: between 1 and 16 modes can be selected");
+    QH_REQUIRE((size_t)nmodes <= AP_LDS_MAX && (size_t)os <= AP_LDS_MAX && (size_t)ntaps <= AP_LDS_MAX,
+               "apply_filter_to_signal: nmodes*(255*os+ntaps) samples exceed the 160 KiB LDS tile");
+    return QH_OK;
+}
+
+// apply_cplx_kernel: the sample rows at their pitch, then room for two rows of paired taps (the packed path stages them; every form asks for it)
+template <typename R> static int apply_cplx_plan(int nmodes, int os, int ntaps, int nsel, ApplyPlan *plan)
+{
+    int rc = apply_plan_sizes(nmodes, os, ntaps, nsel);
+    if (rc) return rc;
+    auto lds_for = [&](int P) { return ((size_t)nmodes * (size_t)ap_pitch(os, ntaps, P) + (size_t)2 * nmodes * (ntaps + 1)) * sizeof(Cx<R>); };
+    QH_REQUIRE(lds_for(1) <= AP_LDS_MAX, "apply_filter_to_signal: nmodes*(255*os+ntaps) samples exceed the 160 KiB LDS tile");
+    plan->per_thread = lds_for(AP_PER_THREAD) <= AP_LDS_MAX ? AP_PER_THREAD : 1;
+    plan->tile = ap_tile(plan->per_thread);
+    plan->lds = lds_for(plan->per_thread);
+    plan->grid_y = nsel == 1 ? 1 : (nsel + 1) / 2;                  // NJ = 1 for one selected mode, pairs (NJ = 2) otherwise
+    return QH_OK;
+}
+
+// apply_real_kernel: the sample rows alone (the taps come through the scalar cache), one selected row per blockIdx.y
+template <typename R> static int apply_real_plan(int nmodes, int os, int ntaps, int nsel, ApplyPlan *plan)
+{
+    int rc = apply_plan_sizes(nmodes, os, ntaps, nsel);
+    if (rc) return rc;
+    auto lds_for = [&](int P) { return (size_t)nmodes * ((size_t)(ap_tile(P) - 1) * os + ntaps) * sizeof(R); };
+    QH_REQUIRE(lds_for(1) <= AP_LDS_MAX, "apply_filter_to_signal: nmodes*(255*os+ntaps) samples exceed the 160 KiB LDS tile");
+    plan->per_thread = lds_for(AP_PER_THREAD) <= AP_LDS_MAX ? AP_PER_THREAD : 1;
+    plan->tile = ap_tile(plan->per_thread);
+    plan->lds = lds_for(plan->per_thread);
+    plan->grid_y = nsel;
+    return QH_OK;
+}
+
+template <typename T> struct ApplyPlanOf { static constexpr auto get = apply_real_plan<T>; };
+template <typename R> struct ApplyPlanOf<Cx<R>> { static constexpr auto get = apply_cplx_plan<R>; };
+
+// the argument check of every entry point: the plan of the element type's kernel (sizes, LDS), then what the plan does not see
+template <typename T> static int apply_check(int nmodes, int64_t L, int os, int ntaps, const int64_t *modes, int nsel, int nrows_w, ApplyPlan *plan)
+{
+    int rc = ApplyPlanOf<T>::get(nmodes, os, ntaps, nsel, plan);
+    if (rc) return rc;
+    QH_REQUIRE(L >= 0, "apply_filter_to_signal: bad sizes");
     for (int j = 0; j < nsel; j++)
         QH_REQUIRE(modes[j] >= 0 && modes[j] < nrows_w, "apply_filter_to_signal: largest mode number is larger than shape of taps");
-    const size_t lds = ((size_t)nmodes * ((size_t)(ap_tile(1) - 1) * os + ntaps + 2) + (size_t)2 * nmodes * (ntaps + 1)) * sizeof(T);
-    QH_REQUIRE(lds <= AP_LDS_MAX, "apply_filter_to_signal: nmodes*(255*os+ntaps) samples exceed the 160 KiB LDS tile");
     return QH_OK;
 }
 
@@ -192,24 +237,24 @@ template <typename R> int apply_cplx_dev(const void *E, int nmodes, int64_t L, i
 {
     int rc = ensure_init();
     if (rc) return rc;
-    if ((rc = apply_check<Cx<R>>(nmodes, L, os, ntaps, modes, nsel, nmodes))) return rc;
+    ApplyPlan plan;
+    if ((rc = apply_check<Cx<R>>(nmodes, L, os, ntaps, modes, nsel, nmodes, &plan))) return rc;
     const int64_t N = (L - ntaps + 1) / os;
     if (N <= 0) return QH_OK;
     ApplyArgs<Cx<R>> a;
     a.E = (const Cx<R> *)E; a.wx = (const Cx<R> *)wx; a.out = (Cx<R> *)out; a.L = L; a.N = N;
     a.nmodes = nmodes; a.ntaps = ntaps; a.os = os; a.nsel = nsel;
     for (int j = 0; j < 16; j++) a.modes[j] = j < nsel ? modes[j] : 0;
-    auto lds_for = [&](int P) { return ((size_t)nmodes * (size_t)ap_pitch(os, ntaps, P) + (size_t)2 * nmodes * (ntaps + 1)) * sizeof(Cx<R>); };   // sample rows + paired taps
-    const int P = lds_for(AP_PER_THREAD) <= AP_LDS_MAX ? AP_PER_THREAD : 1;
-    const size_t lds = lds_for(P);
-    const unsigned ntile = (unsigned)((N + ap_tile(P) - 1) / ap_tile(P));
-#define QH_AP_LAUNCH(NJ, PP, GY)                                                                                                     \
+    const int P = plan.per_thread;
+    const size_t lds = plan.lds;
+    const unsigned ntile = (unsigned)((N + plan.tile - 1) / plan.tile);
+#define QH_AP_LAUNCH(NJ, PP)                                                                                                         \
     do {                                                                                                                             \
-        if (lds > 64 * 1024) QH_HIP(hipFuncSetAttribute((const void *)apply_cplx_kernel<R, NJ, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((apply_cplx_kernel<R, NJ, PP>), dim3(ntile, GY), dim3(AP_THREADS), lds, g_stream, a);                      \
+        if ((rc = dyn_lds(apply_cplx_kernel<R, NJ, PP>, lds))) return rc;                                                            \
+        hipLaunchKernelGGL((apply_cplx_kernel<R, NJ, PP>), dim3(ntile, plan.grid_y), dim3(AP_THREADS), lds, g_stream, a);           \
     } while (0)
-    if (nsel == 1) { if (P == 1) QH_AP_LAUNCH(1, 1, 1); else QH_AP_LAUNCH(1, AP_PER_THREAD, 1); }
-    else { if (P == 1) QH_AP_LAUNCH(2, 1, (nsel + 1) / 2); else QH_AP_LAUNCH(2, AP_PER_THREAD, (nsel + 1) / 2); }
+    if (nsel == 1) { if (P == 1) QH_AP_LAUNCH(1, 1); else QH_AP_LAUNCH(1, AP_PER_THREAD); }
+    else { if (P == 1) QH_AP_LAUNCH(2, 1); else QH_AP_LAUNCH(2, AP_PER_THREAD); }
 #undef QH_AP_LAUNCH
     QH_HIP(hipGetLastError());
     return QH_OK;
@@ -220,23 +265,22 @@ template <typename R> int apply_real_dev(const void *E, int nmodes, int64_t L, i
 {
     int rc = ensure_init();
     if (rc) return rc;
-    if ((rc = apply_check<R>(nmodes, L, os, ntaps, modes, nsel, nmodes))) return rc;
+    ApplyPlan plan;
+    if ((rc = apply_check<R>(nmodes, L, os, ntaps, modes, nsel, nmodes, &plan))) return rc;
     const int64_t N = (L - ntaps + 1) / os;
     if (N <= 0) return QH_OK;
     ApplyArgs<R> a;
     a.E = (const R *)E; a.wx = (const R *)wx; a.out = (R *)out; a.L = L; a.N = N;
     a.nmodes = nmodes; a.ntaps = ntaps; a.os = os; a.nsel = nsel;
     for (int j = 0; j < 16; j++) a.modes[j] = j < nsel ? modes[j] : 0;
-    auto lds_for = [&](int P) { return (size_t)nmodes * ((size_t)(ap_tile(P) - 1) * os + ntaps) * sizeof(R); };
-    const int P = lds_for(AP_PER_THREAD) <= AP_LDS_MAX ? AP_PER_THREAD : 1;
-    const size_t lds = lds_for(P);
-    const unsigned ntile = (unsigned)((N + ap_tile(P) - 1) / ap_tile(P));
-    if (P == 1) {
-        if (lds > 64 * 1024) QH_HIP(hipFuncSetAttribute((const void *)apply_real_kernel<R, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((apply_real_kernel<R, 1>), dim3(ntile, nsel), dim3(AP_THREADS), lds, g_stream, a);
+    const size_t lds = plan.lds;
+    const unsigned ntile = (unsigned)((N + plan.tile - 1) / plan.tile);
+    if (plan.per_thread == 1) {
+        if ((rc = dyn_lds(apply_real_kernel<R, 1>, lds))) return rc;
+        hipLaunchKernelGGL((apply_real_kernel<R, 1>), dim3(ntile, plan.grid_y), dim3(AP_THREADS), lds, g_stream, a);
     } else {
-        if (lds > 64 * 1024) QH_HIP(hipFuncSetAttribute((const void *)apply_real_kernel<R, AP_PER_THREAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((apply_real_kernel<R, AP_PER_THREAD>), dim3(ntile, nsel), dim3(AP_THREADS), lds, g_stream, a);
+        if ((rc = dyn_lds(apply_real_kernel<R, AP_PER_THREAD>, lds))) return rc;
+        hipLaunchKernelGGL((apply_real_kernel<R, AP_PER_THREAD>), dim3(ntile, plan.grid_y), dim3(AP_THREADS), lds, g_stream, a);
     }
     QH_HIP(hipGetLastError());
     return QH_OK;
@@ -248,7 +292,8 @@ static int apply_host(F devfn, const void *E, int nmodes, int64_t L, int os, con
 {
     int rc = ensure_init();
     if (rc) return rc;
-    if ((rc = apply_check<T>(nmodes, L, os, ntaps, modes, nsel, nmodes))) return rc;
+    ApplyPlan plan;
+    if ((rc = apply_check<T>(nmodes, L, os, ntaps, modes, nsel, nmodes, &plan))) return rc;
     const int64_t N = (L - ntaps + 1) / os;
     if (N <= 0) return QH_OK;
     DevBuf dE, dw, dout;
@@ -264,6 +309,19 @@ static int apply_host(F devfn, const void *E, int nmodes, int64_t L, int os, con
 }  // namespace qh
 
 extern "C" {
+int qh_apply_plan(int is_complex, int elem_real_bytes, int nmodes, int os, int ntaps, int nsel, int *per_thread, int *tile, int64_t *lds_bytes, int *grid_y)
+{
+    QH_REQUIRE(elem_real_bytes == 4 || elem_real_bytes == 8, "apply_plan: the real type has 4 or 8 bytes");
+    qh::ApplyPlan p;
+    const int rc = is_complex ? (elem_real_bytes == 4 ? qh::apply_cplx_plan<float>(nmodes, os, ntaps, nsel, &p) : qh::apply_cplx_plan<double>(nmodes, os, ntaps, nsel, &p))
+                              : (elem_real_bytes == 4 ? qh::apply_real_plan<float>(nmodes, os, ntaps, nsel, &p) : qh::apply_real_plan<double>(nmodes, os, ntaps, nsel, &p));
+    if (rc) return rc;
+    if (per_thread) *per_thread = p.per_thread;
+    if (tile) *tile = p.tile;
+    if (lds_bytes) *lds_bytes = (int64_t)p.lds;
+    if (grid_y) *grid_y = p.grid_y;
+    return QH_OK;
+}
 int qh_apply_filter_c64_dev(const void *E, int nmodes, int64_t L, int os, const void *wx, int ntaps, const int64_t *modes, int nsel, void *out)
 { return qh::apply_cplx_dev<float>(E, nmodes, L, os, wx, ntaps, modes, nsel, out); }
 int qh_apply_filter_c128_dev(const void *E, int nmodes, int64_t L, int os, const void *wx, int ntaps, const int64_t *modes, int nsel, void *out)
