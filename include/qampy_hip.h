@@ -917,6 +917,35 @@ int qh_tdh_metrics_c64_dev(const void *E, int nmodes, int64_t L, int fM, int fM1
 int qh_tdh_metrics_c128_dev(const void *E, int nmodes, int64_t L, int fM, int fM1, double powratio, const int32_t *shift_dev, int shift_host,
                             const int32_t *idx_tx, const void *alphabet1, int M1, const void *alphabet2, int M2, double *sums);
 
+/* ---- nonlinear fibre (csrc/fibre.hip): symmetric split-step Fourier propagation of the (Manakov) nonlinear Schroedinger equation
+ * over nspans identical amplified spans, and digital back-propagation.  E, out (nmodes, L) device pointers, out may be E; nmodes 1 (kappa = 1) or
+ * 2 (kappa = 8 / 9); L a length qh_fft_*_dev takes.  dz: HOST table of the nsteps step lengths of one span in metres; f = fftfreq(L, 1 / fs);
+ * beta2 in s^2 / m (add_dispersion's D wl0^2 / (2 pi c)), gamma in 1 / (W m), alpha in 1 / m.
+ *   D(h)  every row becomes ifft(exp(-2 pi i t) . fft(row)), t = pi beta2 h f^2 turns, formed and reduced modulo one in double: exp(-0.5j w^2 beta2 h)
+ *   N(h)  P[n] = sum_m |E[m, n]|^2, E[m, n] <- a exp(+j kappa gamma pscale h_eff P[n]) E[m, n], h_eff = (1 - exp(-alpha h)) / alpha (h for
+ *         alpha == 0), a = exp(-alpha h / 2); the phase and the rotator are formed in the field's real type
+ *   span  D(dz[0] / 2), then for i = 0 .. nsteps - 1: N(dz[i]), D(dz[i] / 2 + dz[i + 1] / 2), the last one D(dz[nsteps - 1] / 2): nsteps point-wise
+ *         launches and nsteps + 1 filters (qh_spectral_filter_*_dev, kind 6); half steps are merged inside a span, never across spans
+ * amplify != 0: the last N of a span also multiplies by exp(+alpha span / 2), span = sum dz: the lumped amplifier.  ase_w > 0 (watts per mode,
+ * forward only): that launch then adds sigma w[m, n], sigma^2 = ase_w / pscale, w the unit noise of qh_impair_pointwise_*_dev (noise_mode 1,
+ * sigma 1) under the seed `seed + s` (modulo 2^64) for span s.  pscale, watts per unit of |E|^2, is fixed once at the start and stays on the
+ * device: power_mode 0: pscale = power; 1: pscale = power / sum_m mean_n |E[m, n]|^2, power the launch power over all rows in watts (two
+ * launches, double, fixed order).  The field's normalisation is never changed.
+ * backward != 0: the algebraic inverse of the noise-free forward call with the same arguments - steps reversed, beta2, gamma and alpha negated,
+ * with amplify the factor exp(-alpha span / 2) in front of the first N of a span, before its power is taken.
+ * QH_ERR_ARG before any launch: nmodes not 1 or 2, a length the transforms do not take, nsteps or nspans outside 1 .. 4096, a step that is not
+ * finite and positive, a non-finite parameter, fs <= 0, ase_w < 0, ase_w != 0 with backward, power <= 0.  The whole loop is enqueued on the current
+ * stream, nothing is read back, no atomics: a repeated call is bit-identical. */
+int qh_fibre_ssfm_c64_dev(const void *E, int nmodes, int64_t L, double fs, double beta2, double gamma, double alpha, const double *dz, int nsteps,
+                          int nspans, int backward, int amplify, int power_mode, double power, double ase_w, uint64_t seed, void *out);
+int qh_fibre_ssfm_c128_dev(const void *E, int nmodes, int64_t L, double fs, double beta2, double gamma, double alpha, const double *dz, int nsteps,
+                           int nspans, int backward, int amplify, int power_mode, double power, double ase_w, uint64_t seed, void *out);
+/* The nonlinear step of the above on its own, one launch: out[m, n] = a exp(+j coef pscale[0] P[n]) E[m, n] (+ sigma w[m, n] when sigma_w > 0,
+ * sigma = sigma_w / sqrt(pscale[0]), w as above under `seed`), P[n] = sum_m |E[m, n]|^2; pscale: one double in DEVICE memory.  nmodes 1 or 2,
+ * 1 <= L <= 2^24; out may be E. */
+int qh_fibre_nl_c64_dev(const void *E, int nmodes, int64_t L, double a, double coef, const double *pscale, double sigma_w, uint64_t seed, void *out);
+int qh_fibre_nl_c128_dev(const void *E, int nmodes, int64_t L, double a, double coef, const double *pscale, double sigma_w, uint64_t seed, void *out);
+
 #ifdef __cplusplus
 }
 #endif

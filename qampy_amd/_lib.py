@@ -48,6 +48,8 @@ _LUT_ACC = [_vp, _vp, _i, _i64, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp]         
 _DAC_TABLE = [_i64, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _i, _vp]           # sim_len, fb, fs, beta, noise, sos (host), nsec, p_f
 _TDH_ASSEMBLE = [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, C.c_double, _vp, _vp]                # part1, part2, lab1, lab2, nmodes, nframes, fM, fM1, powratio, out, idx_out
 _TDH_ROWS = [_vp, _i, _i64, _i, _i, C.c_double, _vp, _i]                                    # E, nmodes, L, fM, fM1, powratio, shift_dev, shift_host
+# E, nmodes, L, fs, beta2, gamma, alpha, dz (host), nsteps, nspans, backward, amplify, power_mode, power, ase_w, seed, out
+_FIBRE = [_vp, _i, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.c_uint64, _vp]
 
 
 def _train_sig(mu_ptr, dev=False):
@@ -208,6 +210,9 @@ SIGNATURES = {
     "qh_tdh_align_dev": [_vp, _i, _i, _i, _i, _vp],                                                                                             # sums, nmodes, fM, fM1, high_first, shift
     "qh_tdh_split_c64_dev": _TDH_ROWS + [_vp, _vp], "qh_tdh_split_c128_dev": _TDH_ROWS + [_vp, _vp],                                            # ..., part1, part2
     "qh_tdh_metrics_c64_dev": _TDH_ROWS + [_vp, _vp, _i, _vp, _i, _vp], "qh_tdh_metrics_c128_dev": _TDH_ROWS + [_vp, _vp, _i, _vp, _i, _vp],    # ..., idx_tx, alphabet1, M1, alphabet2, M2, sums
+    "qh_fibre_ssfm_c64_dev": _FIBRE, "qh_fibre_ssfm_c128_dev": _FIBRE,
+    "qh_fibre_nl_c64_dev": [_vp, _i, _i64, C.c_double, C.c_double, _vp, C.c_double, C.c_uint64, _vp],                                           # E, nmodes, L, a, coef, pscale (device), sigma_w, seed, out
+    "qh_fibre_nl_c128_dev": [_vp, _i, _i64, C.c_double, C.c_double, _vp, C.c_double, C.c_uint64, _vp],
 }
 
 PIT_MAXPASS, PIT_MAXCHUNK = 24, 32

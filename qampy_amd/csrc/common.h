@@ -83,6 +83,7 @@ enum class Slot : int {
     PRECOMP,             // tile maxima and scales of the pattern table, tile sums of the DAC pre-emphasis (precomp.hip)
     BLIND,               // workgroup partials of the blind moments, distance sums and QPSK sums (blind.hip)
     HYBRID,              // tile sums of the frame classes, workgroup partials of the hybrid metrics (hybrid.hip)
+    FIBRE,               // power partials, pscale and the two dispersion tables of the split-step propagation (fibre.hip)
     COUNT
 };
 int scratch(Slot slot, size_t bytes, void **p);  // grow-only device scratch of the calling thread

@@ -69,3 +69,12 @@ def sim_mod_response(sig, dcbias=1, gfactr=1, cfactr=0, dcbias_out=0.5, gfactr_o
     """Response of an IQ modulator to a signal object: see :func:`qampy_amd.core.impairments.modulator_response`."""
     return sig.recreate_from_np_array(_core.modulator_response(sig, dcbias=dcbias, gfactr=gfactr, cfactr=cfactr, dcbias_out=dcbias_out,
                                                                gfactr_out=gfactr_out))
+
+
+def simulate_fibre(sig, D, span_length, nspans=1, gamma=1.3e-3, alpha_db_km=0.2, steps=8, power_dbm=None, pscale=None, amplify=True, nf_db=None,
+                   wl0=1550e-9, seed=None):
+    """``nspans`` amplified spans of nonlinear fibre on a signal object at its own ``fs`` (split-step Fourier, Manakov for two modes): see
+    :func:`qampy_amd.core.fibre.ssfm`."""
+    from .core import fibre as _fibre
+    return sig.recreate_from_np_array(_fibre.ssfm(sig, sig.fs, D, span_length, nspans=nspans, gamma=gamma, alpha_db_km=alpha_db_km, steps=steps,
+                                                  power_dbm=power_dbm, pscale=pscale, amplify=amplify, nf_db=nf_db, wl0=wl0, seed=seed))

@@ -258,6 +258,25 @@ class ResidentReceiver:
         buf.copy_from(self._cd_buf)
         self._capture_written(next_capture)
 
+    def backpropagate(self, fs, D, span_length, nspans, gamma, alpha_db_km, steps, power_dbm, amplify=True, wl0=1550e-9, next_capture=False):
+        """Take ``nspans`` spans of nonlinear fibre out of the loaded capture in HBM (``self.E``, or ``self.E_next`` with ``next_capture``): the
+        nonlinear counterpart of ``compensate_cd``, :func:`qampy_amd.core.hip_dsp.dbp_dev` in place on the capture buffer, enqueued on stream 0
+        between ``load()`` / ``load_next()`` and ``run()``.  The arguments are those of the link as ``hip_dsp.ssfm_dev`` takes them; ``power_dbm``
+        is the launch power over all modes, which is the power of the capture when every span ends in its amplifier; fewer ``steps`` than the
+        link, or a scaled ``gamma``, give the usual practical back-propagation.  One or two modes, and a row length csrc/fft.hip takes:
+        ValueError otherwise, before a launch.  The filters are all-pass and the Kerr term is a phase; with ``amplify`` the scalars of a span
+        multiply to one, so the power ``load()`` read for tier b's acquisition rule is still the capture's power.  With ``amplify=False`` the
+        power grows by the loss of the link, ``exp(alpha span_length nspans)``, which is known on the host: tier b's rule is given the new
+        power without a read-back (not with ``next_capture``, as in ``impair``)."""
+        buf = self._capture_to_write(next_capture)
+        _dsp.dbp_dev(buf, buf, fs, D, span_length, nspans=nspans, gamma=gamma, alpha_db_km=alpha_db_km, steps=steps, power_dbm=power_dbm, amplify=amplify,
+                     wl0=wl0)
+        if not amplify and self._load_power is not None and not next_capture:
+            self._load_power *= float(np.exp(_dsp.fibre_alpha(alpha_db_km) * float(span_length) * int(nspans)))
+            self._capture_written(power=self._load_power)
+        else:
+            self._capture_written(next_capture)
+
     def frontend(self, orthonormalize=True, skew=None, sampling_rate=None, pre_filter_bw=None, next_capture=False):
         """Condition the loaded capture in HBM (``self.E``, or ``self.E_next`` with ``next_capture``) as the analog front end does, between
         ``load()`` / ``load_next()`` and the other compensations, enqueued on stream 0: first the skew between the rails - ``skew=(delay_i,
