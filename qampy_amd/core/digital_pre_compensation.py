@@ -13,7 +13,7 @@ from .impairments import _on_device, _rows, clipper         # noqa: F401  (clipp
 def comp_mod_sin(sig, vpi=1.14):
     """Undo the modulator's sine: ``2 vpi.real arcsin(sig.real) + 1j 2 vpi.imag arcsin(sig.imag)``; a ``vpi`` that is not complex serves both
     rails.  NaN in a rail whose input lies outside [-1, 1], as numpy gives.  complex64 and complex128 keep their dtype."""
-    _dsp._vpi_rails(vpi)
+    _dsp.precomp._vpi_rails(vpi)
     return _on_device(sig, lambda E, out: _dsp.comp_mod_sin_dev(E, out, vpi=vpi))
 
 
@@ -95,7 +95,7 @@ def apply_lut(sig, ea, idx_I, idx_Q, gain=1.0):
         raise ValueError("idx_I and idx_Q hold one whole number per sample of sig")
     if min(a.min(), b.min()) < 0 or max(a.max(), b.max()) >= T.shape[1]:
         raise ValueError("a pattern number lies outside the table")
-    _dsp._precomp_gain(gain, "apply_lut")
+    _dsp.precomp._precomp_gain(gain, "apply_lut")
     D = _lib.DeviceArray
     E = D.from_host(X)
     _dsp.lut_apply_dev(E, D.from_host(T), D.from_host(a.astype(np.int32)), D.from_host(b.astype(np.int32)), E, gain=gain)

@@ -18,8 +18,8 @@ def _check(sig, fs, D, span_length, nspans, gamma, alpha_db_km, steps, power_dbm
         raise ValueError("the fibre takes one row, or two (Manakov), not %d" % X.shape[0])
     if X.size:
         _dsp.fft_plan(X.shape[1])
-    _dsp._fibre_steps(steps, span_length)
-    _dsp._fibre_spans(nspans)
+    _dsp.fibre._fibre_steps(steps, span_length)
+    _dsp.fibre._fibre_spans(nspans)
     if (power_dbm is None) == (pscale is None):
         raise ValueError("give exactly one of power_dbm (the launch power over all rows) and pscale (watts per unit of |E|**2)")
     if not all(np.isfinite(float(v)) for v in (fs, D, gamma, alpha_db_km, wl0)) or not float(fs) > 0:

@@ -108,7 +108,7 @@ def add_modal_delay(sig, delay):
     x = np.asarray(sig)
     if x.ndim != 2:
         raise ValueError("add_modal_delay needs a 2-d signal")
-    _dsp._delays(delay, x.shape[0])
+    _dsp.impair._delays(delay, x.shape[0])
     return _on_device(sig, lambda E, out: _dsp.modal_delay_dev(E, out, delay), inplace=False)
 
 
@@ -125,7 +125,7 @@ def simulate_transmission(sig, fb, fs, snr=None, freq_off=None, lwdth=None, dgd=
     if (modal_delay is not None or dgd is not None) and x.ndim != 2:
         raise ValueError("the modal delay and PMD need a 2-d signal")
     if modal_delay is not None:
-        _dsp._delays(modal_delay, x.shape[0])
+        _dsp.impair._delays(modal_delay, x.shape[0])
     return _on_device(sig, lambda E, out: _dsp.simulate_transmission_dev(E, out, fb, fs, snr=snr, freq_off=freq_off, lwdth=lwdth, dgd=dgd, theta=theta,
                                                                          modal_delay=modal_delay, seed=seed))
 
@@ -179,7 +179,7 @@ def quantize_signal_New(sig_in, nbits=6, rescale_in=True, rescale_out=True):
     complex.  Other values of ``rescale_in`` / ``rescale_out`` are not implemented."""
     if not (rescale_in and rescale_out):
         raise NotImplementedError("quantize_signal_New runs with rescale_in=True and rescale_out=True only")
-    _dsp._dac_stages(1, nbits, 0)
+    _dsp.txresp._dac_stages(1, nbits, 0)
     if np.isclose(float(nbits), 0):
         raise ValueError("nbits must be a whole number from 1 to 16")
     return _recreate(sig_in, _on_device(sig_in, lambda E, out: _dsp.dac_pointwise_dev(E, out, quant_bits=nbits)))
@@ -190,7 +190,7 @@ def apply_enob_as_awgn(sig, enob, verbose=False, seed=None):
     ``x_max`` the largest ``|re|`` or ``|im|`` over all modes, read on the device.  ``verbose``: also the SNR in dB that corresponds to the
     ENOB, ``10 log10(mean |sig|**2 / 2 / (delta**2 / 12))``, computed on the host.  Real input is promoted to complex128."""
     seed = _fresh_seed(seed)
-    _dsp._dac_stages(1, 0, enob)
+    _dsp.txresp._dac_stages(1, 0, enob)
     out = _on_device(sig, lambda E, o: _dsp.dac_pointwise_dev(E, o, enob=enob, seed=seed))
     if not verbose:
         return out
@@ -211,9 +211,9 @@ def sim_DAC_response(sig, fs, enob=5, clip_rat=1, quant_bits=0, seed=None, **dac
     """Clip, quantise, add ENOB noise and - if any ``dac_params`` are given - low-pass: ``sim_DAC_response`` of the reference on the device
     (:func:`qampy_amd.core.hip_dsp.sim_dac_response_dev`).  Real input is promoted to complex128."""
     seed = _fresh_seed(seed)
-    _dsp._dac_stages(clip_rat, quant_bits, enob)
-    if _dsp._dac_filter(dac_params) is not None:
-        _dsp.design_lowpass_sos(fs, _dsp._dac_filter(dac_params), "bessel", 2)
+    _dsp.txresp._dac_stages(clip_rat, quant_bits, enob)
+    if _dsp.txresp._dac_filter(dac_params) is not None:
+        _dsp.design_lowpass_sos(fs, _dsp.txresp._dac_filter(dac_params), "bessel", 2)
     return _on_device(sig, lambda E, out: _dsp.sim_dac_response_dev(E, out, fs, enob=enob, clip_rat=clip_rat, quant_bits=quant_bits, seed=seed, **dac_params))
 
 
@@ -227,21 +227,21 @@ def ideal_amplifier_response(sig, out_volt):
 def modulator_response(rfsig, dcbias=1, gfactr=1, cfactr=0, dcbias_out=0.5, gfactr_out=1):
     """Response of an IQ modulator to the drive voltages ``rfsig`` (I in the real part, Q in the imaginary part, in fractions of Vpi):
     ``modulator_response`` of the reference on the device.  Real input is promoted to complex128."""
-    _dsp._mod_params(dcbias, gfactr, cfactr, dcbias_out, gfactr_out)
+    _dsp.txresp._mod_params(dcbias, gfactr, cfactr, dcbias_out, gfactr_out)
     return _on_device(rfsig, lambda E, out: _dsp.modulator_response_dev(E, out, dcbias=dcbias, gfactr=gfactr, cfactr=cfactr, dcbias_out=dcbias_out,
                                                                          gfactr_out=gfactr_out))
 
 
-def sim_tx_response(sig, fs, enob=6, tgt_v=1, clip_rat=1, quant_bits=0, dac_params=_dsp._DAC_DEFAULT, seed=None, **mod_prms):
+def sim_tx_response(sig, fs, enob=6, tgt_v=1, clip_rat=1, quant_bits=0, dac_params=_dsp.txresp._DAC_DEFAULT, seed=None, **mod_prms):
     """A transmitter: DAC (clip, quantise, ENOB noise, Bessel low-pass), ideal amplifier to ``tgt_v`` (fractions of Vpi) and IQ modulator -
     ``sim_tx_response`` of the reference in one visit to the device (:func:`qampy_amd.core.hip_dsp.sim_tx_response_dev`).  Real input is
     promoted to complex128."""
     seed = _fresh_seed(seed)
-    _dsp._dac_stages(clip_rat, quant_bits, enob)
-    _dsp._mod_params(**mod_prms)
+    _dsp.txresp._dac_stages(clip_rat, quant_bits, enob)
+    _dsp.txresp._mod_params(**mod_prms)
     if not np.isfinite(float(tgt_v)):
         raise ValueError("tgt_v must be finite")
-    if _dsp._dac_filter(dac_params) is not None:
-        _dsp.design_lowpass_sos(fs, _dsp._dac_filter(dac_params), "bessel", 2)
+    if _dsp.txresp._dac_filter(dac_params) is not None:
+        _dsp.design_lowpass_sos(fs, _dsp.txresp._dac_filter(dac_params), "bessel", 2)
     return _on_device(sig, lambda E, out: _dsp.sim_tx_response_dev(E, out, fs, enob=enob, tgt_v=tgt_v, clip_rat=clip_rat, quant_bits=quant_bits,
                                                                    dac_params=dac_params, seed=seed, **mod_prms))

@@ -53,7 +53,7 @@ def _host_stats(row, M):
 
 def _dev_stats(rows, M):
     """The rows uploaded once and their device stats ``(nrows, 6)`` on the host."""
-    _dsp._blind_M("blind signal quality", M)
+    _dsp.blind._blind_M("blind signal quality", M)
     dE = _lib.DeviceArray.from_host(np.ascontiguousarray(rows))
     stats = _dsp.blind_stats_dev(dE, M)
     return dE, stats, stats.to_host().reshape(rows.shape[0], 6)

@@ -52,7 +52,7 @@ def simulate_transmission(sig, snr=None, freq_off=None, lwdth=None, dgd=None, th
     return out
 
 
-def sim_tx_response(sig, enob=6, tgt_v=1, clip_rat=1, quant_bits=0, dac_params=_core._dsp._DAC_DEFAULT, seed=None, **mod_prms):
+def sim_tx_response(sig, enob=6, tgt_v=1, clip_rat=1, quant_bits=0, dac_params=_core._dsp.txresp._DAC_DEFAULT, seed=None, **mod_prms):
     """A transmitter - DAC, ideal amplifier to ``tgt_v``, IQ modulator - on a signal object at its own ``fs``: see
     :func:`qampy_amd.core.impairments.sim_tx_response`."""
     return sig.recreate_from_np_array(_core.sim_tx_response(sig, sig.fs, enob=enob, tgt_v=tgt_v, clip_rat=clip_rat, quant_bits=quant_bits,

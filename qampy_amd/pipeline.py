@@ -34,7 +34,7 @@ def _blind_metrics(rows, M, block, ws):
     """The blind estimators of hip_dsp on the rows of one DeviceArray: what ``blind_metrics`` of a receiver and of a bank return.  ``ws``: the
     caller's dict of work buffers, made again when the shape or the block changes."""
     nrows, N = rows.shape
-    block, nblocks = _dsp._blind_block("blind_metrics", block, N)
+    block, nblocks = _dsp.blind._blind_block("blind_metrics", block, N)
     key = (nrows, N, block)
     if ws.get("key") != key:
         ws.clear()
@@ -294,7 +294,7 @@ class ResidentReceiver:
                 raise ValueError("skew is (delay_i, delay_q) in seconds")
             if sampling_rate is None:
                 raise ValueError("skew needs the sampling_rate of the capture")
-            _dsp._skew_step(self.L, sampling_rate)
+            _dsp.frontend._skew_step(self.L, sampling_rate)
         if pre_filter_bw is not None:
             _dsp.pre_filter_bins(self.L, float(pre_filter_bw))
         if skew is not None or pre_filter_bw is not None:

@@ -263,7 +263,7 @@ def make_tdh_symbols_dev(M, nsym, fr, nmodes=2, order=(15, 23), seed=(None, None
     from ._lib import DeviceArray
     from .core import hip_dsp
     fM, fM1, fM2 = hip_dsp.tdh_geometry(fr)
-    hip_dsp._tdh_frame("make_tdh_symbols_dev", fM, fM1)
+    hip_dsp.hybrid._tdh_frame("make_tdh_symbols_dev", fM, fM1)
     nframes = int(nsym) // fM
     if nframes < 1:
         raise ValueError("make_tdh_symbols_dev: at least one frame of %d symbols" % fM)

@@ -298,7 +298,7 @@ def sim_mi_mc(symbols, snr, N, seed=None):
     if M & (M - 1) == 0 and 2 <= M <= 1024:
         mi = hip_dsp.awgn_mc(sy, lin, N, seed=seed)[:, 1]
     else:
-        lin = hip_dsp._mc_snr(lin, "sim_mi_mc")
+        lin = hip_dsp.theory._mc_snr(lin, "sim_mi_mc")
         z = hip_dsp.awgn_mc_noise_dev(_lib.DeviceArray((lin.size, int(N)), sy.dtype), lin, seed).to_host()
         mi = np.array([hip_dsp.cal_mi_mc(z[p], sy, 1 / lin[p]) for p in range(lin.size)])
     return float(mi[0]) if snr_db.ndim == 0 else mi

@@ -84,7 +84,7 @@ def main():
             return median_ms(lambda: _lib.call("qh_memcpy_d2d", fill_dst.ptr, fill_src.ptr, moved // 2))          # moved: half read, half written
 
         def evm_launches(order):
-            _lib.call("qh_blind_evm_%s_dev" % ("c64" if cb == 8 else "c128"), E.ptr, nm, N, stats.ptr, hip_dsp._blind_alphabet_dev(order, dtype).ptr, order,
+            _lib.call("qh_blind_evm_%s_dev" % ("c64" if cb == 8 else "c128"), E.ptr, nm, N, stats.ptr, hip_dsp.blind._blind_alphabet_dev(order, dtype).ptr, order,
                       None, None, evm_sum.ptr)
 
         hip_dsp.blind_stats_dev(E, M, stats=stats, mom=mom)

@@ -209,7 +209,7 @@ def test_valid_calls_reach_the_library_with_the_abi_arguments(monkeypatch):
     seen = []
     monkeypatch.setattr(_lib, "call", lambda name, *a: seen.append((name,) + a))
     monkeypatch.setattr(_lib.DeviceArray, "from_host", classmethod(lambda cls, arr: _Stub(arr.shape, arr.dtype, 77)))
-    monkeypatch.setattr(hip_dsp, "_PILOT_TABLES", threading.local())          # (the stand-in tables must not outlive this test)
+    monkeypatch.setattr(hip_dsp.pilot, "_PILOT_TABLES", threading.local())          # (the stand-in tables must not outlive this test)
     c = np.complex64
     hip_dsp.pilot_frame_dev(_Stub((2, 11), c, 10), _Stub((2, 63), c, 20), 32, 4, 4, 3, _Stub((2, 96), c, 30), pilot_scale=1.5, repeat_data=False,
                             labels=_Stub((2, 63), np.int32, 40), idx_frame=_Stub((2, 96), np.int32, 50))

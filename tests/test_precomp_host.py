@@ -158,7 +158,7 @@ def test_comp_mod_sin_checks_its_arguments(no_library):
         hip_dsp.comp_mod_sin_dev(x, _Stub((2, 8), c))
     with pytest.raises(TypeError):
         hip_dsp.comp_mod_sin_dev(_Stub((2, 9), np.float64), _Stub((2, 9), np.float64))
-    assert hip_dsp._vpi_rails(1.14) == (1.14, 1.14) and hip_dsp._vpi_rails(1.2 + 0.9j) == (1.2, 0.9) and hip_dsp._vpi_rails(1.2 + 0j) == (1.2, 0.0)
+    assert hip_dsp.precomp._vpi_rails(1.14) == (1.14, 1.14) and hip_dsp.precomp._vpi_rails(1.2 + 0.9j) == (1.2, 0.9) and hip_dsp.precomp._vpi_rails(1.2 + 0j) == (1.2, 0.0)
     with pytest.raises(ValueError):
         dpc.comp_mod_sin(np.zeros(4, complex), vpi=np.nan)
 
@@ -180,7 +180,7 @@ def test_the_dac_table_checks_its_arguments(no_library):
         hip_dsp.dac_preemphasis_dev(_Stub((2, 1), np.complex64), _Stub((2, 1), np.complex64), 20e9, 0.1)          # no transform of one sample
     with pytest.raises(ValueError):
         hip_dsp.dac_preemphasis_dev(_Stub((2, 256), np.complex64), _Stub((2, 256), np.complex64), 20e9, 0.1, table=_Stub((255,), np.complex64))
-    fb, fs, beta, noise, sos = hip_dsp._dac_preemphasis_args(20e9, 256, 0.1, 9, (16e9, 2, "sos", 6), 2)
+    fb, fs, beta, noise, sos = hip_dsp.precomp._dac_preemphasis_args(20e9, 256, 0.1, 9, (16e9, 2, "sos", 6), 2)
     assert (fb, fs, beta) == (20e9, 40e9, 0.1) and sos.shape == (1, 6) and noise == 10 ** 0.9 / (6 * 20e9 * 2 ** 12)
 
 
@@ -230,13 +230,13 @@ def test_the_level_tables_live_as_long_as_their_levels(monkeypatch):
             calls.append([live[p] for p in ptrs])
     monkeypatch.setattr(_lib, "call", call)
     monkeypatch.setattr(_lib.DeviceArray, "from_host", classmethod(from_host))
-    monkeypatch.setattr(hip_dsp, "_PILOT_TABLES", threading.local())
+    monkeypatch.setattr(hip_dsp.pilot, "_PILOT_TABLES", threading.local())
     c = np.complex64
     x, out, ii, ea = _Stub((1, 9), c, 10), _Stub((1, 9), c, 11), _Stub((1, 9), np.int32, 20), _Stub((1, 16), np.complex128, 30)
     square = hip_dsp.PatternLevels([-3, -1, 1, 3], [-3, -1, 1, 3])
     hip_dsp.pattern_index_dev(x, square, 2, ii, ii)
     for k in range(2 * hip_dsp.PILOT_TABLES_KEPT):                              # other tables come and go
-        hip_dsp._pilot_table(np.arange(k + 2, dtype=np.int64))
+        hip_dsp.pilot._pilot_table(np.arange(k + 2, dtype=np.int64))
     rect = hip_dsp.PatternLevels([-3, -1, 1, 3], [-1, 1])                      # the same in-phase rail, another quadrature rail
     hip_dsp.pattern_index_dev(x, rect, 2, ii, ii)
     hip_dsp.lut_predistort_dev(x, rect, 2, ea, out)
