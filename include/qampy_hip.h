@@ -391,7 +391,10 @@ int qh_make_decision_c64_dev(const void *E, int64_t L, const void *symbols, int 
 int qh_make_decision_c128_dev(const void *E, int64_t L, const void *symbols, int M, void *det, void *dist, int32_t *idx);
 
 /* ---- measurement helpers ---------------------------------------------------------------------------------------
- * symbol errors of decided indices against a reference index sequence with a lag: count(idx_rx[i] != idx_tx[i - lag]) */
+ * symbol errors of decided indices against a reference index sequence with a lag: count(idx_rx[i] != idx_tx[i - lag]) over the i < n
+ * with 0 <= i - lag < ntx.  idx_rx (n,), idx_tx (ntx,) and count_dev (one unsigned 64-bit counter) live in HBM.  The count is ADDED to
+ * *count_dev, which is never cleared here: the caller zeroes it, and may accumulate several calls in it; n <= 0 leaves it alone.  The
+ * launch is asynchronous on the library stream.  A NULL pointer or ntx < 0 returns QH_ERR_ARG before anything is launched. */
 int qh_count_errors_dev(const int32_t *idx_rx, const int32_t *idx_tx, int64_t n, int64_t lag, int64_t ntx,
                         unsigned long long *count_dev);
 
@@ -622,7 +625,11 @@ int qh_train_equaliser_c128_batch_dev(const void *E, int nch, int nmodes, int64_
  * HBM; idx_tx: decided indices of the transmitted symbols (nmodes, ntx) int32 in HBM (qh_make_decision_*_dev); symbols
  * (M,) in HBM.  Bounded search over tx mode x quadrant rotation x lag in [-maxlag, maxlag] on a `window` of decided
  * symbols from the middle of the run, then errors over [trim, N - trim).  result (HOST, 7 x int64): errors, compared,
- * tx mode, rotation k (row was multiplied by j^k), lag (rx[i] <-> tx[i - lag]), matches in the window, window length. */
+ * tx mode, rotation k (row was multiplied by j^k), lag (rx[i] <-> tx[i - lag]), matches in the window, window length.
+ * Window: W = window > 0 ? window : 4096, then min(W, N - 2 trim), starting at trim + (N - 2 trim - W) / 2 (integer division).  The
+ * winner is the FIRST maximum of the match counts in (tx mode, rotation, lag) order, lags ascending from -maxlag.  Only symbols with
+ * 0 <= i - lag < ntx are matched or compared; a label outside [0, M) never matches.  1 <= nmodes <= 16, M >= 1, 0 <= maxlag <= 4096,
+ * trim >= 0, 2 trim < N; bad sizes and NULL pointers return QH_ERR_ARG before anything is launched and leave result untouched. */
 int qh_ser_c64_dev(const void *E, int64_t N, const int32_t *idx_tx, int nmodes, int64_t ntx, const void *symbols, int M,
                    int maxlag, int64_t window, int64_t trim, int64_t *result);
 int qh_ser_c128_dev(const void *E, int64_t N, const int32_t *idx_tx, int nmodes, int64_t ntx, const void *symbols, int M,

@@ -1354,7 +1354,8 @@ int qh_count_errors_dev(const int32_t *rx, const int32_t *tx, int64_t n, int64_t
 {
     int rc = qh::ensure_init();
     if (rc) return rc;
-    if (n <= 0) return QH_OK;
+    QH_REQUIRE(rx && tx && count_dev && ntx >= 0, "count_errors: null pointer or negative ntx");
+    if (n <= 0) return QH_OK;                                       // nothing to add: the counter keeps its value
     unsigned nb = (unsigned)((n + 255) / 256);
     if (nb > 2048) nb = 2048;
     hipLaunchKernelGGL(qh::count_errors_kernel, dim3(nb), dim3(256), 0, qh::g_stream, rx, tx, n, lag, ntx, count_dev);

@@ -92,6 +92,7 @@ int ser_dev(const void *E, int64_t N, const int32_t *idx_tx, int nmodes, int64_t
     if (rc) return rc;
     QH_REQUIRE(N > 0 && nmodes >= 1 && nmodes <= 16 && M >= 1 && maxlag >= 0 && maxlag <= 4096 && trim >= 0 && 2 * trim < N,
                "ser: bad sizes");
+    QH_REQUIRE(E && idx_tx && symbols && result, "ser: null pointer");
     int64_t W = window > 0 ? window : 4096;
     if (W > N - 2 * trim) W = N - 2 * trim;
     const int64_t start = trim + (N - 2 * trim - W) / 2;            // window from the middle of the run

@@ -183,6 +183,16 @@ def test_resident_receiver_device_ser_equals_host_ser():
         nerr, ncmp, mode, rot, lag = synth.count_symbol_errors(row, sig.symbols, sig.coded_symbols, max_lag=256, trim=2000)
         assert (d["tx_mode"], d["rotation"]) == (mode, rot) and d["lag"] == lag + 2000      # host lag is relative to the trimmed row
         assert abs(d["errors"] - nerr) <= 2 and abs(d["compared"] - ncmp) <= 2 * 256 + 4000, (d, nerr, ncmp)
+    # the float64 restatement of the harness (tests/ser_ref.py) on the same rows: alignment, compared and window length exactly; the two counts
+    # up to the float32 decisions that may fall the other way - the samples within 1e-4 of a boundary inside the compared range
+    import ser_ref
+    al = np.asarray(sig.coded_symbols, np.complex128)
+    idx_tx = np.stack([ser_ref.decide(t, al)[0] for t in np.asarray(sig.symbols)])
+    for d, row in zip(dev, out):
+        (errors, compared, mode, k, lag, matches, W), at, _ = ser_ref.ser(row, idx_tx, al, 256, 4096, 2000, detail=True)
+        assert (d["tx_mode"], d["rotation"], d["lag"], d["compared"], d["window"]) == (mode, k, lag, compared, W)
+        near = int(np.count_nonzero(ser_ref.decide(row[at] * 1j ** k, al)[1] < 1e-4))
+        assert abs(d["errors"] - errors) <= near and abs(d["window_matches"] - matches) <= near, (d, errors, matches, near)
 
 
 # ------------------------------------------------------------------------------------------------ channel bank (8e, within a GPU)
