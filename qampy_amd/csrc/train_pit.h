@@ -7,8 +7,8 @@
 //   * the number of passes (each costs one segment length of dependent steps),
 // and both end on device-side criteria (error plateau; boundary defect), so the host only enqueues.
 //
-// Buffers per call (scratch slot 2):  X (S tap sets) start taps of the current pass,  Y (S tap sets) trained in place,
-// rot (S x nsel) pass-0 phase rotations, z (S x nsel) 4th-power sums, dfc (S x nsel) boundary defects.
+// Buffers per call: PitBuffers names every one of them (X: start taps of the current pass, Y: trained in place, S tap sets each; rot, z, dfc per segment
+// and mode: pass-0 phase rotations, 4th-power sums, boundary defects; ...) and says which of the PIT_* scratch slots it is carved from.
 #pragma once
 #include <atomic>
 #include <chrono>
@@ -22,8 +22,8 @@ typedef qh_pit_report PitCtrl;
 
 constexpr double PIT_CONTRACT = 0.2; // expected defect ratio of consecutive passes with the coarse correction (measured 0.1 .. 0.4)
 constexpr int PIT_PROBE = 128;      // symbol periods of the capture a boundary defect is measured on
-constexpr int PIT_SEEDWIN = 512;
-constexpr int PIT_MAXSEG = 65536;  // segments of a sweep (was 4096: the 10^7-symbol capture already sat on it)    // symbol periods of a segment's head the phase seed is estimated on
+constexpr int PIT_SEEDWIN = 512;    // symbol periods of a segment's head the phase seed is estimated on
+constexpr int PIT_MAXSEG = 65536;   // segments of a sweep (was 4096: the 10^7-symbol capture already sat on it)
 
 // symmetry group of an error function: errfn(g y) = g errfn(y).  0: every phase (cma, rde); n: the n-th roots of unity
 __host__ __device__ inline int pit_symmetry(int method)
@@ -2176,24 +2176,19 @@ int pit_basis(const void *E, int nmodes, int64_t L, int os, int ntaps, int64_t T
     const int nsweep = PIT_EIGSWEEPS;
     // rotations logged by the solver, applied to V row by row afterwards; block form while two copies of A fit the LDS (n <= 96), else
     // the row / column form
-    float4 *glog = nullptr;
-    const bool logged = true;
-    const size_t jlds = (size_t)ntot * (ntot + 1) * sizeof(Zf) + 256;
-    {
-        void *gl = nullptr;
-        const int mm = (ntot + 1) & ~1;
-        if ((rc = scratch(Slot::PIT_ROTATIONS, (size_t)nsweep * (mm - 1) * (mm / 2) * sizeof(float4) + 64, &gl))) return rc;
-        glog = (float4 *)gl;
-    }
-    const size_t blds = 2 * (size_t)ntot * (ntot + 1) * sizeof(Zf) + 256;
-    if (logged && blds <= 160 * 1024 - 2048) {          // (the kernel's static LDS: the round's pairs and rotations)
+    void *gl = nullptr;
+    const int mm = (ntot + 1) & ~1;
+    if ((rc = scratch(Slot::PIT_ROTATIONS, (size_t)nsweep * (mm - 1) * (mm / 2) * sizeof(float4) + 64, &gl))) return rc;
+    float4 *glog = (float4 *)gl;
+    const size_t jlds = (size_t)ntot * (ntot + 1) * sizeof(Zf) + 256, blds = 2 * jlds - 256;
+    if (blds <= 160 * 1024 - 2048) {          // (the kernel's static LDS: the round's pairs and rotations)
         static std::atomic<bool> battr{false};
         if (!battr.load(std::memory_order_acquire)) { QH_HIP(hipFuncSetAttribute((const void *)pit_jacobi_blk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048)); battr.store(true, std::memory_order_release); }
         hipLaunchKernelGGL(pit_jacobi_blk_kernel, dim3(1), dim3(1024), blds, st, (const Z *)Rc, ntot, 1.0 / (double)ncov, (double *)basis, nsweep, glog);
     } else
     hipLaunchKernelGGL(pit_jacobi_kernel, dim3(1), dim3(1024), jlds, st, (const Z *)Rc, ntot, 1.0 / (double)ncov, (double *)basis,
                        (Zf *)((char *)basis + (size_t)ntot * sizeof(double)), nsweep, glog);
-    if (glog) hipLaunchKernelGGL(pit_jacobi_v_kernel, dim3(ntot), dim3(64), 0, st, (const float4 *)glog, ntot, nsweep, (Zf *)((char *)basis + (size_t)ntot * sizeof(double)));
+    hipLaunchKernelGGL(pit_jacobi_v_kernel, dim3(ntot), dim3(64), 0, st, (const float4 *)glog, ntot, nsweep, (Zf *)((char *)basis + (size_t)ntot * sizeof(double)));
     QH_HIP(hipGetLastError());
     if (overlap) { QH_HIP(hipEventRecord(bs.out, st)); bs.pending = true; }
     return QH_OK;
@@ -2322,6 +2317,19 @@ template <typename R> __global__ void __launch_bounds__(256) pit_adopt_kernel(Cx
         *mu_acq = *mu_acq_prep;
     }
 }
+// the selected modes as a kernel argument: 16 entries, zeros behind the nsel given
+inline void pit_fill_modes(int64_t *dst, const int64_t *modes, int nsel) { for (int j = 0; j < 16; j++) dst[j] = j < nsel ? modes[j] : 0; }
+inline void pit_init_modes(PitInit &init, int64_t *modes_dev, const int64_t *modes, int nsel)
+{
+    init.modes_dev = modes_dev; init.nsel = nsel;
+    pit_fill_modes(init.modes, modes, nsel);
+}
+// the one launch of pit_setup_kernel: power over the first 4096 samples of the capture, gear-shifted step, report header
+template <typename R>
+void pit_setup_launch(const void *E, int nmodes, int64_t L, int ntot, const R *mu_dev, double gear, double bound, double tol, const PitSeg &sg, PitCtrl *ctrl, R *mu_acq)
+{
+    hipLaunchKernelGGL((pit_setup_kernel<R>), dim3(1), dim3(256), 0, g_stream, (const Cx<R> *)E, nmodes, L, (int64_t)(L < 4096 ? L : 4096), ntot, mu_dev, gear, bound, tol, sg, ctrl, mu_acq);
+}
 template <typename R>
 int pit_prepare(const void *E, int nmodes, int64_t L, int64_t TrSyms, int os, const R *mu_dev, const void *wx0, int ntaps, const int64_t *modes, int nsel,
                 const void *symbols, int64_t nsy, int method, const qh_pit_opts *opts, void *prep, size_t prep_bytes)
@@ -2353,13 +2361,11 @@ int pit_prepare(const void *E, int nmodes, int64_t L, int64_t TrSyms, int os, co
     int64_t *modes_dev = (int64_t *)(pb + lay.modes);
     Cx<R> *wxp = (Cx<R> *)(pb + lay.wx), *w0 = (Cx<R> *)(pb + lay.w0), *errp = (Cx<R> *)(pb + lay.err);
     const size_t wset = (size_t)nmodes * ntot, wbytes = wset * sizeof(Cx<R>);
-    const int64_t npow = L < 4096 ? L : 4096;
-    hipLaunchKernelGGL((pit_setup_kernel<R>), dim3(1), dim3(256), 0, g_stream, (const Cx<R> *)E, nmodes, L, npow, ntot, mu_dev, pl.gear, pl.bound, o.tol > 0 ? o.tol : 1e-3, sg, ctrl, mu_acq);
+    pit_setup_launch<R>(E, nmodes, L, ntot, mu_dev, pl.gear, pl.bound, o.tol > 0 ? o.tol : 1e-3, sg, ctrl, mu_acq);
     PitInit init{};
     init.cd[0] = wxp; init.cs[0] = wx0; init.cn[0] = (unsigned)wbytes;
     init.cd[1] = w0; init.cs[1] = wx0; init.cn[1] = (unsigned)wbytes;
-    init.modes_dev = modes_dev; init.nsel = nsel;
-    for (int j = 0; j < 16; j++) init.modes[j] = j < nsel ? modes[j] : 0;
+    pit_init_modes(init, modes_dev, modes, nsel);
     hipLaunchKernelGGL(pit_init_kernel, dim3(32), dim3(256), 0, g_stream, init);
     QH_REQUIRE(pl.ngram <= lay.err_pitch, "pit prepare: acquisition range exceeds the preparation buffer");
     void *G = nullptr;
@@ -2373,80 +2379,533 @@ int pit_prepare(const void *E, int nmodes, int64_t L, int64_t TrSyms, int os, co
     return QH_OK;
 }
 
+// ---- every device buffer of a tier-b call, by name; carved from the five PIT_* scratch slots, one function per slot (S: segments, ncol = S x nsel)
+template <typename R> struct PitBuffers {
+    // PIT_CTRL: control block / report (or the caller's report_dev), gear-shifted step
+    PitCtrl *ctrl; R *mu_acq;
+    // PIT_WORK: start taps of the pass and taps trained in place (S tap sets each); taps before the acquisition, at the call
+    Cx<R> *X, *Y, *w_start, *w_call;
+    // 4th-power sums, pass-0 rotations, boundary defects, powers, gauge phases (per segment and mode)
+    double *z, *rot, *dfc, *pw, *gph, *theta;
+    // selected modes; carries of the unwrap
+    int64_t *modes_dev; double *uw_phi; int *uw_jump;
+    // per-block maxima of the deviation estimate (four floats per block), which block finishes last; head retry: last column above tol, bad flag
+    float *devmax; unsigned *ticket; int *front;
+    // PIT_ACQ: error rows of an exact head (rows of its own length)
+    Cx<R> *errh;
+    // adaptive step (else null): previous error and r at the start / end of every segment, sums of the step sizes, scan states,
+    // change of the start values, the step the call came with
+    Cx<R> *eS, *eE; R *rS, *rE; float *M, *rP, *dP, *chg; R *mu_saved;
+    // PIT_BASIS: eigenvalues, then V and V^T (the slot's or the caller's basis); defect vectors and tap sets in the eigenbasis
+    double *lam; const Zf *Vb; Zf *Dz[2], *Xe, *Ye, *Yprev;
+    // PIT_MODEL: partial sums, signal direction, per-column sums (ualpha and uqv: u_bytes, zeroed as one region), the model, its ticket
+    float *part; Cx<R> *u; float4 *ualpha; float2 *uqv; unsigned u_bytes; PitModel *model; unsigned *model_ticket;
+};
+// A slot's regions are walked twice: without a base, for the total that scratch() is asked for once, then with the base it gave.
+// `regions` names every region once, as c(pointer, elements), in the order of the layout.
+struct PitCarve {
+    uintptr_t base = 0;
+    ScratchLayout lay;
+    template <typename T> void operator()(T *&p, size_t n) { p = reinterpret_cast<T *>(base + lay.take(n * sizeof(T))); }
+};
+template <typename F> int pit_carve(Slot slot, F regions)
+{
+    PitCarve size, c;
+    regions(size);
+    void *p = nullptr;
+    if (int rc = scratch(slot, size.lay.total, &p)) return rc;
+    c.base = (uintptr_t)p;
+    regions(c);
+    return QH_OK;
+}
+template <typename R> int pit_carve_ctrl(PitBuffers<R> &b, void *report_dev)
+{
+    const int rc = pit_carve(Slot::PIT_CTRL, [&](PitCarve &c) { c(b.ctrl, 1); c(b.mu_acq, 1); });
+    if (report_dev) b.ctrl = (PitCtrl *)report_dev;
+    return rc;
+}
+template <typename R> int pit_carve_work(PitBuffers<R> &b, int S, int nsel, size_t wset)
+{
+    const size_t nsj = (size_t)S * nsel;
+    return pit_carve(Slot::PIT_WORK, [&](PitCarve &c) {
+        c(b.X, S * wset); c(b.Y, S * wset); c(b.w_start, wset); c(b.w_call, wset);
+        c(b.z, 2 * nsj); c(b.rot, 2 * nsj); c(b.dfc, nsj); c(b.pw, nsj); c(b.gph, 2 * nsj); c(b.theta, 2 * nsj);
+        c(b.modes_dev, nsel); c(b.uw_phi, nsj); c(b.uw_jump, nsj);
+        c(b.devmax, 4 * ((nsj + 63) / 64)); c(b.ticket, 1); c(b.front, 2);
+    });
+}
+// head: steps of an exact head (its error rows); adaptive: the per-segment state of the adaptive step as well
+template <typename R> int pit_carve_acq(PitBuffers<R> &b, int S, int nmodes, int64_t head, bool adaptive)
+{
+    const size_t nS = ((size_t)S + 15) / 16 * 16;
+    return pit_carve(Slot::PIT_ACQ, [&](PitCarve &c) {
+        c(b.errh, (size_t)nmodes * head);
+        if (!adaptive) return;
+        c(b.eS, nS); c(b.eE, nS); c(b.rS, nS); c(b.rE, nS); c(b.M, nS); c(b.rP, nS); c(b.dP, nS); c(b.chg, 1); c(b.mu_saved, 1);
+    });
+}
+// basis: the caller's eigenbasis (pit_basis), nullptr: the slot's own, which the caller of this function builds at b.lam
+template <typename R> int pit_carve_basis(PitBuffers<R> &b, int ntot, int ncol, int nsel, void *basis)
+{
+    const size_t mat = (size_t)ntot * ncol;
+    char *own = nullptr;
+    const int rc = pit_carve(Slot::PIT_BASIS, [&](PitCarve &c) {
+        c(own, pit_basis_bytes(ntot)); c(b.Dz[0], mat); c(b.Dz[1], mat); c(b.Xe, mat); c(b.Ye, mat); c(b.Yprev, (size_t)ntot * nsel);
+    });
+    b.lam = (double *)(basis ? basis : own); b.Vb = (const Zf *)(b.lam + ntot);
+    return rc;
+}
+template <typename R> int pit_carve_model(PitBuffers<R> &b, int ntot, int ncol, int nsel)
+{
+    const size_t b_ua = ((size_t)ncol * sizeof(float4) + 63) / 64 * 64, b_uq = ((size_t)ncol * sizeof(float2) + 63) / 64 * 64;
+    char *ua = nullptr;                                          // (ualpha and uqv: one region of pit_init_kernel)
+    const int rc = pit_carve(Slot::PIT_MODEL, [&](PitCarve &c) {
+        c(b.part, (size_t)PIT_MODB * 4 * nsel * (2 * PIT_EIGMAX + 8)); c(b.u, (size_t)nsel * ntot); c(ua, b_ua + b_uq); c(b.model, 16); c(b.model_ticket, 1);
+    });
+    b.ualpha = (float4 *)ua; b.uqv = (float2 *)(ua + b_ua); b.u_bytes = (unsigned)(b_ua + b_uq);
+    return rc;
+}
+
+// ---- what a tier-b call was given and what it decided: filled once by train_pit_dev before the first sweep, read-only for everything it calls
+template <typename R> struct PitSweep {
+    // the caller's arguments
+    const void *E; int nmodes; int64_t L, TrSyms; int Niter, os; R *mu_dev; void *wx; int ntaps; const int64_t *modes; int nsel;
+    const void *symbols; int64_t nsy; int method; void *err; const void *gram; void *report_dev; int depth;
+    // the options in force (the caller's or the defaults; acquire cleared where nothing is acquired) and what they come to
+    qh_pit_opts o;
+    int npass, sym, timing_mode;
+    double tol, safety, beta;
+    bool adaptive, seed_phase, want_corr, redo_ok, prepared;
+    static constexpr float ad_relax = 1.0f, ad_damp = 0.7f;          // adaptive step (measured: profiles/r03_adaptive_tier_b.txt)
+    static constexpr int ad_newton = 1;
+    // the form of the passes and of their analysis (pit_decide_form)
+    bool decision, seg_form, use_bi, block_form, pair_tab, eig, tail_fused, ssb, split, xchg_async;
+    int own_first, own_count;
+    // sizes: taps of all modes, of one tap set (elements, bytes), columns S x nsel, blocks of the estimate, LDS of the plain products
+    int ntot, ncol, ndev;
+    size_t wset, wbytes, glds;
+    int64_t head, g_per_step;                                        // steps of the exact head; GramPair elements per step
+    PitPlan pl;
+    PitBuffers<R> b;
+    LaArgs<R> la; TrainArgs<R> ta; PitModelArgs<R> ma;
+    const void *G;                                                   // Gram table (the caller's or built here)
+    const double *rot_use;                                           // b.rot when the sweeps seed the phase, else nullptr
+};
+// coarse model of a sweep on the helper stream: `seed` gates it behind the seed taps, the analysis of pass 0 waits for `done`
+struct PitModelSync { hipEvent_t seed = nullptr, done = nullptr; };
+inline PitModelSync &pit_model_sync() { static thread_local PitModelSync m; return m; }
+
 template <typename R>
 int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Niter, int os, R *mu_dev, void *wx, int ntaps,
                   const int64_t *modes, int nsel, const void *symbols, int64_t nsy, int method, void *err, int zero_err,
-                  const void *gram, const qh_pit_opts *opts, void *report_dev, int depth = 0)
+                  const void *gram, const qh_pit_opts *opts, void *report_dev, int depth = 0);
+
+// The exact form (train_dev) in place of the passes, and the report says so: converged = 2, and for a call that takes it from the start
+// also segments = 1 and `passes` (< 0: left as they are).  The copies come from this stack frame: the stream is synchronised.
+template <typename R> int pit_exact_form(const PitSweep<R> &sw, PitCtrl *c, int ad, int zero, const void *g, int passes)
 {
-    pit_last_launch() = PitLaunch{0, 0, 0, 0, 0, 0};             // (qh_pit_last_launch: nothing but the exact form until a pass is enqueued; a refused call leaves zeros too)
-    int rc = ensure_init();
-    if (rc) return rc;
-    if ((rc = train_args_ok("train_equaliser", method, nmodes, ntaps, os, TrSyms, Niter, nsel, nsy, modes))) return rc;
-    QH_REQUIRE(TrSyms == 0 || (TrSyms - 1) * os + ntaps <= L, "train_equaliser: field shorter than TrSyms*os + ntaps");
-    qh_pit_opts o = opts ? *opts : pit_opts_default();
-    // The exact form (train_dev) in place of the passes, and the report says so: converged = 2, and for a call that takes it from the start
-    // also segments = 1 and `passes` (< 0: left as they are).  The copies come from this stack frame: the stream is synchronised.
-    auto exact_form = [&](PitCtrl *c, int ad, int zero, const void *g, int passes) -> int {
-        int r = train_dev<R>(E, nmodes, L, TrSyms, Niter, os, mu_dev, wx, ntaps, modes, nsel, ad, symbols, nsy, method, err, zero, g);
-        if (r) return r;
-        const int32_t hdr[3] = {1, passes, 2};
-        if (passes < 0) QH_HIP(hipMemcpyAsync(&c->converged, &hdr[2], sizeof(int32_t), hipMemcpyHostToDevice, g_stream));
-        else QH_HIP(hipMemcpyAsync(&c->segments, hdr, sizeof(hdr), hipMemcpyHostToDevice, g_stream));
-        QH_HIP(hipStreamSynchronize(g_stream));
-        return QH_OK;
-    };
-    QH_REQUIRE(o.segments >= 0 && o.segments <= PIT_MAXSEG && o.max_passes >= 0 && o.max_passes <= QH_PIT_MAXPASS, "train_equaliser: bad segment / pass count");
-    QH_REQUIRE(o.adaptive >= 0 && o.adaptive <= 2, "train_equaliser: adaptive must be 0, 1 or 2");
-    // Adaptive step (opts.adaptive = 1): ONE output mode per call (the reference carries one step size from mode to mode: the caller runs
-    // the modes in turn), one sweep, single precision, the error functions of train_seg_*_f32_ad.hip.  The head of the sweep runs in
-    // the exact form; the segments cover the rest, with r = 1 / mu and the previous error as boundary states (DESIGN.md 3.2.1).
-    // Tier b is TOTAL: a call for which no parallel-in-time solver exists - data-aided training (the symbols are indexed by the step:
-    // nothing to certify against a segment grid yet), the adaptive step with another error function / precision / several sweeps /
-    // several modes at once / one step size per mode (adaptive = 2) - takes the exact form right away and says so (report:
-    // segments = 1, converged = 2); the result is the reference's either way.
-    bool adaptive = o.adaptive != 0;
-    {
-        bool exact_only = method == QH_M_SBD_DATA;
-        if (adaptive && (o.adaptive == 2 || sizeof(R) != 4 || nsel != 1 || Niter != 1 || !seg_adaptive_supported(method))) exact_only = true;
-        QH_REQUIRE(!(adaptive && o.exchange), "train_equaliser: a capture split over processes is trained with a fixed step");
-        if (exact_only) {
-            QH_REQUIRE(!o.exchange, "train_equaliser: a capture split over processes needs the parallel-in-time solver (blind / decision-directed method, fixed step)");
-            void *cb0 = nullptr;
-            if ((rc = scratch(Slot::PIT_CTRL, sizeof(PitCtrl) + 64, &cb0))) return rc;
-            PitCtrl *c0 = report_dev ? (PitCtrl *)report_dev : (PitCtrl *)cb0;
-            PitSeg s1; s1.S = 1; s1.len = TrSyms; s1.extra = 0; s1.tail = 0;
-            hipLaunchKernelGGL((pit_setup_kernel<R>), dim3(1), dim3(256), 0, g_stream, (const Cx<R> *)E, nmodes, L, (int64_t)(L < 4096 ? L : 4096), nmodes * ntaps, (const R *)mu_dev, 1.0, 1.0,
-                               o.tol > 0 ? o.tol : 1e-3, s1, c0, (R *)((char *)cb0 + sizeof(PitCtrl)));
-            return exact_form(c0, o.adaptive, zero_err, adaptive ? nullptr : gram, 0);
-        }
+    int r = train_dev<R>(sw.E, sw.nmodes, sw.L, sw.TrSyms, sw.Niter, sw.os, sw.mu_dev, sw.wx, sw.ntaps, sw.modes, sw.nsel, ad, sw.symbols, sw.nsy, sw.method, sw.err, zero, g);
+    if (r) return r;
+    const int32_t hdr[3] = {1, passes, 2};
+    if (passes < 0) QH_HIP(hipMemcpyAsync(&c->converged, &hdr[2], sizeof(int32_t), hipMemcpyHostToDevice, g_stream));
+    else QH_HIP(hipMemcpyAsync(&c->segments, hdr, sizeof(hdr), hipMemcpyHostToDevice, g_stream));
+    QH_HIP(hipStreamSynchronize(g_stream));
+    return QH_OK;
+}
+
+// what pit_decide_kernel gets for pass p.  est: the deviation estimate was formed (devmax; the correction is wanted); eigen: the end taps in the eigenbasis too
+template <typename R> PitDecideArgs<R> pit_decide_args(const PitSweep<R> &sw, const PitEvents &ev, int p, bool est, bool eigen)
+{
+    const PitBuffers<R> &b = sw.b; const PitSeg &sg = sw.pl.sg;
+    PitDecideArgs<R> d;
+    d.dfc = b.dfc; d.pw = b.pw; d.nb = (int)((sg.S - 1) * sw.nsel); d.Ylast = (const Cx<R> *)(b.Y + (size_t)(sg.S - 1) * sw.wset); d.n = (int)sw.wset; d.wx = (Cx<R> *)sw.wx; d.c = b.ctrl;
+    d.host_view = &ev.hview[2 * p]; d.nrow = sw.nsel; d.devmax = est ? (const float *)b.devmax : nullptr; d.ndev = sw.ndev; d.safety = sw.safety;
+    d.Ye = eigen ? (const float2 *)b.Ye : nullptr; d.Yprev = eigen ? (float2 *)b.Yprev : nullptr; d.ne = eigen ? sw.ntot : 0; d.ncol_e = eigen ? sw.ncol : 0;
+    d.theta = b.theta; d.modes_dev = (const int64_t *)b.modes_dev; d.ntot_w = sw.ntot; d.S = (int)sg.S; d.sym = sw.sym; d.corr_wanted = est ? 1 : 0;
+    d.extra = sw.adaptive ? (const float *)b.chg : nullptr;
+    d.Dfin = (eigen && !sw.adaptive) ? (const float2 *)b.Dz[1] : nullptr; d.Vfin = (const float2 *)b.Vb; d.lam_fin = b.lam;
+    // (plain relaxation asked for - opts.correction = 0: its fixed point is reached after S passes whatever the boundary defects do on the way - from
+    // converged taps they stay at the noise level until the last pass - so "nothing gained over two passes" must not end such a sweep early)
+    d.stall_from = sw.o.correction == 0 ? QH_PIT_MAXPASS : (sw.adaptive ? 5 : 2);
+    return d;
+}
+// HIP events around the trainer launch of a pass (qh_pit_last_timing): an event is ~5.6 us of idle stream, so by default only
+// pass 1 of a sweep is timed (pass 0 of a cold sweep shares the chip with the basis build); QAMPY_HIP_PIT_TIMING = all | none
+template <typename R> inline bool pit_timed(const PitSweep<R> &sw, int p) { return sw.timing_mode == 2 || (sw.timing_mode == 1 && p == 1); }
+// a basis still being built on the other stream (pit_basis with overlap): the first launch that reads it waits
+inline int pit_wait_basis(const qh_pit_opts &o)
+{
+    if (o.basis && pit_basis_sync().pending) {
+        QH_HIP(hipStreamWaitEvent(g_stream, pit_basis_sync().out, 0));
+        pit_basis_sync().pending = false;
     }
-    if (adaptive) o.acquire = 0;
-    const int ntot = nmodes * ntaps;
-    // Adaptive sweeps apply 0.7 of every correction after the first (the full one overshoots: the estimate then GROWS 1.7 x per pass on the
-    // blind stage of the reference script's recipe; damped it falls 0.3-0.5 x per pass, profiles/r03_adaptive_tier_b.txt) and what is left
-    // of the early corrections sits in the result, so they are held to a third of the tolerance and may take 24 passes.
-    const int npass = o.max_passes > 0 ? o.max_passes : (adaptive ? QH_PIT_MAXPASS : 16);
-    const double tol = (o.tol > 0 ? o.tol : 1e-3) * (adaptive ? 1.0 / 3.0 : 1.0);
-    const double safety = o.dev_safety > 0 ? o.dev_safety : PIT_DEV_SAFETY;
-    const int sym = pit_symmetry(method);
-    const bool seed_phase = o.phase_seed < 0 ? sym == 4 : o.phase_seed != 0;
-    const bool want_corr = o.correction != 0 && pit_basis_ok(ntot, sizeof(Cx<R>));
-    double beta = o.corr_beta >= 0 ? o.corr_beta : (sym == 0 ? 1.5 : 0.0);       // (round-3 model only: the measured model needs no extra damping, see below)
+    return QH_OK;
+}
 
-    // ---- control block / report
-    void *cbuf = nullptr;
-    if ((rc = scratch(Slot::PIT_CTRL, sizeof(PitCtrl) + 64, &cbuf))) return rc;
-    PitCtrl *ctrl = report_dev ? (PitCtrl *)report_dev : (PitCtrl *)cbuf;
-    R *mu_acq = (R *)((char *)cbuf + sizeof(PitCtrl));            // 8-byte aligned: sizeof(PitCtrl) is a multiple of 8
-
-    // ---- segment grid
+// ---- one relaxation pass, in the order it is enqueued: start taps, trainer, exchange (split capture), analysis
+// back_done_for: the pass whose start taps the last tail launch wrote into X (0: none)
+template <typename R> int pit_start_taps(const PitSweep<R> &sw, int p, const PitFuse<R> &fz, int back_done_for)
+{
+    const PitBuffers<R> &b = sw.b;
+    const int ntot = sw.ntot, ncol = sw.ncol, S = sw.pl.sg.S;
+    if (p == 0 || (sw.tail_fused && back_done_for == p)) return QH_OK;     // pit_seed_kernel / the tail of pass p - 1 has written them into X already
+    if (sw.want_corr) {
+        // start taps = theta X + V D~ with D[s+1] = d[s+1] + J D[s] from the analysis that closed pass p - 1; with the
+        // correction switched off on the device (corr_on = 0) the scan ran with coefficient 0, D = d: plain relaxation
+        if (sw.eig)
+            hipLaunchKernelGGL((pit_basis_mfma_kernel<R, 1>), dim3((ncol + PIT_MC - 1) / PIT_MC), dim3(pit_mfma_threads(ntot)), pit_mfma_lds(ntot), g_stream, b.Vb + (size_t)ntot * ntot,
+                               (const Cx<R> *)nullptr, (const Zf *)b.Dz[1], (Zf *)nullptr, ntot, ncol, (const PitCtrl *)b.ctrl, fz);
+        else
+            hipLaunchKernelGGL((pit_cgemm_kernel<R, false>), dim3((ncol + PIT_GT - 1) / PIT_GT), dim3(256), sw.glds, g_stream, b.Vb + (size_t)ntot * ntot, (const Zf *)b.Dz[1], (Zf *)nullptr, ntot, ncol, (const PitCtrl *)b.ctrl, fz);
+        QH_HIP(hipGetLastError());
+    } else {
+        QH_HIP(hipMemcpyAsync(b.X + sw.wset, b.Y, (size_t)(S - 1) * sw.wbytes, hipMemcpyDeviceToDevice, g_stream));   // X[s] = end taps of s-1
+        QH_HIP(hipMemcpyAsync(b.Y, b.X, (size_t)S * sw.wbytes, hipMemcpyDeviceToDevice, g_stream));
+    }
+    return QH_OK;
+}
+// the trainer over all segments of sweep `it`: throughput segments, a block form (block-iterative / look-ahead), or the direct form
+template <typename R> int pit_train_pass(const PitSweep<R> &sw, int it)
+{
+    const PitBuffers<R> &b = sw.b; const PitSeg &sg = sw.pl.sg;
+    if (sw.seg_form) {
+        SegArgs<R> sa{};
+        sa.E = (const Cx<R> *)sw.E; sa.wx = sw.tail_fused ? b.X : b.Y; sa.wx_out = sw.tail_fused ? b.Y : nullptr; sa.symbols = sw.la.symbols; sa.err = (Cx<R> *)sw.err; sa.mu = sw.mu_dev;
+        sa.L = sw.L; sa.TrSyms = sw.TrSyms; sa.nsy = sw.la.nsy; sa.sy_pitch = sw.la.sy_pitch; sa.err_pitch = sw.TrSyms * sw.Niter; sa.err_off = (int64_t)it * sw.TrSyms;
+        sa.nmodes = sw.nmodes; sa.ntaps = sw.ntaps; sa.os = sw.os; sa.nsel = sw.nsel; sa.S = sg.S;
+        sa.seg_len = sg.len; sa.seg_extra = sg.extra; sa.seg_tail = sg.tail; sa.seg_begin = sg.begin;
+        sa.r_in = b.rS; sa.r_out = b.rE; sa.e_in = b.eS; sa.e_out = b.eE; sa.mu_sum = (R *)b.M; sa.adapt_first = sg.begin > 0 ? 1 : 0;
+        pit_fill_modes(sa.modes, sw.modes, sw.nsel);
+        sa.skip = &b.ctrl->done;
+        sa.q_first = sw.own_first * sw.nsel; sa.q_count = sw.split ? sw.own_count * sw.nsel : 0;
+        pit_last_launch().form = 1;                             // (launch_seg adds the layout; a process of a split capture that owns no segment launches none)
+        if (!sw.split || sw.own_count > 0) { int r = launch_seg<R>(sa, sw.method, sw.adaptive); if (r) return r; }
+        if (sw.adaptive) hipLaunchKernelGGL((pit_adapt_scan_kernel<R>), dim3(1), dim3(1024), 0, g_stream, b.rS, (const R *)b.rE, b.eS, (const Cx<R> *)b.eE, sg.S, b.chg, (const PitCtrl *)b.ctrl, sw.ad_relax, b.rP, b.dP, sw.ad_newton);
+        return QH_OK;
+    }
+    if (sw.block_form) {
+        LaArgs<R> ls = sw.la;
+        ls.TrSyms = sg.len; ls.nch = sg.S; ls.wx = b.Y; ls.err_off = (int64_t)it * sw.TrSyms; ls.seg = 1; ls.seg_extra = sg.extra; ls.seg_tail = sg.tail;
+        ls.skip = &b.ctrl->done;
+        pit_last_launch() = PitLaunch{sw.use_bi ? 2 : 3, 0, 0, 0, 0, 0};
+        if (sg.begin > 0) {                                  // an exact head: the segments cover the steps from sg.begin on
+            ls.E = (const Cx<R> *)sw.E + sg.begin * sw.os; ls.L = sw.L - sg.begin * sw.os; ls.err_off += sg.begin;
+            ls.G = (const GramPair<R> *)sw.G + sg.begin * sw.g_per_step;
+        }
+        return sw.use_bi ? launch_bi<R>(ls) : launch_la<R>(ls);
+    }
+    TrainArgs<R> ts = sw.ta;
+    ts.wx = b.Y; ts.nseg = sg.S; ts.seg_begin = sg.begin; ts.seg_len = sg.len; ts.seg_extra = sg.extra; ts.seg_tail = sg.tail; ts.seg_iter = it; ts.skip = &b.ctrl->done;
+    pit_last_launch() = PitLaunch{4, 0, 0, 0, 0, 0};
+    return launch_any<R>(ts);
+}
+// one capture over several processes: the end taps of the segments trained elsewhere arrive through the caller's
+// all-reduce (zeros here, the trained taps there); from then on every process works on identical data
+template <typename R> int pit_exchange(const PitSweep<R> &sw)
+{
+    Cx<R> *Y = sw.b.Y;
+    const int S = sw.pl.sg.S, own_end = sw.own_first + sw.own_count;
+    if (sw.own_first > 0) QH_HIP(hipMemsetAsync(Y, 0, (size_t)sw.own_first * sw.wbytes, g_stream));
+    if (own_end < S) QH_HIP(hipMemsetAsync(Y + (size_t)own_end * sw.wset, 0, (size_t)(S - own_end) * sw.wbytes, g_stream));
+    if (!sw.xchg_async) QH_HIP(hipStreamSynchronize(g_stream));
+    if (sw.o.exchange(sw.o.exchange_user, Y, (size_t)S * sw.wbytes) != 0) { set_error("train_equaliser: the exchange callback failed"); return QH_ERR_ARG; }
+    return QH_OK;
+}
+// ---- analysis of a pass: boundary defects -> gauge -> defect vectors in the eigenbasis -> scan (the next correction,
+// and - weighted with the eigenvalues - the estimate of how far this pass is from the sequential recurrence) -> decision.
+// Eigen form (complex64): all of it in the eigenbasis; with the fused tail the last launch also writes the start taps of pass p + 1.
+template <typename R> int pit_analyse_eig(const PitSweep<R> &sw, const PitEvents &ev, int p, const PitFuse<R> &fz, int &back_done_for)
+{
+    const PitBuffers<R> &b = sw.b; const PitSeg &sg = sw.pl.sg;
+    const int ntot = sw.ntot, ncol = sw.ncol, nsel = sw.nsel, nbnd = (int)((sg.S - 1) * nsel), nprod = (ncol + PIT_MC - 1) / PIT_MC;
+    const PitCtrl *ctrl = b.ctrl;
+    const float damp = (sw.adaptive && p >= 1) ? sw.ad_damp : 1.f;
+    int rc = pit_wait_basis(sw.o);
+    if (rc) return rc;
+    if (p == 0 && sw.ssb) QH_HIP(hipStreamWaitEvent(g_stream, pit_model_sync().done, 0));       // the sweep's coarse model (other stream)
+    // Start and end taps of this pass into the eigenbasis, both products in ONE launch (a launch is ~4.5 us whatever it does) - in EVERY pass
+    // (round 5).  Rounds 3-4 projected the start taps once per sweep and kept x~ up to
+    // date in the eigenbasis (x~ <- theta x~ + D~, pit_recur_eig_kernel) while the back product updated X itself (X <- theta X + V D~).
+    // The two copies part by the rounding of the products and by what V lacks to be unitary (7e-6 per entry, single-precision Jacobi)
+    // times the correction - ~1e-6 per boundary, the same sign from boundary to boundary - and a fixed point of the TRACKED copy
+    // leaves exactly that as a true defect at every boundary; the weakly excited directions (coefficient ~1) add them up over the
+    // whole sweep: 1.0-1.7e-3 of tap deviation at C3 whatever the tolerance, invisible to the estimate (profiles/r05_tap_floor.txt).
+    PitFuse<R> f2 = fz;
+    f2.T2 = (const Cx<R> *)b.Y; f2.Out2 = reinterpret_cast<float2 *>(b.Ye);
+    hipLaunchKernelGGL((pit_basis_mfma_kernel<R, 0>), dim3(2 * nprod), dim3(pit_mfma_threads(ntot)), pit_mfma_lds(ntot), g_stream, b.Vb, (const Cx<R> *)b.X, (const Zf *)nullptr, b.Xe, ntot, ncol, ctrl, f2);
+    hipLaunchKernelGGL(pit_bound_kernel, dim3((nbnd + nsel + 3) / 4), dim3(256), 0, g_stream, (const Zf *)b.Xe, (const Zf *)b.Ye, (const Zf *)b.Yprev, b.lam, ntot, sg.S, nsel, sw.sym,
+                       ctrl, b.dfc, b.pw, b.gph, b.ualpha);
+    hipLaunchKernelGGL((pit_gauge_kernel<R>), dim3(sw.ssb ? 2 : 1), dim3(PIT_GT_THREADS), 0, g_stream, (const double *)b.gph, sg.S, nsel, b.ctrl, b.theta, (const double *)b.pw,
+                       nbnd, sw.method, (const Cx<R> *)sw.symbols + (size_t)sw.modes[0] * sw.nsy, 1, (const PitModel *)b.model, (const float4 *)b.ualpha, b.uqv,
+                       (const R *)sw.mu_dev, sg.len, (const float *)b.M);
+    hipLaunchKernelGGL((pit_recur_eig_kernel<R>), dim3(ntot, nsel), dim3(PIT_RT), 0, g_stream, b.Xe, (const Zf *)b.Ye, b.Dz[1], (const double *)b.theta, b.lam, nsel, sg.S, sg.len,
+                       (const R *)sw.mu_dev, sw.beta, ctrl, (const float *)b.M, damp, (const float4 *)b.ualpha, (const float2 *)b.uqv);
+    if (!sw.tail_fused) {
+        hipLaunchKernelGGL((pit_devest_kernel<R>), dim3(sw.ndev), dim3(256), 0, g_stream, (const Zf *)b.Dz[1], b.lam, ntot, ncol, ctrl, b.devmax, b.ticket, pit_decide_args(sw, ev, p, true, true));
+        return QH_OK;
+    }
+    // (whether or not pass p + 1 will be enqueued: the product blocks of a tail behind the last pass write start taps nobody reads)
+    const int nt_prod = pit_mfma_threads(ntot);
+    PitFuse<R> fn = fz;
+    fn.damp = 1.f;                                   // (the next pass's: not adaptive)
+    hipLaunchKernelGGL((pit_tail_kernel<R>), dim3(sw.ndev + nprod), dim3(nt_prod > 256 ? nt_prod : 256), pit_mfma_lds(ntot), g_stream, (const Zf *)b.Dz[1], b.lam, ntot, ncol, ctrl, b.devmax,
+                       b.ticket, sw.ndev, pit_decide_args(sw, ev, p, true, true), b.Vb + (size_t)ntot * ntot, fn, nt_prod);
+    back_done_for = p + 1;
+    return QH_OK;
+}
+// Probe form (complex128; complex64 under qh_set_form("pit_probe", "1")): the defect vectors are formed in double precision on a probe of the
+// capture before they are projected; without a coarse correction the decision follows the gauge directly.
+template <typename R> int pit_analyse_probe(const PitSweep<R> &sw, const PitEvents &ev, int p, const PitFuse<R> &fz)
+{
+    const PitBuffers<R> &b = sw.b; const PitSeg &sg = sw.pl.sg;
+    const int ntot = sw.ntot, ncol = sw.ncol, nsel = sw.nsel, nbnd = (int)((sg.S - 1) * nsel);
+    const PitCtrl *ctrl = b.ctrl;
+    const size_t dlds = (2 * (size_t)ntot + (size_t)sw.nmodes * sw.os * pit_phase_pitch(sw.ntaps, sw.os, PIT_PROBE)) * sizeof(Cx<R>);
+    QH_REQUIRE(dlds <= 60 * 1024, "train_equaliser: boundary probe does not fit the LDS for this filter shape");
+    hipLaunchKernelGGL((pit_defect_kernel<R>), dim3(sg.S, nsel), dim3(PIT_PROBE), dlds, g_stream, (const Cx<R> *)sw.E, sw.nmodes, sw.L, sw.os,
+                       sw.ntaps, sg, sw.TrSyms, (const int64_t *)b.modes_dev, (const Cx<R> *)b.X, (const Cx<R> *)b.Y, sw.sym, ctrl, b.dfc, b.pw, b.gph, (const Cx<R> *)sw.wx);
+    hipLaunchKernelGGL((pit_gauge_kernel<R>), dim3(1), dim3(PIT_GT_THREADS), 0, g_stream, (const double *)b.gph, sg.S, nsel, b.ctrl, b.theta, (const double *)b.pw,
+                       nbnd, sw.method, (const Cx<R> *)sw.symbols + (size_t)sw.modes[0] * sw.nsy, sw.want_corr ? 1 : 0);
+    if (!sw.want_corr) {
+        hipLaunchKernelGGL((pit_decide_kernel<R>), dim3(1), dim3(256), 0, g_stream, pit_decide_args(sw, ev, p, false, false));
+        return QH_OK;
+    }
+    const int rc = pit_wait_basis(sw.o);
+    if (rc) return rc;
+    hipLaunchKernelGGL((pit_cgemm_kernel<R, true>), dim3((ncol + PIT_GT - 1) / PIT_GT), dim3(256), sw.glds, g_stream, b.Vb, (const Zf *)nullptr, b.Dz[1], ntot, ncol, ctrl, fz);
+    hipLaunchKernelGGL((pit_recur_kernel<R>), dim3(ntot, nsel), dim3(256), 0, g_stream, b.Dz[1], b.lam, nsel, sg.S, sg.len, (const R *)sw.mu_dev, sw.beta, ctrl);
+    hipLaunchKernelGGL((pit_devest_kernel<R>), dim3(sw.ndev), dim3(256), 0, g_stream, (const Zf *)b.Dz[1], b.lam, ntot, ncol, ctrl, b.devmax, b.ticket, pit_decide_args(sw, ev, p, true, false));
+    return QH_OK;
+}
+template <typename R> int pit_enqueue_pass(const PitSweep<R> &sw, const PitEvents &ev, int it, int p, int &back_done_for)
+{
+    const PitBuffers<R> &b = sw.b;
+    ((volatile float *)ev.hview)[2 * p] = -1.f;             // "not decided yet": pit_decide_kernel overwrites it (polled by pit_wait_decision)
+    PitFuse<R> fz;
+    fz.X = b.X; fz.Y = b.Y; fz.theta = b.theta; fz.modes_dev = (const int64_t *)b.modes_dev; fz.nmodes = sw.nmodes; fz.nsel = sw.nsel;
+    fz.damp = (sw.adaptive && p > 1) ? sw.ad_damp : 1.f;      // (the first correction - from the seeds to the trajectory - in full)
+    fz.x_only = sw.tail_fused ? 1 : 0;
+    int rc = pit_start_taps(sw, p, fz, back_done_for);
+    if (rc) return rc;
+    if (sw.o.on_pass) {
+        // the caller's chip-wide work for other streams, to run BESIDE this pass's trainer: an event recorded here is behind everything of the
+        // pass before (its back product), so what is gated on it starts with the trainer - not in the analysis behind it, where it would share
+        // the chip with the control path, which is the critical path (hook behind the trainer launch: gaps of 88-90 instead of 70-75 us between
+        // the passes, C3 1137-1146 against 1163-1167 MSym/s)
+        hipStream_t keep = g_stream;
+        sw.o.on_pass(sw.o.on_pass_user, it, p);
+        g_stream = keep;
+    }
+    if (pit_timed(sw, p)) QH_HIP(hipEventRecord(ev.t0[p], g_stream));
+    if ((rc = pit_train_pass(sw, it))) return rc;
+    if (pit_timed(sw, p)) QH_HIP(hipEventRecord(ev.t1[p], g_stream));
+    if (sw.split && (rc = pit_exchange(sw))) return rc;
+    if ((rc = sw.eig ? pit_analyse_eig(sw, ev, p, fz, back_done_for) : pit_analyse_probe(sw, ev, p, fz))) return rc;
+    QH_HIP(hipGetLastError());
+    return QH_OK;
+}
+// the decision of pass p: polled in pinned memory (an event here would idle the stream for ~5.6 us per pass); the stream
+// going idle without a decision means a launch failed or the sweep was already done
+inline int pit_wait_decision(const PitEvents &ev, int p)
+{
+    volatile float *hv = (volatile float *)ev.hview;
+    unsigned spins = 0;
+    auto t_last = std::chrono::steady_clock::now();
+    while (hv[2 * p] < 0.f) {
+        if ((++spins & 255u) != 0) continue;
+        const auto now = std::chrono::steady_clock::now();
+        if (now - t_last < std::chrono::milliseconds(20)) continue;     // (a stream query puts a marker into the queue: rarely)
+        t_last = now;
+        const hipError_t q = hipStreamQuery(g_stream);
+        if (q == hipSuccess) { if (hv[2 * p] < 0.f) hv[2 * p] = 2.f; break; }       // (nothing decided: treated as not certified)
+        if (q != hipErrorNotReady) QH_HIP(q);
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return QH_OK;
+}
+// ---- the stages of a sweep ahead of its passes
+// first sweep of a cold start: adopt the acquisition that ran ahead of the call (qh_pit_prepare_*_dev, on another stream beside the previous capture's
+// training), or run it here.  acq_timed: its event pair was recorded (read when the passes are through)
+template <typename R> int pit_acquire_or_adopt(const PitSweep<R> &sw, const PitEvents &ev, bool &acq_timed)
+{
+    const PitBuffers<R> &b = sw.b;
+    const unsigned nblk = (unsigned)((sw.wset + 255) / 256);
+    if (sw.prepared) {
+        const PitPrepLayout lay = pit_prep_layout<R>(sw.nmodes, sw.ntaps, sw.pl.amax);
+        const char *pb = (const char *)sw.o.prepared;
+        hipLaunchKernelGGL((pit_adopt_kernel<R>), dim3(nblk), dim3(256), 0, g_stream, (Cx<R> *)sw.wx, (const Cx<R> *)(pb + lay.wx), (int)sw.wset,
+                           (const PitCtrl *)(pb + lay.ctrl), b.ctrl, b.mu_acq, (const R *)(pb + lay.mu_acq));
+    } else if (sw.o.acquire) {
+        // All chunks are enqueued at once and the host does not wait for any of them: once the plateau is reached (or the run diverged) the
+        // monitor sets acq_done on the device and the chunks behind it return at once, and everything downstream reads the device's flags.
+        // (Rounds 2-3 waited for every chunk's flag: ~30 us of idle GPU after the last one.)  One event pair around the run times it.
+        if (sw.pl.nchunks > 0) { QH_HIP(hipEventRecord(ev.t0[PIT_NEV - 1], g_stream)); acq_timed = true; }
+        const int rc = pit_acq_enqueue<R>(sw.pl, sw.block_form ? &sw.la : nullptr, sw.use_bi, &sw.ta, (Cx<R> *)sw.wx, (Cx<R> *)sw.err, sw.TrSyms * sw.Niter, b.ctrl, b.mu_acq, sw.mu_dev,
+                                          b.modes_dev, sw.nsel);
+        if (rc) return rc;
+        if (sw.pl.nchunks > 0) QH_HIP(hipEventRecord(ev.t1[PIT_NEV - 1], g_stream));
+        hipLaunchKernelGGL((pit_acq_finish_kernel<R>), dim3(nblk), dim3(256), 0, g_stream, (Cx<R> *)sw.wx, (const Cx<R> *)b.w_start, (int)sw.wset, b.ctrl);
+    } else
+        return QH_OK;
+    QH_HIP(hipGetLastError());
+    return QH_OK;
+}
+// the head of sweep `it` in the exact form: the adaptive step's (its taps and step are kept for the way out), or a fixed step's exact head
+template <typename R> int pit_sweep_head(const PitSweep<R> &sw, int it)
+{
+    const PitBuffers<R> &b = sw.b;
+    const int64_t head = sw.head, TrSyms = sw.TrSyms;
+    const int S = sw.pl.sg.S;
+    Cx<R> *err = (Cx<R> *)sw.err;
+    int rc;
+    if (sw.adaptive) {
+        const int64_t m0 = sw.modes[0];
+        QH_HIP(hipMemcpyAsync(b.w_start, sw.wx, sw.wbytes, hipMemcpyDeviceToDevice, g_stream));
+        QH_HIP(hipMemcpyAsync(b.mu_saved, sw.mu_dev, sizeof(R), hipMemcpyDeviceToDevice, g_stream));
+        if ((rc = train_dev<R>(sw.E, sw.nmodes, sw.L, head, 1, sw.os, sw.mu_dev, sw.wx, sw.ntaps, sw.modes, 1, 1, sw.symbols, sw.nsy, sw.method, b.errh, 0, nullptr))) return rc;
+        QH_HIP(hipMemcpyAsync(err + (size_t)m0 * TrSyms, b.errh + (size_t)m0 * head, (size_t)head * sizeof(Cx<R>), hipMemcpyDeviceToDevice, g_stream));
+        hipLaunchKernelGGL((pit_adapt_init_kernel<R>), dim3((S + 255) / 256), dim3(256), 0, g_stream, (const R *)sw.mu_dev, (const Cx<R> *)(b.errh + (size_t)m0 * head + head - 1), S, b.rS, b.eS);
+        QH_HIP(hipGetLastError());
+    } else if (head > 0) {
+        if ((rc = train_dev<R>(sw.E, sw.nmodes, sw.L, head, 1, sw.os, sw.mu_dev, sw.wx, sw.ntaps, sw.modes, sw.nsel, 0, sw.symbols, sw.nsy, sw.method, b.errh, 0, nullptr))) return rc;
+        for (int j = 0; j < sw.nsel; j++)
+            QH_HIP(hipMemcpyAsync(err + (size_t)sw.modes[j] * TrSyms * sw.Niter + (size_t)it * TrSyms, b.errh + (size_t)sw.modes[j] * head, (size_t)head * sizeof(Cx<R>),
+                                  hipMemcpyDeviceToDevice, g_stream));
+    }
+    return QH_OK;
+}
+// pass-0 start taps of sweep `it` (phase seeds, unwrap, seed; the per-sweep fields of the control block are reset by pit_seed_kernel) and its coarse model
+template <typename R> int pit_seed_sweep(const PitSweep<R> &sw, int it)
+{
+    const PitBuffers<R> &b = sw.b; const PitSeg &sg = sw.pl.sg;
+    if (sw.seed_phase) {
+        int nwin = PIT_SEEDWIN;                                   // head staged in LDS: shortened until it fits the default 64 KiB
+        auto phase_lds = [&](int nw) { return ((size_t)sw.ntot + (size_t)sw.nmodes * sw.os * pit_phase_pitch(sw.ntaps, sw.os, nw)) * sizeof(Cx<R>); };
+        while (nwin > 32 && phase_lds(nwin) > 60 * 1024) nwin /= 2;
+        QH_REQUIRE(phase_lds(nwin) <= 60 * 1024, "train_equaliser: phase seeding does not fit the LDS for this filter shape (pass phase_seed = 0)");
+        hipLaunchKernelGGL((pit_phase_kernel<R>), dim3(sg.S, sw.nsel), dim3(256), phase_lds(nwin), g_stream, (const Cx<R> *)sw.E, sw.nmodes, sw.L, sw.os,
+                           (const Cx<R> *)sw.wx, sw.ntaps, sg, (const int64_t *)b.modes_dev, nwin, b.z);
+        hipLaunchKernelGGL(pit_unwrap_kernel, dim3(sw.nsel), dim3(256), 0, g_stream, (const double *)b.z, sg.S, sw.nsel, b.rot, b.uw_phi, b.uw_jump);
+    }
+    // segment 0 starts from the taps the sweep starts from in the reference (before the acquisition moved them), unrotated
+    const Cx<R> *w_exact = sw.o.start == 1 ? nullptr : ((it == 0 && sw.o.acquire) ? (const Cx<R> *)b.w_start : (const Cx<R> *)sw.wx);
+    hipLaunchKernelGGL((pit_seed_kernel<R>), dim3(sg.S), dim3(256), 0, g_stream, (const Cx<R> *)sw.wx, sw.nmodes, sw.ntot, (const int64_t *)b.modes_dev, sw.nsel, sw.rot_use, b.X, w_exact, b.Y, b.ctrl);
+    if (sw.ssb) {
+        // the coarse model of this sweep, measured at its seed taps: two small launches on the library's helper stream, beside pass 0 (which
+        // does not need it; its analysis waits for it) and beside the basis build of a cold sweep on the other stream.
+        PitModelSync &ms = pit_model_sync();
+        if (!ms.seed) { QH_HIP(hipEventCreateWithFlags(&ms.seed, hipEventDisableTiming)); QH_HIP(hipEventCreateWithFlags(&ms.done, hipEventDisableTiming)); }
+        hipStream_t ss = helper_stream();
+        QH_HIP(hipEventRecord(ms.seed, g_stream));
+        QH_HIP(hipStreamWaitEvent(ss, ms.seed, 0));
+        hipLaunchKernelGGL((pit_model_kernel<R, 0>), dim3(PIT_MODB), dim3(256), 0, ss, sw.ma);
+        hipLaunchKernelGGL((pit_model_kernel<R, 1>), dim3(PIT_MODB), dim3(256), 0, ss, sw.ma);
+        QH_HIP(hipEventRecord(ms.done, ss));
+    }
+    QH_HIP(hipGetLastError());
+    return QH_OK;
+}
+// ---- the relaxation passes of sweep `it`.  certified: the sweep's last decision was "stopped AND below the tolerance".
+// Pass p + 1 is enqueued BEFORE the host has seen the flag of pass p - unless pass p is expected to be the last one, since
+// a pass enqueued in vain costs a dozen empty launches (~55 us), about as much as the idle round trip it would save:
+// expected defect of pass p = PIT_CONTRACT x the defect of pass p - 1 (the first pass never converges from seeds).
+template <typename R> int pit_run_passes(const PitSweep<R> &sw, const PitEvents &ev, int it, bool &certified)
+{
+    PitTiming &tm = pit_timing();
+    int back_done_for = 0, rc;
+    certified = false;
+    if ((rc = pit_enqueue_pass(sw, ev, it, 0, back_done_for))) return rc;
+    if (it == 0 && sw.o.on_pass0) {                              // the caller's work for the other streams: enqueued while pass 0 keeps the device busy
+        hipStream_t keep = g_stream;
+        sw.o.on_pass0(sw.o.on_pass0_user);
+        g_stream = keep;
+    }
+    for (int p = 0; p < sw.npass; p++) {
+        // (expected criterion of pass p: the last one times the contraction the last two passes showed; the first guess is PIT_CONTRACT)
+        double contr = PIT_CONTRACT;
+        if (p >= 2 && ev.hview[2 * (p - 2) + 1] > 0) {
+            contr = (double)ev.hview[2 * (p - 1) + 1] / (double)ev.hview[2 * (p - 2) + 1];
+            contr = contr < 0.1 ? 0.1 : (contr > 0.9 ? 0.9 : contr);
+        }
+        const bool expect_last = p > 0 && contr * (double)ev.hview[2 * (p - 1) + 1] < sw.tol;
+        bool ahead = false;                                       // pass p + 1 already in the stream
+        if (p + 1 < sw.npass && !expect_last && (!sw.split || sw.xchg_async)) { if ((rc = pit_enqueue_pass(sw, ev, it, p + 1, back_done_for))) return rc; ahead = true; }   // (a host-side exchange cannot be enqueued ahead)
+        if ((rc = pit_wait_decision(ev, p))) return rc;
+        if (pit_timed(sw, p) && tm.npass < QH_PIT_MAXPASS) {
+            float ms = 0;
+            QH_HIP(hipEventSynchronize(ev.t1[p]));
+            QH_HIP(hipEventElapsedTime(&ms, ev.t0[p], ev.t1[p]));
+            tm.pass_ms[tm.npass++] = ms;
+        }
+        if (ev.hview[2 * p] != 0.f) { certified = ev.hview[2 * p] == 1.f; break; }
+        if (p + 1 < sw.npass && !ahead && (rc = pit_enqueue_pass(sw, ev, it, p + 1, back_done_for))) return rc;
+    }
+    return QH_OK;
+}
+// ---- ways out of a sweep the passes did not certify
+// Stalled on the START of the sweep?  A stage that begins far from its own fixed point - a decision-directed stage whose start
+// taps were locked to the carrier phase at the END of the capture - goes through a non-linear pull-in that the passes can only
+// follow at the speed of plain relaxation (measured, 64-QAM mcma -> sbd: the bulk of the sweep converged after two passes, a
+// front of ~0.1 deviation moved 1.5 segments per pass).  If the estimate of the last pass sits in the first quarter of the
+// segments only, the call is repeated with that stretch (+ a margin) as an EXACT head: sequential there, parallel after it.
+// retried: the call was repeated and the return value is its result.
+template <typename R> int pit_retry_with_head(const PitSweep<R> &sw, bool &retried)
+{
+    const PitBuffers<R> &b = sw.b; const PitSeg &sg = sw.pl.sg;
+    retried = false;
+    if (!sw.eig) return QH_OK;
+    double hp = 0;
+    int hfront[2] = {-1, 0};
+    QH_HIP(hipMemcpyAsync(&hp, &b.ctrl->out_power, sizeof(double), hipMemcpyDeviceToHost, g_stream));
+    QH_HIP(hipStreamSynchronize(g_stream));
+    QH_HIP(hipMemcpyAsync(b.front, hfront, sizeof(hfront), hipMemcpyHostToDevice, g_stream));
+    hipLaunchKernelGGL(pit_front_kernel, dim3((sw.ncol + 255) / 256), dim3(256), 0, g_stream, (const Zf *)b.Dz[1], b.lam, sw.ntot, sw.ncol, sw.tol * sw.tol * (hp > 0 ? hp : 1.0), b.front, b.front + 1);
+    QH_HIP(hipMemcpyAsync(hfront, b.front, sizeof(hfront), hipMemcpyDeviceToHost, g_stream));
+    QH_HIP(hipStreamSynchronize(g_stream));
+    const bool finite = hp > 0 && hfront[1] == 0;
+    const int front = hfront[0];
+    const int64_t front_seg = front < 0 ? -1 : front / sw.nsel + 1;      // one past the last segment above the tolerance
+    if (!finite || front < 0 || front_seg > sg.S / 4) return QH_OK;
+    int64_t hs = front_seg + 8 + (front_seg + 1) / 2;                 // margin: the front keeps moving while the head is redone
+    if (hs > sg.S - 4) hs = sg.S - 4;
+    const int64_t new_head = sg.start(hs);
+    if (!(new_head > sw.head && new_head < sw.TrSyms && new_head <= 0x7fffffff)) return QH_OK;
+    QH_HIP(hipMemcpyAsync(sw.wx, b.w_call, sw.wbytes, hipMemcpyDeviceToDevice, g_stream));
+    qh_pit_opts o2 = sw.o;                                            // (what the call changed in it is set here too)
+    o2.head_steps = (int32_t)new_head; o2.acquire = 0; o2.segments = 0;
+    retried = true;
+    return train_pit_dev<R>(sw.E, sw.nmodes, sw.L, sw.TrSyms, sw.Niter, sw.os, sw.mu_dev, sw.wx, sw.ntaps, sw.modes, sw.nsel, sw.symbols, sw.nsy, sw.method, sw.err, 0, sw.gram, &o2, sw.report_dev,
+                            sw.depth + 1);
+}
+// End of an adaptive sweep: the step the last segment ended with goes back to the caller.  A sweep the passes cannot agree on - the later
+// modes of a BLIND stage, which start from centre-spike taps with the tiny step the first mode left behind: no linear model describes that -
+// ends not converged after a few passes; the call then does what the reference does: the exact form from the saved taps and step size
+// (report: converged = 2; fell_back says so).
+template <typename R> int pit_adaptive_finish(const PitSweep<R> &sw, bool &fell_back)
+{
+    const PitBuffers<R> &b = sw.b;
+    hipLaunchKernelGGL((pit_adapt_finish_kernel<R>), dim3(1), dim3(1), 0, g_stream, sw.mu_dev, (const R *)b.rE, sw.pl.sg.S);
+    int32_t conv = 0;
+    QH_HIP(hipMemcpyAsync(&conv, &b.ctrl->converged, sizeof(conv), hipMemcpyDeviceToHost, g_stream));
+    QH_HIP(hipStreamSynchronize(g_stream));
+    if (conv || !sw.redo_ok) return QH_OK;
+    fell_back = true;
+    QH_HIP(hipMemcpyAsync(sw.wx, b.w_start, sw.wbytes, hipMemcpyDeviceToDevice, g_stream));
+    QH_HIP(hipMemcpyAsync(sw.mu_dev, b.mu_saved, sizeof(R), hipMemcpyDeviceToDevice, g_stream));
+    return pit_exact_form(sw, b.ctrl, 1, 0, nullptr, -1);       // (Niter = 1, nsel = 1: see the exact-only way out of train_pit_dev)
+}
+// ---- what train_pit_dev decides before the first sweep
+// exact head and segment grid: sw.head, sw.pl (and o.acquire cleared where a head seeds the segments)
+template <typename R> int pit_plan_grid(PitSweep<R> &sw)
+{
+    qh_pit_opts &o = sw.o;
+    const int64_t TrSyms = sw.TrSyms;
+    const bool adaptive = sw.adaptive;
     int S = o.segments;
     // adaptive step: the first 16384 steps (while the step is large) in the exact form, then segments of 2048 steps
-    const float ad_relax = 1.0f, ad_damp = 0.7f;                  // (measured: profiles/r03_adaptive_tier_b.txt)
-    const int ad_newton = 1;
     const int64_t head_want = 16384;
     // Fixed step: opts.head_steps > 0 - the first head_steps steps of every sweep in the exact form, the segments cover the rest (what the
-    // automatic way out below uses when the passes stall on a transient at the start of the sweep that no linear model describes)
+    // automatic way out, pit_retry_with_head, uses when the passes stall on a transient at the start of the sweep that no linear model describes)
     int64_t head = adaptive ? ((TrSyms / 4 < head_want ? TrSyms / 4 : head_want) / LA_B * LA_B) : 0;
     if (!adaptive && o.head_steps > 0) {
         QH_REQUIRE(!o.exchange, "train_equaliser: a capture split over processes takes no exact head");
@@ -2458,7 +2917,7 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
     // with the number of segments (2^22 symbols: 2039 segments of 2048 steps meet tol / 3 only at the 24-pass cap or not at all, 509
     // segments of 8192 steps in 12-14 passes; the decision-directed stage needs 5-7 passes either way and is faster with short segments)
     int64_t seg_want = 2048;
-    if (adaptive && !(method == QH_M_SBD || method == QH_M_MDDMA || method == QH_M_DD)) {
+    if (adaptive && !(sw.method == QH_M_SBD || sw.method == QH_M_MDDMA || sw.method == QH_M_DD)) {
         const int64_t t = ((TrSyms - head) / 512 + LA_B - 1) / LA_B * LA_B;
         if (t > seg_want) seg_want = t;
     }
@@ -2466,159 +2925,174 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
     if (S == 0) {
         R mu_h = (R)o.mu_hint;                                    // the caller's host copy of the step, if it gave one: no read-back, no synchronisation
         if (!(o.mu_hint > 0)) {
-            QH_HIP(hipMemcpyAsync(&mu_h, mu_dev, sizeof(R), hipMemcpyDeviceToHost, g_stream));
+            QH_HIP(hipMemcpyAsync(&mu_h, sw.mu_dev, sizeof(R), hipMemcpyDeviceToHost, g_stream));
             QH_HIP(hipStreamSynchronize(g_stream));
         }
-        S = pit_auto_segments(TrSyms, (double)mu_h, nsel, o.acquire);
+        S = pit_auto_segments(TrSyms, (double)mu_h, sw.nsel, o.acquire);
     }
-    PitPlan pl = pit_plan(o, TrSyms, head, S, adaptive, o.acquire ? o.acq_chunk : 0);
+    sw.head = head;
+    sw.pl = pit_plan(o, TrSyms, head, S, adaptive, o.acquire ? o.acq_chunk : 0);
+    return QH_OK;
+}
+// the form of the passes and of their analysis, from the trainer form f that takes the segments
+template <typename R> int pit_decide_form(PitSweep<R> &sw, const TrainerForm &f)
+{
+    const qh_pit_opts &o = sw.o;
+    const PitSeg &sg = sw.pl.sg;
+    const int method = sw.method;
+    sw.decision = method == QH_M_SBD || method == QH_M_MDDMA || method == QH_M_DD;
+    sw.seg_form = f.seg; sw.use_bi = f.use_bi; sw.block_form = f.block; sw.pair_tab = f.pair_tab;
+    sw.split = o.exchange != nullptr;
+    sw.own_first = sw.split ? o.seg_first : 0; sw.own_count = sw.split ? o.seg_count : sg.S;
+    sw.xchg_async = sw.split && o.exchange_on_stream != 0;
+    if (sw.split) {
+        QH_REQUIRE(sw.seg_form, "train_equaliser: a capture split over processes needs the throughput form of the passes (>= 512 chains, supported tap layout)");
+        QH_REQUIRE(sw.own_first >= 0 && sw.own_count >= 0 && sw.own_first + sw.own_count <= sg.S, "train_equaliser: owned segments outside the segment grid");
+        QH_REQUIRE(sw.Niter == 1, "train_equaliser: a capture split over processes is trained in one sweep");
+    }
+    sw.wset = (size_t)sw.nmodes * sw.ntot; sw.wbytes = sw.wset * sizeof(Cx<R>);
+    sw.ncol = sg.S * sw.nsel; sw.ndev = (sw.ncol + 63) / 64;
+    sw.g_per_step = sw.pair_tab ? LA_B : GRAM_TRI / 2 / LA_B;
+    sw.glds = ((size_t)PIT_EIGMAX * PIT_EIGMAX + (size_t)PIT_EIGMAX * PIT_GT) * sizeof(Zf);
+    sw.prepared = o.prepared != nullptr && o.acquire && !sw.adaptive && sw.head == 0 && sw.Niter >= 1;
+    // complex64: the analysis of a pass runs in the eigenbasis (pit_analyse_eig); complex128 keeps the probe-based analysis, whose defect vectors
+    // are formed in double precision before they are projected (qh_set_form("pit_probe", "1") forces it for complex64 too: tests compare the two)
+    sw.eig = sw.want_corr && sizeof(R) == 4 && form(FORM_PIT_PROBE) == 0;
+    // The tail of a pass - estimate, decision, and the back product for the next pass - in one launch (pit_tail_kernel) where the trainer can
+    // read its start taps from X and write its end taps to Y: the throughput form of a fixed-step sweep of a whole capture under the eigen-space
+    // analysis.  Every other case keeps the two launches (qh_set_form("pit_tail", "split") forces them: tests compare the two).
+    sw.tail_fused = sw.eig && sw.seg_form && !sw.adaptive && !sw.split && form(FORM_PIT_TAIL) == 0;
+    // Measured coarse model (pit_model_kernel): gain and the 2 x 2 block of the signal direction from the capture itself.  complex128, cma2 and
+    // decision methods whose passes run in neither the segment nor the block-iterative form keep round 3's model (one formula gain per error
+    // function, diagonal in the eigenbasis, extra damping beta).
+    const bool tables_ok = method == QH_M_CMA || method == QH_M_SGNCMA || method == QH_M_MCMA || method == QH_M_RDE || method == QH_M_MRDE ||
+                           (sw.decision && (sw.use_bi || sw.seg_form));
+    sw.ssb = sw.eig && tables_ok && method != QH_M_CMA2;
+    sw.beta = o.corr_beta >= 0 ? o.corr_beta : ((sw.sym == 0 && !sw.ssb) ? 1.5 : 0.0);       // (round-3 model only: the measured model needs no extra damping)
+    // Way out (every tier-b call returns the reference's result): a sweep the passes do not certify - estimate stuck above tol, pass
+    // budget used up, no coarse model to certify with - is redone in the EXACT form from the taps the call started with, inside the
+    // call (report: converged = 2, pit_exact_form).  opts.exact_redo_off != 0 leaves the uncertified result in place (converged = 0): for
+    // the tests of the iteration itself.
+    sw.redo_ok = o.exact_redo_off == 0;
+    sw.timing_mode = pit_timing_mode();                // (qh_set_pit_timing; the environment variable QAMPY_HIP_PIT_TIMING = all | none is its initial value)
+    return QH_OK;
+}
+// the arguments of the coarse-model kernels (sw.b carved, sw.rot_use set)
+template <typename R> void pit_model_args(PitSweep<R> &sw, const TrainerForm &f)
+{
+    PitModelArgs<R> &ma = sw.ma;
+    ma.part = sw.b.part; ma.u = sw.b.u; ma.model = sw.b.model; ma.ticket = sw.b.model_ticket;
+    ma.E = (const Cx<R> *)sw.E; ma.wx = (const Cx<R> *)sw.wx; ma.L = sw.L; ma.TrSyms = sw.TrSyms; ma.nmodes = sw.nmodes; ma.ntaps = sw.ntaps; ma.os = sw.os; ma.nsel = sw.nsel; ma.method = sw.method;
+    if (sw.decision) { ma.symbols = (const Cx<R> *)f.dd_table; ma.nsy = 2 * f.dd_npart + 1; ma.sy_pitch = 2 * BI_DD_MAXLEV; ma.tables = 1; }
+    else { ma.symbols = (const Cx<R> *)sw.symbols; ma.nsy = sw.nsy; ma.sy_pitch = sw.nsy; ma.tables = (sw.method == QH_M_RDE || sw.method == QH_M_MRDE) ? 1 : 0; }
+    pit_fill_modes(ma.modes, sw.modes, sw.nsel);
+    ma.sg = sw.pl.sg; ma.rot = sw.rot_use;
+}
+
+// ---- the driver of a tier-b call: checks, the exact-only way out, grid, buffers, what the host must read back, tables and basis, then the sweeps
+template <typename R>
+int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Niter, int os, R *mu_dev, void *wx, int ntaps,
+                  const int64_t *modes, int nsel, const void *symbols, int64_t nsy, int method, void *err, int zero_err,
+                  const void *gram, const qh_pit_opts *opts, void *report_dev, int depth)
+{
+    pit_last_launch() = PitLaunch{0, 0, 0, 0, 0, 0};             // (qh_pit_last_launch: nothing but the exact form until a pass is enqueued; a refused call leaves zeros too)
+    int rc = ensure_init();
+    if (rc) return rc;
+    if ((rc = train_args_ok("train_equaliser", method, nmodes, ntaps, os, TrSyms, Niter, nsel, nsy, modes))) return rc;
+    QH_REQUIRE(TrSyms == 0 || (TrSyms - 1) * os + ntaps <= L, "train_equaliser: field shorter than TrSyms*os + ntaps");
+    PitSweep<R> sw{};
+    sw.E = E; sw.nmodes = nmodes; sw.L = L; sw.TrSyms = TrSyms; sw.Niter = Niter; sw.os = os; sw.mu_dev = mu_dev; sw.wx = wx; sw.ntaps = ntaps; sw.modes = modes; sw.nsel = nsel;
+    sw.symbols = symbols; sw.nsy = nsy; sw.method = method; sw.err = err; sw.gram = gram; sw.report_dev = report_dev; sw.depth = depth;
+    sw.o = opts ? *opts : pit_opts_default();
+    qh_pit_opts &o = sw.o;
+    PitBuffers<R> &b = sw.b;
+    QH_REQUIRE(o.segments >= 0 && o.segments <= PIT_MAXSEG && o.max_passes >= 0 && o.max_passes <= QH_PIT_MAXPASS, "train_equaliser: bad segment / pass count");
+    QH_REQUIRE(o.adaptive >= 0 && o.adaptive <= 2, "train_equaliser: adaptive must be 0, 1 or 2");
+    // Adaptive step (opts.adaptive = 1): ONE output mode per call (the reference carries one step size from mode to mode: the caller runs
+    // the modes in turn), one sweep, single precision, the error functions of train_seg_*_f32_ad.hip.  The head of the sweep runs in
+    // the exact form; the segments cover the rest, with r = 1 / mu and the previous error as boundary states (DESIGN.md 3.2.1).
+    // Tier b is TOTAL: a call for which no parallel-in-time solver exists - data-aided training (the symbols are indexed by the step:
+    // nothing to certify against a segment grid yet), the adaptive step with another error function / precision / several sweeps /
+    // several modes at once / one step size per mode (adaptive = 2) - takes the exact form right away and says so (report:
+    // segments = 1, converged = 2); the result is the reference's either way.
+    const bool adaptive = sw.adaptive = o.adaptive != 0;
+    const double tol0 = o.tol > 0 ? o.tol : 1e-3;
+    bool exact_only = method == QH_M_SBD_DATA;
+    if (adaptive && (o.adaptive == 2 || sizeof(R) != 4 || nsel != 1 || Niter != 1 || !seg_adaptive_supported(method))) exact_only = true;
+    QH_REQUIRE(!(adaptive && o.exchange), "train_equaliser: a capture split over processes is trained with a fixed step");
+    QH_REQUIRE(!(exact_only && o.exchange), "train_equaliser: a capture split over processes needs the parallel-in-time solver (blind / decision-directed method, fixed step)");
+    if ((rc = pit_carve_ctrl(b, report_dev))) return rc;
+    PitCtrl *ctrl = b.ctrl;
+    if (exact_only) {
+        pit_setup_launch<R>(E, nmodes, L, nmodes * ntaps, mu_dev, 1.0, 1.0, tol0, PitSeg{1, TrSyms, 0, 0}, ctrl, b.mu_acq);
+        return pit_exact_form(sw, ctrl, o.adaptive, zero_err, adaptive ? nullptr : gram, 0);
+    }
+    if (adaptive) o.acquire = 0;
+    const int ntot = sw.ntot = nmodes * ntaps;
+    // Adaptive sweeps apply 0.7 of every correction after the first (the full one overshoots: the estimate then GROWS 1.7 x per pass on the
+    // blind stage of the reference script's recipe; damped it falls 0.3-0.5 x per pass, profiles/r03_adaptive_tier_b.txt) and what is left
+    // of the early corrections sits in the result, so they are held to a third of the tolerance and may take 24 passes.
+    sw.npass = o.max_passes > 0 ? o.max_passes : (adaptive ? QH_PIT_MAXPASS : 16);
+    sw.tol = tol0 * (adaptive ? 1.0 / 3.0 : 1.0);
+    sw.safety = o.dev_safety > 0 ? o.dev_safety : PIT_DEV_SAFETY;
+    sw.sym = pit_symmetry(method);
+    sw.seed_phase = o.phase_seed < 0 ? sw.sym == 4 : o.phase_seed != 0;
+    sw.want_corr = o.correction != 0 && pit_basis_ok(ntot, sizeof(Cx<R>));
+
+    // ---- segment grid, report header
+    if ((rc = pit_plan_grid(sw))) return rc;
+    PitPlan &pl = sw.pl;
     const PitSeg &sg = pl.sg;
     if (zero_err) QH_HIP(hipMemsetAsync(err, 0, (size_t)nmodes * TrSyms * Niter * sizeof(Cx<R>), g_stream));
-    const int64_t npow = L < 4096 ? L : 4096;
-    hipLaunchKernelGGL((pit_setup_kernel<R>), dim3(1), dim3(256), 0, g_stream, (const Cx<R> *)E, nmodes, L, npow, ntot, (const R *)mu_dev, pl.gear, pl.bound, tol, sg, ctrl, mu_acq);
+    pit_setup_launch<R>(E, nmodes, L, ntot, mu_dev, pl.gear, pl.bound, sw.tol, sg, ctrl, b.mu_acq);
     QH_HIP(hipGetLastError());
     if (TrSyms == 0 || Niter == 0) return QH_OK;
     if (sg.S < 2) {                 // nothing to parallelise: the sequential path (report: one segment, one pass, defect 0)
         const double zero = 0;
         QH_HIP(hipMemcpyAsync(&ctrl->defect[0], &zero, sizeof(double), hipMemcpyHostToDevice, g_stream));
-        return exact_form(ctrl, adaptive ? 1 : 0, 0, gram, 1);
+        return pit_exact_form(sw, ctrl, adaptive ? 1 : 0, 0, gram, 1);
     }
-
     // ---- which exact form takes the segments; the adaptive solver needs the throughput form of the passes: a tap layout / alphabet
     // it cannot take runs in the exact form (converged = 2)
     TrainerForm f;
     if ((rc = trainer_form<R>(f, FORM_PASSES, method, adaptive, nmodes, ntaps, os, sg.len, (int64_t)sg.S * nsel, symbols, nsy, modes, nsel))) return rc;
-    if (adaptive && !f.seg) return exact_form(ctrl, 1, 0, nullptr, 0);
-    const bool decision = method == QH_M_SBD || method == QH_M_MDDMA || method == QH_M_DD;
-    const bool seg_form = f.seg, use_bi = f.use_bi, block_form = f.block, pair_tab = f.pair_tab;
-    const bool split = o.exchange != nullptr;
-    const int own_first = split ? o.seg_first : 0, own_count = split ? o.seg_count : sg.S;
-    const bool xchg_async = split && o.exchange_on_stream != 0;
-    if (split) {
-        QH_REQUIRE(seg_form, "train_equaliser: a capture split over processes needs the throughput form of the passes (>= 512 chains, supported tap layout)");
-        QH_REQUIRE(own_first >= 0 && own_count >= 0 && own_first + own_count <= sg.S, "train_equaliser: owned segments outside the segment grid");
-        QH_REQUIRE(Niter == 1, "train_equaliser: a capture split over processes is trained in one sweep");
-    }
+    if (adaptive && !f.seg) return pit_exact_form(sw, ctrl, 1, 0, nullptr, 0);
+    if ((rc = pit_decide_form(sw, f))) return rc;
 
     // ---- buffers
-    const size_t wset = (size_t)nmodes * ntot;
-    const size_t wbytes = wset * sizeof(Cx<R>);
-    void *wbuf = nullptr;
-    const size_t nsj = (size_t)sg.S * nsel;
-    const size_t bytes_w = ((2 * (size_t)sg.S + 2) * wbytes + 63) / 64 * 64;
-    if ((rc = scratch(Slot::PIT_WORK, bytes_w + 10 * nsj * sizeof(double) + (size_t)nsel * sizeof(int64_t) + 320 + nsj * 16 + 4 * ((nsj + 63) / 64) * sizeof(float) + 64, &wbuf))) return rc;
-    Cx<R> *X = (Cx<R> *)wbuf, *Y = X + (size_t)sg.S * wset, *w_start = Y + (size_t)sg.S * wset, *w_call = w_start + wset;
-    double *z = (double *)((char *)wbuf + bytes_w), *rot = z + 2 * nsj, *dfc = rot + 2 * nsj, *pw = dfc + nsj, *gph = pw + nsj, *theta = gph + 2 * nsj;
-    int64_t *modes_dev = (int64_t *)(theta + 2 * nsj);
-    double *uw_phi = (double *)(modes_dev + ((nsel + 7) / 8 * 8));
-    int *uw_jump = (int *)(uw_phi + (size_t)sg.S * nsel);
-    float *devmax = (float *)(uw_jump + (size_t)sg.S * nsel);                    // per-block maxima of the deviation estimate (ndev of them)
-    const int ndev = (int)((nsj + 63) / 64);                     // (four floats per block: worst column, sum, sum / worst of the tap norms)
-    unsigned *ticket = (unsigned *)(devmax + 4 * (size_t)ndev);  // pit_devest_kernel: which block finishes last
-    PitInit init{};                                              // (launched once, right before the sweeps: pit_init_kernel)
-    init.z[0] = ticket; init.zn[0] = sizeof(unsigned);
-    // adaptive step: r and previous error at the start / end of every segment, the sum of its step sizes, the change of the start values;
-    // error rows of the head (the exact form writes rows of its own length)
-    R *ad_rS = nullptr, *ad_rE = nullptr;
-    Cx<R> *ad_eS = nullptr, *ad_eE = nullptr, *ad_errh = nullptr;
-    float *ad_M = nullptr, *ad_chg = nullptr, *ad_rP = nullptr, *ad_dP = nullptr;
-    if (!adaptive && head > 0) {
-        void *ab = nullptr;
-        if ((rc = scratch(Slot::PIT_ACQ, (size_t)nmodes * head * sizeof(Cx<R>) + 64, &ab))) return rc;
-        ad_errh = (Cx<R> *)ab;
-    }
-    if (adaptive) {
-        void *ab = nullptr;
-        const size_t nS = ((size_t)sg.S + 15) / 16 * 16;
-        if ((rc = scratch(Slot::PIT_ACQ, nS * (2 * sizeof(R) + 2 * sizeof(Cx<R>) + 3 * sizeof(float)) + 64 + (size_t)nmodes * head * sizeof(Cx<R>), &ab))) return rc;
-        ad_eS = (Cx<R> *)ab; ad_eE = ad_eS + nS; ad_errh = ad_eE + nS;
-        ad_rS = (R *)(ad_errh + (size_t)nmodes * head); ad_rE = ad_rS + nS;
-        ad_M = (float *)(ad_rE + nS); ad_rP = ad_M + nS; ad_dP = ad_rP + nS; ad_chg = ad_dP + nS;
-    }
-    // (the selected modes go to the device as a kernel argument - pit_init_kernel - : no copy from the caller's memory to wait for)
-    init.modes_dev = modes_dev; init.nsel = nsel;
-    for (int j = 0; j < 16; j++) init.modes[j] = j < nsel ? modes[j] : 0;
-    // What the host needs to know before it can enqueue the rest: the step size (a sweep with mu = 0 takes the exact form) and, for a cold
+    if ((rc = pit_carve_work(b, sg.S, nsel, sw.wset))) return rc;
+    if ((adaptive || sw.head > 0) && (rc = pit_carve_acq(b, sg.S, nmodes, sw.head, adaptive))) return rc;
+    sw.rot_use = sw.seed_phase ? b.rot : nullptr;
+
+    // ---- What the host needs to know before it can enqueue the rest: the step size (a sweep with mu = 0 takes the exact form) and, for a cold
     // start, the gear-shifted step size pit_setup_kernel chose (it sizes the acquisition chunks).  A caller that hands over its host copy of
     // the step (mu_hint) and the chunk length (acq_chunk: from the report of an earlier capture) spares the call its one synchronisation -
     // ~90 us of idle GPU per stage at C3.
-    const bool prepared = o.prepared != nullptr && o.acquire && !adaptive && head == 0 && Niter >= 1;
-    const bool need_mu = adaptive || !(o.mu_hint > 0), need_acq = o.acquire && !(o.acq_chunk > 0) && !prepared;
-    R mu_acq_h = 0;                                               // the gear-shifted step size pit_setup_kernel chose (sizes the acquisition run)
-    if (need_acq) QH_HIP(hipMemcpyAsync(&mu_acq_h, mu_acq, sizeof(R), hipMemcpyDeviceToHost, g_stream));
-    R mu_host = need_mu ? (R)1 : (R)o.mu_hint;
+    const bool need_mu = adaptive || !(o.mu_hint > 0), need_acq = o.acquire && !(o.acq_chunk > 0) && !sw.prepared;
+    R mu_acq_h = 0, mu_host = need_mu ? (R)1 : (R)o.mu_hint;
+    if (need_acq) QH_HIP(hipMemcpyAsync(&mu_acq_h, b.mu_acq, sizeof(R), hipMemcpyDeviceToHost, g_stream));
     if (need_mu) QH_HIP(hipMemcpyAsync(&mu_host, mu_dev, sizeof(R), hipMemcpyDeviceToHost, g_stream));
     if (need_mu || need_acq) QH_HIP(hipStreamSynchronize(g_stream));
     if (!adaptive && !(mu_host != 0))                             // a sweep that moves nothing (or a NaN step): the exact form, as it is
-        return exact_form(ctrl, 0, 0, gram, 0);
+        return pit_exact_form(sw, ctrl, 0, 0, gram, 0);
     if (o.acquire && !(o.acq_chunk > 0)) pl.acquisition(o, TrSyms, pit_acq_chunk(mu_acq_h));
 
     // ---- Gram table: of the whole sweep when the passes run in a block form (acquisition chunks and segments index into
-    // it), of the acquisition range only when they run in the throughput form
-    const int64_t amax = pl.amax;
+    // it), of the acquisition range only when they run in the throughput form; the eigenbasis of the coarse correction, the coarse model's arguments
     void *G = const_cast<void *>(gram);
-    if (prepared) QH_REQUIRE(seg_form && o.acq_chunk > 0, "train_equaliser: a prepared acquisition belongs to throughput-form passes with acq_chunk given (qh_pit_prepare_*_dev said so)");
-    if (block_form && !G && (!seg_form || amax > 0) && !prepared) {
-        const int64_t n = seg_form ? pl.ngram : TrSyms;
-        rc = pair_tab ? gram_build<R>(E, nmodes, L, os, ntaps, n, &G) : gram_cur_build<R>(E, nmodes, L, os, ntaps, n, &G);
+    if (sw.prepared) QH_REQUIRE(sw.seg_form && o.acq_chunk > 0, "train_equaliser: a prepared acquisition belongs to throughput-form passes with acq_chunk given (qh_pit_prepare_*_dev said so)");
+    if (sw.block_form && !G && (!sw.seg_form || pl.amax > 0) && !sw.prepared) {
+        const int64_t n = sw.seg_form ? pl.ngram : TrSyms;
+        rc = sw.pair_tab ? gram_build<R>(E, nmodes, L, os, ntaps, n, &G) : gram_cur_build<R>(E, nmodes, L, os, ntaps, n, &G);
         if (rc) return rc;
     }
-    const int64_t g_per_step = pair_tab ? LA_B : GRAM_TRI / 2 / LA_B;      // GramPair elements per step
-
-    // ---- coarse correction: eigenbasis of the input covariance (the caller's, or built here), defect vectors in that basis
-    const int ncol = sg.S * nsel;
-    const double *lam = nullptr;
-    const Zf *Vb = nullptr;
-    Zf *Dz[2] = {nullptr, nullptr};
-    Zf *Xe = nullptr, *Ye = nullptr, *Yprev = nullptr;
-    if (want_corr) {
-        void *cb = nullptr;
-        if ((rc = scratch(Slot::PIT_BASIS, pit_basis_bytes(ntot) + 4 * (size_t)ntot * ncol * sizeof(Zf) + (size_t)ntot * nsel * sizeof(Zf) + 256, &cb))) return rc;
-        void *basis = o.basis ? o.basis : cb;
-        if (!o.basis && (rc = pit_basis<R>(E, nmodes, L, os, ntaps, TrSyms, basis))) return rc;
-        lam = (const double *)basis; Vb = (const Zf *)((const char *)basis + (size_t)ntot * sizeof(double));
-        Dz[0] = (Zf *)((char *)cb + (pit_basis_bytes(ntot) + 63) / 64 * 64); Dz[1] = Dz[0] + (size_t)ntot * ncol;
-        Xe = Dz[1] + (size_t)ntot * ncol; Ye = Xe + (size_t)ntot * ncol; Yprev = Ye + (size_t)ntot * ncol;
-    }
-    // complex64: the analysis of a pass runs in the eigenbasis (pit_basis_gemm_kernel / pit_bound_kernel / pit_recur_eig_kernel); complex128
-    // keeps the probe-based analysis, whose defect vectors are formed in double precision before they are projected
-    // (qh_set_form("pit_probe", "1") forces it for complex64 too: tests compare the two)
-    const bool eig = want_corr && sizeof(R) == 4 && form(FORM_PIT_PROBE) == 0;
-    // The tail of a pass - estimate, decision, and the back product for the next pass - in one launch (pit_tail_kernel) where the trainer can
-    // read its start taps from X and write its end taps to Y: the throughput form of a fixed-step sweep of a whole capture under the eigen-space
-    // analysis.  Every other case keeps the two launches (qh_set_form("pit_tail", "split") forces them: tests compare the two).
-    const bool tail_fused = eig && seg_form && !adaptive && !split && form(FORM_PIT_TAIL) == 0;
-    // Measured coarse model (pit_model_kernel): gain and the 2 x 2 block of the signal direction from the capture itself.  complex128, cma2 and
-    // decision methods whose passes run in neither the segment nor the block-iterative form keep round 3's model (one formula gain per error
-    // function, diagonal in the eigenbasis, extra damping beta).
-    const bool tables_ok = method == QH_M_CMA || method == QH_M_SGNCMA || method == QH_M_MCMA || method == QH_M_RDE || method == QH_M_MRDE ||
-                           (decision && (use_bi || seg_form));
-    const bool ssb = eig && tables_ok && method != QH_M_CMA2;
-    PitModel *model = nullptr;
-    float4 *ualpha = nullptr;
-    float2 *uqv = nullptr;
-    PitModelArgs<R> ma;
-    hipEvent_t model_event = nullptr;                             // recorded behind the model kernels of the current sweep
-    if (ssb) {
-        void *mb = nullptr;
-        const size_t pw_ = 2 * PIT_EIGMAX + 8;
-        const size_t b_part = (size_t)PIT_MODB * 4 * nsel * pw_ * sizeof(float), b_u = ((size_t)nsel * ntot * sizeof(Cx<R>) + 63) / 64 * 64;
-        const size_t b_ua = ((size_t)ncol * sizeof(float4) + 63) / 64 * 64, b_uq = ((size_t)ncol * sizeof(float2) + 63) / 64 * 64;
-        if ((rc = scratch(Slot::PIT_MODEL, b_part + b_u + b_ua + b_uq + 16 * sizeof(PitModel) + 128, &mb))) return rc;
-        ma.part = (float *)mb; ma.u = (Cx<R> *)((char *)mb + b_part);
-        ualpha = (float4 *)((char *)mb + b_part + b_u); uqv = (float2 *)((char *)ualpha + b_ua);
-        model = (PitModel *)((char *)uqv + b_uq); ma.model = model; ma.ticket = (unsigned *)(model + 16);
-        init.z[1] = ma.ticket; init.zn[1] = sizeof(unsigned);
-        init.z[2] = ualpha; init.zn[2] = (unsigned)(b_ua + b_uq);
-        ma.E = (const Cx<R> *)E; ma.wx = (const Cx<R> *)wx; ma.L = L; ma.TrSyms = TrSyms; ma.nmodes = nmodes; ma.ntaps = ntaps; ma.os = os; ma.nsel = nsel; ma.method = method;
-        if (decision) { ma.symbols = (const Cx<R> *)f.dd_table; ma.nsy = 2 * f.dd_npart + 1; ma.sy_pitch = 2 * BI_DD_MAXLEV; ma.tables = 1; }
-        else { ma.symbols = (const Cx<R> *)symbols; ma.nsy = nsy; ma.sy_pitch = nsy; ma.tables = (method == QH_M_RDE || method == QH_M_MRDE) ? 1 : 0; }
-        for (int j = 0; j < 16; j++) ma.modes[j] = j < nsel ? modes[j] : 0;
-        if (o.corr_beta < 0) beta = 0.0;
-    }
-    const size_t glds = ((size_t)PIT_EIGMAX * PIT_EIGMAX + (size_t)PIT_EIGMAX * PIT_GT) * sizeof(Zf);
+    sw.G = G;
+    if (sw.want_corr && (rc = pit_carve_basis(b, ntot, sw.ncol, nsel, o.basis))) return rc;
+    if (sw.want_corr && !o.basis && (rc = pit_basis<R>(E, nmodes, L, os, ntaps, TrSyms, b.lam))) return rc;
+    if (sw.ssb && (rc = pit_carve_model(b, ntot, sw.ncol, nsel))) return rc;
+    if (sw.ssb) pit_model_args(sw, f);
     static std::atomic<bool> gemm_attr{false};
-    if (want_corr && !gemm_attr.load(std::memory_order_acquire)) {
+    if (sw.want_corr && !gemm_attr.load(std::memory_order_acquire)) {
         QH_HIP(hipFuncSetAttribute((const void *)pit_cgemm_kernel<R, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
         QH_HIP(hipFuncSetAttribute((const void *)pit_cgemm_kernel<R, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
         QH_HIP(hipFuncSetAttribute((const void *)pit_basis_mfma_kernel<R, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
@@ -2626,359 +3100,55 @@ int train_pit_dev(const void *E, int nmodes, int64_t L, int64_t TrSyms, int Nite
         QH_HIP(hipFuncSetAttribute((const void *)pit_tail_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
         gemm_attr.store(true, std::memory_order_release);
     }
+    sw.la = la_args<R>(E, L, nmodes, ntaps, os, modes, nsel, method, symbols, nsy, mu_dev, err, TrSyms * Niter);
+    sw.la.G = (const GramPair<R> *)G; sw.la.gpair = sw.pair_tab ? 1 : 0; sw.la.wx_cs = (int64_t)sw.wset;
+    sw.la.dd_general = f.dd_general;
+    f.alphabet(sw.la);
+    sw.ta = train_args<R>(E, L, nmodes, ntaps, os, TrSyms, Niter, modes, nsel, method, symbols, nsy, mu_dev, err);
 
-    LaArgs<R> la = la_args<R>(E, L, nmodes, ntaps, os, modes, nsel, method, symbols, nsy, mu_dev, err, TrSyms * Niter);
-    la.G = (const GramPair<R> *)G; la.gpair = pair_tab ? 1 : 0; la.wx_cs = (int64_t)wset;
-    la.dd_general = f.dd_general;
-    f.alphabet(la);
-    const TrainArgs<R> ta = train_args<R>(E, L, nmodes, ntaps, os, TrSyms, Niter, modes, nsel, method, symbols, nsy, mu_dev, err);
-
+    // ---- the small initialisations in one launch: tickets, the coarse model's sums, the taps the ways out go back to, the selected modes
+    // (as a kernel argument: no copy from the caller's memory to wait for)
     PitTiming &tm = pit_timing();
     tm.npass = 0; tm.acq_ms = 0;
-    bool acq_timed = false;                                       // the acquisition's event pair (read when the passes are through)
     PitEvents &ev = pit_events();
     QH_REQUIRE(ev.ok, "train_equaliser: no pinned memory for the pass flags");
-    // Way out (every tier-b call returns the reference's result): a sweep the passes do not certify - estimate stuck above tol, pass
-    // budget used up, no coarse model to certify with - is redone in the EXACT form from the taps the call started with, inside the
-    // call (report: converged = 2, `exact_form`).  opts.exact_redo_off != 0 leaves the uncertified result in place (converged = 0): for
-    // the tests of the iteration itself.
-    const bool redo_ok = o.exact_redo_off == 0;
-    bool fell_back = false;
-    if (redo_ok && !adaptive) { init.cd[0] = w_call; init.cs[0] = wx; init.cn[0] = (unsigned)wbytes; }
-    if (o.acquire && Niter > 0) { init.cd[1] = w_start; init.cs[1] = wx; init.cn[1] = (unsigned)wbytes; }     // (the taps the acquisition starts from)
+    PitInit init{};
+    init.z[0] = b.ticket; init.zn[0] = sizeof(unsigned);
+    if (sw.ssb) { init.z[1] = b.model_ticket; init.zn[1] = sizeof(unsigned); init.z[2] = b.ualpha; init.zn[2] = b.u_bytes; }
+    pit_init_modes(init, b.modes_dev, modes, nsel);
+    if (sw.redo_ok && !adaptive) { init.cd[0] = b.w_call; init.cs[0] = wx; init.cn[0] = (unsigned)sw.wbytes; }
+    if (o.acquire && Niter > 0) { init.cd[1] = b.w_start; init.cs[1] = wx; init.cn[1] = (unsigned)sw.wbytes; }     // (the taps the acquisition starts from)
     hipLaunchKernelGGL(pit_init_kernel, dim3(32), dim3(256), 0, g_stream, init);
     QH_HIP(hipGetLastError());
+
+    bool acq_timed = false, fell_back = false;
     for (int it = 0; it < Niter; it++) {
-        // ================================================================ acquisition (first sweep of a cold start)
-        if (it == 0 && prepared) {
-            // the acquisition ran ahead of the call (qh_pit_prepare_*_dev, on another stream beside the previous capture's training): adopt it
-            const PitPrepLayout lay = pit_prep_layout<R>(nmodes, ntaps, amax);
-            const char *pb = (const char *)o.prepared;
-            hipLaunchKernelGGL((pit_adopt_kernel<R>), dim3((unsigned)((wset + 255) / 256)), dim3(256), 0, g_stream, (Cx<R> *)wx, (const Cx<R> *)(pb + lay.wx), (int)wset,
-                               (const PitCtrl *)(pb + lay.ctrl), ctrl, mu_acq, (const R *)(pb + lay.mu_acq));
-            QH_HIP(hipGetLastError());
-        } else if (it == 0 && o.acquire) {
-            // All chunks are enqueued at once and the host does not wait for any of them: once the plateau is reached (or the run diverged) the
-            // monitor sets acq_done on the device and the chunks behind it return at once, and everything downstream reads the device's flags.
-            // (Rounds 2-3 waited for every chunk's flag: ~30 us of idle GPU after the last one.)  One event pair around the run times it.
-            if (pl.nchunks > 0) { QH_HIP(hipEventRecord(ev.t0[PIT_NEV - 1], g_stream)); acq_timed = true; }
-            if ((rc = pit_acq_enqueue<R>(pl, block_form ? &la : nullptr, use_bi, &ta, (Cx<R> *)wx, (Cx<R> *)err, TrSyms * Niter, ctrl, mu_acq, mu_dev,
-                                         modes_dev, nsel))) return rc;
-            if (pl.nchunks > 0) QH_HIP(hipEventRecord(ev.t1[PIT_NEV - 1], g_stream));
-            hipLaunchKernelGGL((pit_acq_finish_kernel<R>), dim3((unsigned)((wset + 255) / 256)), dim3(256), 0, g_stream, (Cx<R> *)wx, (const Cx<R> *)w_start, (int)wset, ctrl);
-            QH_HIP(hipGetLastError());
-        }
-        // ================================================================ adaptive step: the head of the sweep in the exact form
-        if (adaptive) {
-            QH_HIP(hipMemcpyAsync(w_start, wx, wbytes, hipMemcpyDeviceToDevice, g_stream));           // (kept for the way out below)
-            QH_HIP(hipMemcpyAsync(ad_chg + 1, mu_dev, sizeof(R), hipMemcpyDeviceToDevice, g_stream));
-            if ((rc = train_dev<R>(E, nmodes, L, head, 1, os, mu_dev, wx, ntaps, modes, 1, 1, symbols, nsy, method, ad_errh, 0, nullptr))) return rc;
-            QH_HIP(hipMemcpyAsync((Cx<R> *)err + (size_t)modes[0] * TrSyms, ad_errh + (size_t)modes[0] * head, (size_t)head * sizeof(Cx<R>), hipMemcpyDeviceToDevice, g_stream));
-            hipLaunchKernelGGL((pit_adapt_init_kernel<R>), dim3((sg.S + 255) / 256), dim3(256), 0, g_stream, (const R *)mu_dev, (const Cx<R> *)(ad_errh + (size_t)modes[0] * head + head - 1),
-                               sg.S, ad_rS, ad_eS);
-            QH_HIP(hipGetLastError());
-        }
-        // ================================================================ fixed step: the head of the sweep in the exact form
-        if (!adaptive && head > 0) {
-            if ((rc = train_dev<R>(E, nmodes, L, head, 1, os, mu_dev, wx, ntaps, modes, nsel, 0, symbols, nsy, method, ad_errh, 0, nullptr))) return rc;
-            for (int j = 0; j < nsel; j++)
-                QH_HIP(hipMemcpyAsync((Cx<R> *)err + (size_t)modes[j] * TrSyms * Niter + (size_t)it * TrSyms, ad_errh + (size_t)modes[j] * head, (size_t)head * sizeof(Cx<R>),
-                                      hipMemcpyDeviceToDevice, g_stream));
-        }
-        // ================================================================ pass-0 start taps
-        // (the per-sweep fields of the control block are reset by pit_seed_kernel below)
-        const double *rot_use = nullptr;
-        if (seed_phase) {
-            int nwin = PIT_SEEDWIN;                                   // head staged in LDS: shortened until it fits the default 64 KiB
-            auto phase_lds = [&](int nw) { return ((size_t)ntot + (size_t)nmodes * os * pit_phase_pitch(ntaps, os, nw)) * sizeof(Cx<R>); };
-            while (nwin > 32 && phase_lds(nwin) > 60 * 1024) nwin /= 2;
-            QH_REQUIRE(phase_lds(nwin) <= 60 * 1024, "train_equaliser: phase seeding does not fit the LDS for this filter shape (pass phase_seed = 0)");
-            hipLaunchKernelGGL((pit_phase_kernel<R>), dim3(sg.S, nsel), dim3(256), phase_lds(nwin), g_stream, (const Cx<R> *)E, nmodes, L, os,
-                               (const Cx<R> *)wx, ntaps, sg, (const int64_t *)modes_dev, nwin, z);
-            hipLaunchKernelGGL(pit_unwrap_kernel, dim3(nsel), dim3(256), 0, g_stream, (const double *)z, sg.S, nsel, rot, uw_phi, uw_jump);
-            rot_use = rot;
-        }
-        // segment 0 starts from the taps the sweep starts from in the reference (before the acquisition moved them), unrotated
-        const Cx<R> *w_exact = o.start == 1 ? nullptr : ((it == 0 && o.acquire) ? (const Cx<R> *)w_start : (const Cx<R> *)wx);
-        hipLaunchKernelGGL((pit_seed_kernel<R>), dim3(sg.S), dim3(256), 0, g_stream, (const Cx<R> *)wx, nmodes, ntot, (const int64_t *)modes_dev, nsel, rot_use, X, w_exact, Y, ctrl);
-        if (ssb) {
-            // the coarse model of this sweep, measured at its seed taps: two small launches on the library's helper stream, beside pass 0 (which
-            // does not need it; its analysis waits for it) and beside the basis build of a cold sweep on the other stream.
-            ma.sg = sg; ma.rot = rot_use;
-            static thread_local hipEvent_t ev_seed = nullptr, ev_model = nullptr;
-            if (!ev_seed) { QH_HIP(hipEventCreateWithFlags(&ev_seed, hipEventDisableTiming)); QH_HIP(hipEventCreateWithFlags(&ev_model, hipEventDisableTiming)); }
-            hipStream_t ss = helper_stream();
-            QH_HIP(hipEventRecord(ev_seed, g_stream));
-            QH_HIP(hipStreamWaitEvent(ss, ev_seed, 0));
-            hipLaunchKernelGGL((pit_model_kernel<R, 0>), dim3(PIT_MODB), dim3(256), 0, ss, ma);
-            hipLaunchKernelGGL((pit_model_kernel<R, 1>), dim3(PIT_MODB), dim3(256), 0, ss, ma);
-            QH_HIP(hipEventRecord(ev_model, ss));
-            model_event = ev_model;
-        }
-        QH_HIP(hipGetLastError());
-        // ================================================================ relaxation passes
-        // HIP events around the trainer launch of a pass (qh_pit_last_timing): an event is ~5.6 us of idle stream, so by default only
-        // pass 1 of a sweep is timed (pass 0 of a cold sweep shares the chip with the basis build); QAMPY_HIP_PIT_TIMING = all | none
-        const int timing_mode = pit_timing_mode();                // (qh_set_pit_timing; the environment variable QAMPY_HIP_PIT_TIMING = all | none is its initial value)
-        auto decide_args = [&](int p, const float *dm, const float2 *ye, float2 *yprev, int ne, int ncol_e, int corr_wanted) {
-            PitDecideArgs<R> d;
-            d.dfc = dfc; d.pw = pw; d.nb = (int)((sg.S - 1) * nsel); d.Ylast = (const Cx<R> *)(Y + (size_t)(sg.S - 1) * wset); d.n = (int)wset; d.wx = (Cx<R> *)wx; d.c = ctrl;
-            d.host_view = &ev.hview[2 * p]; d.nrow = nsel; d.devmax = dm; d.ndev = ndev; d.safety = safety; d.Ye = ye; d.Yprev = yprev; d.ne = ne; d.ncol_e = ncol_e;
-            d.theta = theta; d.modes_dev = (const int64_t *)modes_dev; d.ntot_w = ntot; d.S = (int)sg.S; d.sym = sym; d.corr_wanted = corr_wanted;
-            d.extra = adaptive ? (const float *)ad_chg : nullptr;
-            d.Dfin = (ye && !adaptive) ? (const float2 *)Dz[1] : nullptr; d.Vfin = (const float2 *)Vb; d.lam_fin = lam;
-            // (plain relaxation asked for - opts.correction = 0: its fixed point is reached after S passes whatever the boundary defects do on the way - from
-            // converged taps they stay at the noise level until the last pass - so "nothing gained over two passes" must not end such a sweep early)
-            d.stall_from = o.correction == 0 ? QH_PIT_MAXPASS : (adaptive ? 5 : 2);
-            return d;
-        };
-        auto timed = [&](int p) { return timing_mode == 2 || (timing_mode == 1 && p == 1); };
-        int back_done_for = 0;                                    // the pass whose start taps the last tail launch wrote into X (0: none)
-        auto enqueue_pass = [&](int p) -> int {
-            ((volatile float *)ev.hview)[2 * p] = -1.f;             // "not decided yet": pit_decide_kernel overwrites it (polled below)
-            PitFuse<R> fz;
-            fz.X = X; fz.Y = Y; fz.theta = theta; fz.modes_dev = (const int64_t *)modes_dev; fz.nmodes = nmodes; fz.nsel = nsel;
-            fz.damp = (adaptive && p > 1) ? ad_damp : 1.f;      // (the first correction - from the seeds to the trajectory - in full)
-            fz.x_only = tail_fused ? 1 : 0;
-            if (p > 0 && tail_fused && back_done_for == p) {
-                // the tail of pass p - 1 has written this pass's start taps into X already
-            } else if (p > 0 && want_corr) {
-                // start taps = theta X + V D~ with D[s+1] = d[s+1] + J D[s] from the analysis that closed pass p - 1 (below); with the
-                // correction switched off on the device (corr_on = 0) the scan ran with coefficient 0, D = d: plain relaxation
-                if (eig)
-                    hipLaunchKernelGGL((pit_basis_mfma_kernel<R, 1>), dim3((ncol + PIT_MC - 1) / PIT_MC), dim3(pit_mfma_threads(ntot)), pit_mfma_lds(ntot), g_stream, Vb + (size_t)ntot * ntot,
-                                       (const Cx<R> *)nullptr, (const Zf *)Dz[1], (Zf *)nullptr, ntot, ncol, (const PitCtrl *)ctrl, fz);
-                else
-                    hipLaunchKernelGGL((pit_cgemm_kernel<R, false>), dim3((ncol + PIT_GT - 1) / PIT_GT), dim3(256), glds, g_stream, Vb + (size_t)ntot * ntot, (const Zf *)Dz[1], (Zf *)nullptr, ntot, ncol, (const PitCtrl *)ctrl, fz);
-                QH_HIP(hipGetLastError());
-            } else if (p > 0) {
-                QH_HIP(hipMemcpyAsync(X + wset, Y, (size_t)(sg.S - 1) * wbytes, hipMemcpyDeviceToDevice, g_stream));   // X[s] = end taps of s-1
-                QH_HIP(hipMemcpyAsync(Y, X, (size_t)sg.S * wbytes, hipMemcpyDeviceToDevice, g_stream));
-            }                                                       // (pass 0: pit_seed_kernel wrote the start taps into X and Y)
-            if (o.on_pass) {
-                // the caller's chip-wide work for other streams, to run BESIDE this pass's trainer: an event recorded here is behind everything of the
-                // pass before (its back product), so what is gated on it starts with the trainer - not in the analysis behind it, where it would share
-                // the chip with the control path, which is the critical path (hook behind the trainer launch: gaps of 88-90 instead of 70-75 us between
-                // the passes, C3 1137-1146 against 1163-1167 MSym/s)
-                hipStream_t keep = g_stream;
-                o.on_pass(o.on_pass_user, it, p);
-                g_stream = keep;
-            }
-            if (timed(p)) QH_HIP(hipEventRecord(ev.t0[p], g_stream));
-            if (seg_form) {
-                SegArgs<R> sa{};
-                sa.E = (const Cx<R> *)E; sa.wx = tail_fused ? X : Y; sa.wx_out = tail_fused ? Y : nullptr; sa.symbols = la.symbols; sa.err = (Cx<R> *)err; sa.mu = mu_dev;
-                sa.L = L; sa.TrSyms = TrSyms; sa.nsy = la.nsy; sa.sy_pitch = la.sy_pitch; sa.err_pitch = TrSyms * Niter; sa.err_off = (int64_t)it * TrSyms;
-                sa.nmodes = nmodes; sa.ntaps = ntaps; sa.os = os; sa.nsel = nsel; sa.S = sg.S;
-                sa.seg_len = sg.len; sa.seg_extra = sg.extra; sa.seg_tail = sg.tail; sa.seg_begin = sg.begin;
-                sa.r_in = ad_rS; sa.r_out = ad_rE; sa.e_in = ad_eS; sa.e_out = ad_eE; sa.mu_sum = (R *)ad_M; sa.adapt_first = sg.begin > 0 ? 1 : 0;
-                for (int j = 0; j < 16; j++) sa.modes[j] = j < nsel ? modes[j] : 0;
-                sa.skip = &ctrl->done;
-                sa.q_first = own_first * nsel; sa.q_count = split ? own_count * nsel : 0;
-                pit_last_launch().form = 1;                             // (launch_seg adds the layout; a process of a split capture that owns no segment launches none)
-                if (!split || own_count > 0) { int r = launch_seg<R>(sa, method, adaptive); if (r) return r; }
-                if (adaptive) hipLaunchKernelGGL((pit_adapt_scan_kernel<R>), dim3(1), dim3(1024), 0, g_stream, ad_rS, (const R *)ad_rE, ad_eS, (const Cx<R> *)ad_eE, sg.S, ad_chg, (const PitCtrl *)ctrl, ad_relax, ad_rP, ad_dP, ad_newton);
-            } else if (block_form) {
-                LaArgs<R> ls = la;
-                ls.TrSyms = sg.len; ls.nch = sg.S; ls.wx = Y; ls.err_off = (int64_t)it * TrSyms; ls.seg = 1; ls.seg_extra = sg.extra; ls.seg_tail = sg.tail;
-                ls.skip = &ctrl->done;
-                pit_last_launch() = PitLaunch{use_bi ? 2 : 3, 0, 0, 0, 0, 0};
-                if (sg.begin > 0) {                                  // an exact head: the segments cover the steps from sg.begin on
-                    ls.E = (const Cx<R> *)E + sg.begin * os; ls.L = L - sg.begin * os; ls.err_off += sg.begin;
-                    ls.G = (const GramPair<R> *)G + sg.begin * g_per_step;
-                }
-                { int r = use_bi ? launch_bi<R>(ls) : launch_la<R>(ls); if (r) return r; }
-            } else {
-                TrainArgs<R> ts = ta;
-                ts.wx = Y; ts.nseg = sg.S; ts.seg_begin = sg.begin; ts.seg_len = sg.len; ts.seg_extra = sg.extra; ts.seg_tail = sg.tail; ts.seg_iter = it; ts.skip = &ctrl->done;
-                pit_last_launch() = PitLaunch{4, 0, 0, 0, 0, 0};
-                { int r = launch_any<R>(ts); if (r) return r; }
-            }
-            if (timed(p)) QH_HIP(hipEventRecord(ev.t1[p], g_stream));
-            if (split) {
-                // one capture over several processes: the end taps of the segments trained elsewhere arrive through the caller's
-                // all-reduce (zeros here, the trained taps there); from then on every process works on identical data
-                if (own_first > 0) QH_HIP(hipMemsetAsync(Y, 0, (size_t)own_first * wbytes, g_stream));
-                if (own_first + own_count < sg.S)
-                    QH_HIP(hipMemsetAsync(Y + (size_t)(own_first + own_count) * wset, 0, (size_t)(sg.S - own_first - own_count) * wbytes, g_stream));
-                if (!xchg_async) QH_HIP(hipStreamSynchronize(g_stream));
-                if (o.exchange(o.exchange_user, Y, (size_t)sg.S * wbytes) != 0) { set_error("train_equaliser: the exchange callback failed"); return QH_ERR_ARG; }
-            }
-            // ---- analysis of the pass: boundary defects -> gauge -> defect vectors in the eigenbasis -> scan (the next correction,
-            // and - weighted with the eigenvalues - the estimate of how far this pass is from the sequential recurrence) -> decision
-            const int nbnd = (int)((sg.S - 1) * nsel);
-            if (eig) {
-                if (o.basis && pit_basis_sync().pending) {           // a basis still being built on the other stream
-                    QH_HIP(hipStreamWaitEvent(g_stream, pit_basis_sync().out, 0));
-                    pit_basis_sync().pending = false;
-                }
-                auto forward2 = [&](const Cx<R> *src, Zf *dst, const Cx<R> *src2, Zf *dst2) {      // both products in ONE launch (a launch is ~4.5 us whatever it does)
-                    PitFuse<R> f2 = fz;
-                    f2.T2 = src2; f2.Out2 = reinterpret_cast<float2 *>(dst2);
-                    hipLaunchKernelGGL((pit_basis_mfma_kernel<R, 0>), dim3(2 * ((ncol + PIT_MC - 1) / PIT_MC)), dim3(pit_mfma_threads(ntot)), pit_mfma_lds(ntot), g_stream, Vb, src, (const Zf *)nullptr, dst, ntot, ncol, (const PitCtrl *)ctrl, f2);
-                };
-                if (p == 0 && model_event) QH_HIP(hipStreamWaitEvent(g_stream, model_event, 0));       // the sweep's coarse model (other stream)
-                // Start taps of this pass into the eigenbasis - in EVERY pass (round 5).  Rounds 3-4 projected them once per sweep and kept x~ up to
-                // date in the eigenbasis (x~ <- theta x~ + D~, pit_recur_eig_kernel) while the back product updated X itself (X <- theta X + V D~).
-                // The two copies part by the rounding of the products and by what V lacks to be unitary (7e-6 per entry, single-precision Jacobi)
-                // times the correction - ~1e-6 per boundary, the same sign from boundary to boundary - and a fixed point of the TRACKED copy
-                // leaves exactly that as a true defect at every boundary; the weakly excited directions (coefficient ~1) add them up over the
-                // whole sweep: 1.0-1.7e-3 of tap deviation at C3 whatever the tolerance, invisible to the estimate (profiles/r05_tap_floor.txt).
-                forward2((const Cx<R> *)X, Xe, (const Cx<R> *)Y, Ye);
-                hipLaunchKernelGGL(pit_bound_kernel, dim3((nbnd + nsel + 3) / 4), dim3(256), 0, g_stream, (const Zf *)Xe, (const Zf *)Ye, (const Zf *)Yprev, lam, ntot, sg.S, nsel, sym,
-                                   (const PitCtrl *)ctrl, dfc, pw, gph, ualpha);
-                hipLaunchKernelGGL((pit_gauge_kernel<R>), dim3(ssb ? 2 : 1), dim3(PIT_GT_THREADS), 0, g_stream, (const double *)gph, sg.S, nsel, ctrl, theta, (const double *)pw,
-                                   nbnd, method, (const Cx<R> *)symbols + (size_t)modes[0] * nsy, 1, (const PitModel *)model, (const float4 *)ualpha, uqv,
-                                   (const R *)mu_dev, sg.len, (const float *)ad_M);
-                hipLaunchKernelGGL((pit_recur_eig_kernel<R>), dim3(ntot, nsel), dim3(PIT_RT), 0, g_stream, Xe, (const Zf *)Ye, Dz[1], (const double *)theta, lam, nsel, sg.S, sg.len,
-                                   (const R *)mu_dev, beta, (const PitCtrl *)ctrl, (const float *)ad_M, (adaptive && p >= 1) ? ad_damp : 1.f,
-                                   (const float4 *)ualpha, (const float2 *)uqv);
-                if (tail_fused) {
-                    // (whether or not pass p + 1 will be enqueued: the product blocks of a tail behind the last pass write start taps nobody reads)
-                    const int nt_prod = pit_mfma_threads(ntot);
-                    PitFuse<R> fn = fz;
-                    fn.damp = 1.f;                                   // (the next pass's: not adaptive)
-                    hipLaunchKernelGGL((pit_tail_kernel<R>), dim3(ndev + (ncol + PIT_MC - 1) / PIT_MC), dim3(nt_prod > 256 ? nt_prod : 256), pit_mfma_lds(ntot), g_stream,
-                                       (const Zf *)Dz[1], lam, ntot, ncol, (const PitCtrl *)ctrl, devmax, ticket, ndev,
-                                       decide_args(p, (const float *)devmax, (const float2 *)Ye, (float2 *)Yprev, ntot, ncol, 1), Vb + (size_t)ntot * ntot, fn, nt_prod);
-                    back_done_for = p + 1;
-                } else
-                hipLaunchKernelGGL((pit_devest_kernel<R>), dim3(ndev), dim3(256), 0, g_stream, (const Zf *)Dz[1], lam, ntot, ncol, (const PitCtrl *)ctrl, devmax, ticket,
-                                   decide_args(p, (const float *)devmax, (const float2 *)Ye, (float2 *)Yprev, ntot, ncol, 1));
-            } else {
-            const size_t dlds = (2 * (size_t)ntot + (size_t)nmodes * os * pit_phase_pitch(ntaps, os, PIT_PROBE)) * sizeof(Cx<R>);
-            QH_REQUIRE(dlds <= 60 * 1024, "train_equaliser: boundary probe does not fit the LDS for this filter shape");
-            hipLaunchKernelGGL((pit_defect_kernel<R>), dim3(sg.S, nsel), dim3(PIT_PROBE), dlds, g_stream, (const Cx<R> *)E, nmodes, L, os,
-                               ntaps, sg, TrSyms, (const int64_t *)modes_dev, (const Cx<R> *)X, (const Cx<R> *)Y, sym, (const PitCtrl *)ctrl, dfc, pw, gph, (const Cx<R> *)wx);
-            hipLaunchKernelGGL((pit_gauge_kernel<R>), dim3(1), dim3(PIT_GT_THREADS), 0, g_stream, (const double *)gph, sg.S, nsel, ctrl, theta, (const double *)pw,
-                               nbnd, method, (const Cx<R> *)symbols + (size_t)modes[0] * nsy, want_corr ? 1 : 0);
-            if (want_corr) {
-                if (o.basis && pit_basis_sync().pending) {           // a basis still being built on the other stream
-                    QH_HIP(hipStreamWaitEvent(g_stream, pit_basis_sync().out, 0));
-                    pit_basis_sync().pending = false;
-                }
-                hipLaunchKernelGGL((pit_cgemm_kernel<R, true>), dim3((ncol + PIT_GT - 1) / PIT_GT), dim3(256), glds, g_stream, Vb, (const Zf *)nullptr, Dz[1], ntot, ncol, (const PitCtrl *)ctrl, fz);
-                hipLaunchKernelGGL((pit_recur_kernel<R>), dim3(ntot, nsel), dim3(256), 0, g_stream, Dz[1], lam, nsel, sg.S, sg.len, (const R *)mu_dev, beta, (const PitCtrl *)ctrl);
-                hipLaunchKernelGGL((pit_devest_kernel<R>), dim3(ndev), dim3(256), 0, g_stream, (const Zf *)Dz[1], lam, ntot, ncol, (const PitCtrl *)ctrl, devmax, ticket,
-                                   decide_args(p, (const float *)devmax, (const float2 *)nullptr, (float2 *)nullptr, 0, 0, 1));
-            } else
-                hipLaunchKernelGGL((pit_decide_kernel<R>), dim3(1), dim3(256), 0, g_stream, decide_args(p, (const float *)nullptr, (const float2 *)nullptr, (float2 *)nullptr, 0, 0, 0));
-            }
-            QH_HIP(hipGetLastError());
-            return QH_OK;
-        };
-        // Pass p + 1 is enqueued BEFORE the host has seen the flag of pass p - unless pass p is expected to be the last one, since
-        // a pass enqueued in vain costs a dozen empty launches (~55 us), about as much as the idle round trip it would save:
-        // expected defect of pass p = PIT_CONTRACT x the defect of pass p - 1 (the first pass never converges from seeds).
-        if ((rc = enqueue_pass(0))) return rc;
-        if (it == 0 && o.on_pass0) {                              // the caller's work for the other streams: enqueued while pass 0 keeps the device busy
-            hipStream_t keep = g_stream;
-            o.on_pass0(o.on_pass0_user);
-            g_stream = keep;
-        }
-        bool ahead = false;                                       // pass p + 1 already in the stream
-        bool certified = false;                                   // the sweep's last decision: stopped AND below the tolerance
-        for (int p = 0; p < npass; p++) {
-            // (expected criterion of pass p: the last one times the contraction the last two passes showed; the first guess is PIT_CONTRACT)
-            double contr = PIT_CONTRACT;
-            if (p >= 2 && ev.hview[2 * (p - 2) + 1] > 0) {
-                contr = (double)ev.hview[2 * (p - 1) + 1] / (double)ev.hview[2 * (p - 2) + 1];
-                contr = contr < 0.1 ? 0.1 : (contr > 0.9 ? 0.9 : contr);
-            }
-            const bool expect_last = p > 0 && contr * (double)ev.hview[2 * (p - 1) + 1] < tol;
-            ahead = false;
-            if (p + 1 < npass && !expect_last && (!split || xchg_async)) { if ((rc = enqueue_pass(p + 1))) return rc; ahead = true; }   // (a host-side exchange cannot be enqueued ahead)
-            // the decision of pass p: polled in pinned memory (an event here would idle the stream for ~5.6 us per pass); the stream
-            // going idle without a decision means a launch failed or the sweep was already done
-            {
-                volatile float *hv = (volatile float *)ev.hview;
-                unsigned spins = 0;
-                auto t_last = std::chrono::steady_clock::now();
-                while (hv[2 * p] < 0.f) {
-                    if ((++spins & 255u) != 0) continue;
-                    const auto now = std::chrono::steady_clock::now();
-                    if (now - t_last < std::chrono::milliseconds(20)) continue;     // (a stream query puts a marker into the queue: rarely)
-                    t_last = now;
-                    const hipError_t q = hipStreamQuery(g_stream);
-                    if (q == hipSuccess) { if (hv[2 * p] < 0.f) hv[2 * p] = 2.f; break; }       // (nothing decided: treated as not certified)
-                    if (q != hipErrorNotReady) QH_HIP(q);
-                }
-                std::atomic_thread_fence(std::memory_order_acquire);
-            }
-            if (timed(p) && tm.npass < QH_PIT_MAXPASS) {
-                float ms = 0;
-                QH_HIP(hipEventSynchronize(ev.t1[p]));
-                QH_HIP(hipEventElapsedTime(&ms, ev.t0[p], ev.t1[p]));
-                tm.pass_ms[tm.npass++] = ms;
-            }
-            if (ev.hview[2 * p] != 0.f) { certified = ev.hview[2 * p] == 1.f; break; }
-            if (p + 1 < npass && !ahead && (rc = enqueue_pass(p + 1))) return rc;
-        }
+        if (it == 0 && (rc = pit_acquire_or_adopt(sw, ev, acq_timed))) return rc;
+        if ((rc = pit_sweep_head(sw, it))) return rc;
+        if ((rc = pit_seed_sweep(sw, it))) return rc;
+        bool certified = false;
+        if ((rc = pit_run_passes(sw, ev, it, certified))) return rc;
         if (acq_timed) {                                          // (complete long before the passes were)
             float ms = 0;
             QH_HIP(hipEventSynchronize(ev.t1[PIT_NEV - 1]));
             QH_HIP(hipEventElapsedTime(&ms, ev.t0[PIT_NEV - 1], ev.t1[PIT_NEV - 1]));
             tm.acq_ms = ms; acq_timed = false;
         }
-        if (!adaptive && !certified && redo_ok && !split && depth < 3 && o.head_auto_off == 0) {
-            // Stalled on the START of the sweep?  A stage that begins far from its own fixed point - a decision-directed stage whose start
-            // taps were locked to the carrier phase at the END of the capture - goes through a non-linear pull-in that the passes can only
-            // follow at the speed of plain relaxation (measured, 64-QAM mcma -> sbd: the bulk of the sweep converged after two passes, a
-            // front of ~0.1 deviation moved 1.5 segments per pass).  If the estimate of the last pass sits in the first quarter of the
-            // segments only, the call is repeated with that stretch (+ a margin) as an EXACT head: sequential there, parallel after it.
-            double hp = 0;
-            int hfront[2] = {-1, 0};
-            bool finite = false;
-            if (eig) {
-                int *fr = (int *)(ticket + 4);                               // (two ints behind the ticket: scratch slot 2 has the room)
-                QH_HIP(hipMemcpyAsync(&hp, &ctrl->out_power, sizeof(double), hipMemcpyDeviceToHost, g_stream));
-                QH_HIP(hipStreamSynchronize(g_stream));
-                QH_HIP(hipMemcpyAsync(fr, hfront, sizeof(hfront), hipMemcpyHostToDevice, g_stream));
-                hipLaunchKernelGGL(pit_front_kernel, dim3((ncol + 255) / 256), dim3(256), 0, g_stream, (const Zf *)Dz[1], lam, ntot, ncol, tol * tol * (hp > 0 ? hp : 1.0), fr, fr + 1);
-                QH_HIP(hipMemcpyAsync(hfront, fr, sizeof(hfront), hipMemcpyDeviceToHost, g_stream));
-                QH_HIP(hipStreamSynchronize(g_stream));
-                finite = hp > 0 && hfront[1] == 0;
-            }
-            const int front = hfront[0];
-            const int64_t front_seg = front < 0 ? -1 : front / nsel + 1;      // one past the last segment above the tolerance
-            if (eig && finite && front >= 0 && front_seg <= sg.S / 4) {
-                int64_t hs = front_seg + 8 + (front_seg + 1) / 2;                 // margin: the front keeps moving while the head is redone
-                if (hs > sg.S - 4) hs = sg.S - 4;
-                const int64_t new_head = sg.start(hs);
-                if (new_head > head && new_head < TrSyms && new_head <= 0x7fffffff) {
-                    QH_HIP(hipMemcpyAsync(wx, w_call, wbytes, hipMemcpyDeviceToDevice, g_stream));
-                    qh_pit_opts o2 = opts ? *opts : pit_opts_default();
-                    o2.head_steps = (int32_t)new_head; o2.acquire = 0; o2.segments = 0;
-                    return train_pit_dev<R>(E, nmodes, L, TrSyms, Niter, os, mu_dev, wx, ntaps, modes, nsel, symbols, nsy, method, err, 0, gram, &o2, report_dev, depth + 1);
-                }
-            }
+        if (!adaptive && !certified && sw.redo_ok && !sw.split && depth < 3 && o.head_auto_off == 0) {
+            bool retried = false;
+            rc = pit_retry_with_head(sw, retried);
+            if (rc || retried) return rc;
         }
-        if (!adaptive && !certified && redo_ok) {
+        if (!adaptive && !certified && sw.redo_ok) {
             // not certified: the whole call again in the exact form, from the taps it started with (all sweeps: a later sweep starts from
             // the result of this one).  Identical on every process of a split capture (they all took the same decision).
-            QH_HIP(hipMemcpyAsync(wx, w_call, wbytes, hipMemcpyDeviceToDevice, g_stream));
-            if ((rc = exact_form(ctrl, 0, 0, gram, -1))) return rc;
-            fell_back = true;
-            break;
+            QH_HIP(hipMemcpyAsync(wx, b.w_call, sw.wbytes, hipMemcpyDeviceToDevice, g_stream));
+            return pit_exact_form(sw, ctrl, 0, 0, gram, -1);
         }
-        if (adaptive) {
-            hipLaunchKernelGGL((pit_adapt_finish_kernel<R>), dim3(1), dim3(1), 0, g_stream, mu_dev, (const R *)ad_rE, sg.S);
-            // A sweep the passes cannot agree on - the later modes of a BLIND stage, which start from centre-spike taps with the tiny step
-            // the first mode left behind: no linear model describes that - ends not converged after a few passes; the call then does what
-            // the reference does: the exact form from the saved taps and step size (report: converged = 2).
-            int32_t conv = 0;
-            QH_HIP(hipMemcpyAsync(&conv, &ctrl->converged, sizeof(conv), hipMemcpyDeviceToHost, g_stream));
-            QH_HIP(hipStreamSynchronize(g_stream));
-            if (!conv && redo_ok) {
-                fell_back = true;
-                QH_HIP(hipMemcpyAsync(wx, w_start, wbytes, hipMemcpyDeviceToDevice, g_stream));
-                QH_HIP(hipMemcpyAsync(mu_dev, ad_chg + 1, sizeof(R), hipMemcpyDeviceToDevice, g_stream));
-                if ((rc = exact_form(ctrl, 1, 0, nullptr, -1))) return rc;       // (Niter = 1, nsel = 1: see exact_only above)
-            }
-        }
-        if (sym == 0 && !fell_back)
+        if (adaptive && (rc = pit_adaptive_finish(sw, fell_back))) return rc;
+        if (sw.sym == 0 && !fell_back)
             hipLaunchKernelGGL((pit_rotate_err_kernel<R>), dim3(sg.S, nsel), dim3(256), 0, g_stream, (Cx<R> *)err, (int64_t)(TrSyms * Niter), (int64_t)it * TrSyms, sg,
-                               (const int64_t *)modes_dev, nsel, (const double *)theta, (const PitCtrl *)ctrl, -1);
+                               (const int64_t *)b.modes_dev, nsel, (const double *)b.theta, (const PitCtrl *)ctrl, -1);
         QH_HIP(hipGetLastError());
     }
     return QH_OK;
