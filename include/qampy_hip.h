@@ -211,7 +211,11 @@ int qh_bps_c128_dev(const void *E, int64_t L, const void *testangles, int64_t p,
  * angles: the grid (A,) real in HBM, as the host builds it (np.linspace(-pi/4, pi/4, A, endpoint=False) in double, cast to
  * the signal's precision), or NULL for a grid formed on the device.  np.unwrap's jump decisions are evaluated with numpy's own
  * operations on the grid values (a jump of exactly half the range depends on their rounding), the running correction is an
- * exact integer prefix sum.  E, Eout (nm, L) complex; ph (nm, L) real; idx (nm, L) int32 scratch/out. */
+ * exact integer prefix sum.  With the host's grid ph carries exactly the quarter turns np.unwrap gives the host layer.  A grid
+ * formed on the device may differ from the host's in the last bit of an entry: a jump of exactly A/2 entries then follows
+ * numpy's rule on the DEVICE's values and may be corrected where the host's is not, or the reverse - a whole quarter turn on
+ * every later symbol of the row.  Pass the host's grid where that matters.
+ * E, Eout (nm, L) complex; ph (nm, L) real; idx (nm, L) int32 scratch/out. */
 int qh_bps_recover_c64_dev(const void *E, int nm, int64_t L, const void *angles, int A, const void *symbols, int M, int N, int32_t *idx,
                            void *ph, void *Eout);
 int qh_bps_recover_c128_dev(const void *E, int nm, int64_t L, const void *angles, int A, const void *symbols, int M, int N, int32_t *idx,
@@ -276,7 +280,9 @@ int qh_vv_recover_c128_dev(const void *E, int nmodes, int64_t L, int N, int M, v
 int qh_partition16_recover_c64_dev(const void *E, int nmodes, int64_t L, int Nblock, void *trace, void *Eout);
 int qh_partition16_recover_c128_dev(const void *E, int nmodes, int64_t L, int Nblock, void *trace, void *Eout);
 /* Tail of pilot_based_cpe_new (qampy/core/pilotbased_receiver.py:318-327): the averaged pilot phases kph (nmodes, nk) at the symbol
- * positions knots (nk, increasing) interpolated linearly to every symbol (np.interp) and taken out: out = E exp(-1j trace); trace in the
+ * positions knots (nk, strictly increasing - the caller's duty: two equal knots divide by zero) interpolated linearly to every symbol by
+ * np.interp's expression in double, slope * (i - knot) + phase with the product and the sum each rounded (numpy's result to the bit
+ * where numpy's build does not fuse the two), and taken out: out = E exp(-1j trace); trace in the
  * signal's complex dtype like the reference returns it.  Host arrays. */
 int qh_pilot_phase_trace_c64(const void *E, int nmodes, int64_t L, const int64_t *knots, const double *kph, int nk, void *out, void *trace);
 int qh_pilot_phase_trace_c128(const void *E, int nmodes, int64_t L, const int64_t *knots, const double *kph, int nk, void *out, void *trace);

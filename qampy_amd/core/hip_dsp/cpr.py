@@ -105,6 +105,8 @@ def pilot_phase_trace(E, knots, knot_phase):
     kph = np.ascontiguousarray(knot_phase, dtype=np.float64)
     if kph.shape != (E.shape[0], knots.size) or knots.size < 1:
         raise ValueError("one phase per mode and knot")
+    if np.any(np.diff(knots.ravel()) <= 0):                       # (the kernel divides by the distance of two knots)
+        raise ValueError("knots must be strictly increasing")
     big = E.nbytes >= _lib.PINNED_MIN_BYTES                       # results through the pinned pool: one DMA at the link rate each
     out = _lib.pinned_empty(E.shape, E.dtype) if big else np.empty_like(E)
     trace = _lib.pinned_empty(E.shape, E.dtype) if big else np.empty_like(E)

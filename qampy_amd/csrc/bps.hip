@@ -1261,6 +1261,10 @@ __global__ void __launch_bounds__(256) pilot_phase_trace_kernel(const Cx<R> *E, 
     if (i <= knots[0]) ph = p[0];
     else if (i >= knots[nk - 1]) ph = p[nk - 1];
     else {
+        // numpy's two roundings, product then sum: fused into one (the compiler's default) the result differs by the rounding of the PRODUCT,
+        // which is many ulps of a result in which the two terms cancel - a third of the samples between two knots, by up to 350 ulp where the
+        // trace crosses zero (tests/test_gpu_bps_unwrap.py)
+#pragma clang fp contract(off)
         int lo = 0, hi = nk - 1;                                   // knots[lo] <= i < knots[hi]
         while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (knots[mid] <= i) lo = mid; else hi = mid; }
         const double slope = (p[hi] - p[lo]) / (double)(knots[hi] - knots[lo]);

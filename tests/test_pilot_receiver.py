@@ -342,3 +342,12 @@ def test_long_pilot_sequence_results_are_complete_arrays(monkeypatch):
     assert np.all(np.isfinite(taps_ref)) and abs(float(foe_ref[0, 0])) > 0
     for taps, foe in runs:
         assert np.array_equal(taps, taps_ref) and np.array_equal(foe, foe_ref)
+
+
+@pytest.mark.parametrize("knots", [[5, 5], [3, 9, 9, 20], [7, 4], [0, 10, 9]])
+def test_pilot_phase_trace_wants_strictly_increasing_knots(knots):
+    """The device kernel divides by the distance of two knots: the wrapper refuses knots that repeat or go back, before anything reaches the device."""
+    from qampy_amd.core import hip_dsp
+    E = np.ones((2, 32), np.complex64)
+    with pytest.raises(ValueError, match="strictly increasing"):
+        hip_dsp.pilot_phase_trace(E, np.array(knots), np.zeros((2, len(knots))))
